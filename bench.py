@@ -211,6 +211,38 @@ def cpu_baseline(model_dir: Path, graph_dir: Path, pcms, streaming: bool, second
             "one_load": steady, "all_cores": all_cores}
 
 
+def dump_outputs(out_dir: Path, res, rec: np.ndarray, sharded: bool) -> None:
+    """--dump-outputs: the 1-best of every utterance as the last timed step handed it to its caller, one .npy per field.  `res`
+    is the step's rs_result (one rank, rs_decode_batch / rs_streams_finish): words and costs are read through the API, uncut.
+    Otherwise (rs_decode_batch_sharded, or records gathered over ranks) the fixed-size records are all the caller gets:
+    rs_result_pack's {status, n_words, ids, cost bits} or the sharded {utterance, status, n_words, ids, cost bits}.
+    Integer fields are stored as float64 (exact); word ids are padded with -1; costs stay float32."""
+    if sharded:
+        rec = rec[np.argsort(rec[:, 0], kind="stable")]
+    head = 1 if sharded else 0                       # the sharded record leads with the utterance index
+    status = rec[:, head].astype(np.float64)
+    n_words = rec[:, head + 1].astype(np.float64)
+    costs = np.ascontiguousarray(rec[:, -2:]).view(np.float32)
+    slots = rec.shape[1] - head - 4
+    words = [list(r[head + 2:head + 2 + min(int(r[head + 1]), slots)]) if r[head] == 0 else [] for r in rec]
+    out = {}
+    if res is not None:
+        n = res.num_utts
+        words = [res.words(u) if status[u] == 0 else [] for u in range(n)]
+        n_words = np.array([len(w) for w in words], np.float64)
+        costs = np.array([res.costs(u) if status[u] == 0 else (0.0, 0.0) for u in range(n)], np.float32).reshape(n, 2)
+        out["num_frames"] = np.array([res.num_frames(u) for u in range(n)], np.float64)
+    width = max([len(w) for w in words] + [1])
+    ids = np.full((len(words), width), -1.0)
+    for u, w in enumerate(words):
+        ids[u, :len(w)] = w
+    out.update(status=status, n_words=n_words, words=ids, graph_cost=np.ascontiguousarray(costs[:, 0]),
+               acoustic_cost=np.ascontiguousarray(costs[:, 1]))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in out.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -228,7 +260,13 @@ def main() -> None:
                     help="rs_decode_opts.prune_output_pdfs=0 for the headline too: evaluate the output layer for every pdf like the "
                          "reference does.  The library's default evaluates it for the pdfs that occur on HCLG arcs only (the search can "
                          "read no others; same words, same costs); a default run reports the all-pdfs figure as `reference_output_layer`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (status, "
+                         "word ids, costs, frames per utterance; float32 / float64): two builds run with the same arguments decode "
+                         "the same inputs and can be compared array for array")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = args.workload
     # (timed steps, warm-up, calls in flight).  Headline: four calls in flight since round 4 -- with the layer GEMMs at two thirds of
     # their round-3 time a fourth call's search fits under the others' stages: 2.08 -> 1.91 ms per step (2, 3, 4, 5 in flight: 2.41,
@@ -596,6 +634,8 @@ def main() -> None:
         t = torch.tensor([elapsed], device=comm_device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), res if world == 1 and not sharded else None, rec, sharded)
 
     def figure(n, secs, note):
         return {"value": audio_seconds * n / secs, "unit": "audio-seconds/s", "ms_per_step": 1000.0 * secs / n, "steps": n, "note": note}

@@ -2,9 +2,9 @@
 CompactLattice table entry the reference's online2-wav-nnet3-latgen-faster writes.  Checked two ways:
 
  * structurally, by a reader of the format written for the tests (tests/lattice_io.py: header, arc type, deterministic on word labels, acyclic);
- * by the REFERENCE's own tools (oracle/_ref, test infrastructure): the bytes go through `lattice-to-nbest |
-   nbest-to-linear` and every path -- words, transition-id alignment, graph and acoustic cost -- is compared with the paths
-   of the reference's lattice for the same case (tests/golden/lattice/*.json, oracle/gen_lattice_golden.py).
+ * by what the REFERENCE's `lattice-to-nbest | nbest-to-linear` lists for the bytes (tests/lattice_io.reference_paths, pinned to
+   those tools' output in tests/test_lattice_cpu.py): every path -- words, transition-id alignment, graph and acoustic cost --
+   is compared with the paths of the reference's lattice for the same case (tests/golden/lattice/*.json, oracle/gen_lattice_golden.py).
 """
 import json
 from pathlib import Path
@@ -39,10 +39,10 @@ def test_lattice_entry_matches_reference_lattice(case_cache, tmp_path, name):
     for row in arcs:
         labels = [a[0] for a in row if a[0] != 0]
         assert len(labels) == len(set(labels)), "not deterministic on word labels"
-    # ---- the reference's tools read it and list the same paths as for the reference's own lattice
+    # ---- its n-best list is the reference's own lattice's
     ark = tmp_path / "lat.ark"
     ark.write_bytes(entry)
-    mine = reference_paths(ark, golden["n_requested"], tmp_path)
+    mine = reference_paths(ark, golden["n_requested"])
     ref = golden["paths"]
     best = ref[0]["graph"] + ref[0]["acoustic"]
     beam = float(opts.lattice_beam)
@@ -86,7 +86,7 @@ def test_lattice_batch_and_scale(case_cache, tmp_path):
     res = model.decode_batch(pcms, nbest=3)
     ark = tmp_path / "all.ark"
     ark.write_bytes(b"".join(res.lattice(u, f"utt{u}") for u in range(3)))
-    paths = reference_paths(ark, 3, tmp_path)
+    paths = reference_paths(ark, 3)
     keys_seen = [p["words"] for p in paths]
     expect = [res.words(u, k) for u in range(3) for k in range(res.num_hyps(u))]
     assert keys_seen == expect
@@ -94,7 +94,7 @@ def test_lattice_batch_and_scale(case_cache, tmp_path):
     r2 = half.decode_batch(pcms[:1], nbest=1)
     _, finals, arcs = read_compact_lattice(r2.lattice(0, "k"), "k")
     ark.write_bytes(r2.lattice(0, "k"))
-    p = reference_paths(ark, 1, tmp_path)[0]
+    p = reference_paths(ark, 1)[0]
     gc, ac = r2.costs(0, 0)
     assert p["words"] == r2.words(0, 0)
     assert abs(p["graph"] - gc) < 2e-3 * max(1.0, abs(gc)) and abs(p["acoustic"] - ac) < 2e-3 * max(1.0, abs(ac))

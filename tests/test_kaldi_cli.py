@@ -1,6 +1,6 @@
 """The Kaldi-named executables over the HIP library (rhasspy_speech_amd/bin, kaldi_cli.py): command lines exactly as the
-reference builds them (transcribe_wav.py:46-74, transcribe_stream.py:53-64), output read by the REFERENCE's own
-lattice-to-nbest | nbest-to-linear (oracle/_ref, test infrastructure) as in the reference's pipelines."""
+reference builds them (transcribe_wav.py:46-74, transcribe_stream.py:53-64), output read the way the reference's pipelines
+read it, `lattice-to-nbest | nbest-to-linear` (tests/lattice_io.nbest_text, pinned to those tools' output in tests/test_lattice_cpu.py)."""
 import os
 import subprocess
 import sys
@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests import cases
-from tests.lattice_io import BIN
+from tests.lattice_io import nbest_text
 
 REPO = Path(__file__).resolve().parent.parent
 SHIMS = REPO / "rhasspy_speech_amd" / "bin"
@@ -69,26 +69,17 @@ def test_wav_executable_checks_what_the_binary_checks(case_cache, tmp_path):
     assert p.returncode != 0 and p.stdout == b"" and b"adaptation state" in p.stderr, p.stderr
 
 
-def _nbest_text(lattice: bytes, n: int, env) -> bytes:
-    sh = f"lattice-to-nbest --n={n} --acoustic-scale=1.0 ark:- ark:- | nbest-to-linear ark:- ark:/dev/null ark,t:-"
-    p = subprocess.run(["bash", "-c", sh], input=lattice, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    assert p.returncode == 0, p.stderr.decode()[-2000:]
-    return p.stdout
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["tiny_u0", "zam_u1", "tiny_arpa_u7"])
 def test_wav_executable_in_the_reference_pipeline(case_cache, name):
     from rhasspy_speech_amd import _lib
-    if not (BIN / "lattice-to-nbest").exists():
-        pytest.fail("oracle/_ref is not built (bash oracle/build_ref.sh in the build container; it travels with the snapshot)")
     model_dir, graph_dir, wav, pcm = case_cache(name)
     o = cases.CASES[name].get("opts", {})
     argv = reference_wav_argv(model_dir, graph_dir, wav, o.get("max_active", 7000), o.get("lattice_beam", 8.0), o.get("beam", 24.0))
-    env = dict(os.environ, PATH=f"{SHIMS}:{BIN}:{os.environ['PATH']}")       # the executables first, the Kaldi tools behind them
+    env = dict(os.environ, PATH=f"{SHIMS}:{os.environ['PATH']}")
     p = subprocess.run(argv, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
-    text = _nbest_text(p.stdout, cases.NBEST, env)
+    text = nbest_text(p.stdout, cases.NBEST)
     model = _lib.Model(model_dir, graph_dir, _lib.default_opts(**o))
     res = model.decode_batch([pcm], nbest=cases.NBEST)
     assert text == res.text(0, "utt") and text.startswith(b"utt-1")
@@ -102,10 +93,10 @@ def test_stream_executable_in_the_reference_pipeline(case_cache, tmp_path):
     argv = ["online2-cli-nnet3-decode-faster", f"--config={model_dir}/model/online/conf/online.conf", "--max-active=7000",
             "--lattice-beam=8.0", "--acoustic-scale=1.0", "--beam=24.0", f"{model_dir}/model/model/final.mdl", f"{graph_dir}/HCLG.fst",
             f"{graph_dir}/words.txt", f"ark:{lat}"]
-    env = dict(os.environ, PATH=f"{SHIMS}:{BIN}:{os.environ['PATH']}")
+    env = dict(os.environ, PATH=f"{SHIMS}:{os.environ['PATH']}")
     p = subprocess.run(argv, env=env, input=np.asarray(pcm, dtype="<i2").tobytes(), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
-    text = _nbest_text(lat.read_bytes(), 3, env)
+    text = nbest_text(lat.read_bytes(), 3)
     stream = _lib.Stream(_lib.Model(model_dir, graph_dir, _lib.default_opts()))
     stream.accept(pcm)
     assert text == stream.finish(nbest=3).text(0, "utt") and text.startswith(b"utt-1")

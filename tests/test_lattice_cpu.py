@@ -3,37 +3,21 @@ CompactLatticeArkEntry code rs_result_lattice uses, on raw lattices made here.
 
 Checked against a brute-force enumeration written in this file (every path of the raw lattice, grouped by word sequence,
 best alignment per sequence under LatticeWeight's order: total cost, then graph cost -- fstext/lattice-weight.h:294-307),
-and, when oracle/_ref is built, by pushing the bytes through the REFERENCE's lattice-to-nbest | nbest-to-linear.
+and by the paths the REFERENCE's lattice-to-nbest | nbest-to-linear listed for the same bytes (tests/golden/lattice_tools.json,
+oracle/gen_lattice_tools_golden.py), which also pins the n-best lister of tests/lattice_io.py that the GPU tests read lattices with.
 """
+import json
 import math
 
 import numpy as np
 import pytest
 
-from tests.lattice_io import BIN, read_compact_lattice, reference_paths
+from tests import cases
+from tests.lattice_io import nbest_text, random_raw_lattice, read_compact_lattice, reference_paths
+
+TOOLS = json.loads((cases.GOLDEN / "lattice_tools.json").read_text())
 
 INF = float("inf")
-
-
-def random_raw_lattice(rng, n_states, fan, n_words, eps_rate=0.3, quantum=0.0):
-    """Acyclic state-level lattice in time order: arcs go forward, a share of them carry no word (label 0).  quantum > 0
-    rounds the costs to multiples of it, which makes equal-cost alignments common."""
-    def cost(scale):
-        c = rng.random() * scale
-        return float(np.float32(round(c / quantum) * quantum if quantum else c))
-    arcs = []
-    tid = 1
-    for s in range(n_states - 1):
-        for _ in range(int(rng.integers(1, fan + 1))):
-            d = int(rng.integers(s + 1, min(n_states, s + 4)))
-            w = 0 if rng.random() < eps_rate else int(rng.integers(1, n_words + 1))
-            arcs.append((s, d, w, tid, cost(3), cost(5)))
-            tid += 1
-    final = [INF] * n_states
-    final[n_states - 1] = cost(1)
-    if n_states > 3:
-        final[n_states - 2] = cost(2)
-    return arcs, final
 
 
 def brute_force(n_states, start, final, arcs):
@@ -133,24 +117,53 @@ def test_bad_arguments_are_errors():
         _lib.lattice_entry_from_raw(2, 0, [INF, 0.0], [(0, 9, 1, 1, 0.0, 0.0)], 10.0)
 
 
-@pytest.mark.skipif(not (BIN / "lattice-to-nbest").exists(), reason="oracle/_ref is not built (bash oracle/build_ref.sh)")
-@pytest.mark.parametrize("seed", [100, 101, 102, 103])
-def test_reference_tools_list_the_same_paths(seed, tmp_path):
+def _entry(seed, n_states, key="utt"):
     from rhasspy_speech_amd import _lib
     rng = np.random.default_rng(seed)
-    n_states = int(rng.integers(5, 10))
+    n_states = n_states or int(rng.integers(5, 10))
     arcs, final = random_raw_lattice(rng, n_states, fan=3, n_words=4)
+    return _lib.lattice_entry_from_raw(n_states, 0, final, arcs, 1e9, key=key), n_states, arcs, final
+
+
+@pytest.mark.parametrize("seed", [100, 101, 102, 103])
+def test_reference_tools_list_the_same_paths(seed, tmp_path):
+    """The reference's tools list every path of the entry (stored): one per word sequence, in cost order, each the best
+    alignment of the raw lattice; the lister of tests/lattice_io.py lists the same."""
+    rec = next(r for r in TOOLS["lists"] if r["seed"] == seed)
+    entry, n_states, arcs, final = _entry(seed, None)
     want = brute_force(n_states, 0, final, arcs)
     ark = tmp_path / "lat.ark"
-    ark.write_bytes(_lib.lattice_entry_from_raw(n_states, 0, final, arcs, 1e9, key="utt"))
-    listed = reference_paths(ark, 10000, tmp_path)
-    assert len(listed) == len(want)
-    totals = [p["graph"] + p["acoustic"] for p in listed]
-    assert totals == sorted(totals)
-    for p in listed:
-        g, a, tids = want[tuple(p["words"])]
-        assert p["ali"] == tids
-        assert p["graph"] == pytest.approx(g, abs=1e-3) and p["acoustic"] == pytest.approx(a, abs=1e-3)
+    ark.write_bytes(entry)
+    for listed in (rec["paths"], reference_paths(ark, rec["n"])):
+        assert len(listed) == len(want)
+        totals = [p["graph"] + p["acoustic"] for p in listed]
+        assert totals == sorted(totals)
+        for p in listed:
+            g, a, tids = want[tuple(p["words"])]
+            assert p["ali"] == tids
+            assert p["graph"] == pytest.approx(g, abs=1e-3) and p["acoustic"] == pytest.approx(a, abs=1e-3)
+
+
+@pytest.mark.parametrize("rec", TOOLS["lists"], ids=lambda r: f"seed{r['seed']}")
+def test_nbest_lister_is_the_reference_tools(rec, tmp_path):
+    """Whole lists and lists cut at n paths of larger lattices: words, alignment and costs as the reference's tools printed them."""
+    entry, n_states, _, _ = _entry(rec["seed"], rec["n_states"] if rec["n"] < 10000 else None)
+    assert n_states == rec["n_states"]
+    ark = tmp_path / "lat.ark"
+    ark.write_bytes(entry)
+    got = reference_paths(ark, rec["n"])
+    assert [(p["words"], p["ali"]) for p in got] == [(p["words"], p["ali"]) for p in rec["paths"]]
+    for p, q in zip(got, rec["paths"]):
+        assert p["graph"] == pytest.approx(q["graph"], abs=1e-3) and p["acoustic"] == pytest.approx(q["acoustic"], abs=1e-3)
+
+
+def test_nbest_text_of_a_table_is_the_reference_tools():
+    """Several entries in one table, the last a single final state (a path without words): the exact bytes."""
+    from rhasspy_speech_amd import _lib
+    t = TOOLS["table"]
+    table = b"".join(_entry(seed, None, key=f"utt{i}")[0] for i, seed in enumerate(t["seeds"]))
+    table += _lib.lattice_entry_from_raw(1, 0, [0.75], [], 10.0, key="empty")
+    assert nbest_text(table, t["n"]) == t["text"].encode()
 
 
 def test_subset_reached_again_with_a_better_cost_is_expanded_again():
