@@ -153,6 +153,23 @@ int rs_streams_accept(rs_stream *const *streams, const int16_t *const *pcm, cons
 int rs_streams_advance(rs_stream *const *streams, int32_t n_streams);
 int rs_streams_finish(rs_stream *const *streams, int32_t n_streams, int32_t nbest, float lattice_acoustic_scale,
                       rs_result **out);
+/* Partial results = SingleUtteranceNnet3Decoder::GetBestPath(end_of_utterance = false) (online-nnet3-decoding.cc:82-85), what
+ * online2-tcp-nnet3-decode-faster prints as its temporary transcript.  rs_streams_partial does, batched over the listed streams, the
+ * device work rs_streams_advance would do -- for every completed tick, without the 16-tick coalescing -- then returns, per stream,
+ * the best path over the decoder frames searched so far with NO final costs: an ordinary rs_result with one hypothesis per stream
+ * (utterance i = streams[i]): words = the non-zero output labels along the path, graph / acoustic cost with the per-frame cost
+ * offsets removed (TraceBackBestPath), rs_result_num_frames = the decoder frames searched so far (NumFramesDecoded()).  A stream
+ * with no decoded frame yet gets 0 words, cost 0 and 0 frames, status RS_OK (the reference asserts there).  The streams stay open,
+ * and a later rs_streams_finish gives bit for bit what it gives without the partial calls.  A finished, freed or failed stream is
+ * refused like by the other stream calls; so are streams opened with RS_STREAM_BATCH=1.
+ * Ties between equal frontier costs go to the lowest state index (the reference keeps the first token of its list).
+ * rs_result_counters out[0] of a partial result = back-pointer rows the traceback read; out[1..6] = 0.
+ * Cost: on grammar graphs the register-resident search holds (<= 5000 states), the traceback reads the rows between the frontier and
+ * the point where the best path joins the previous call's best path (cached per stream), not the whole stream while the best
+ * hypothesis holds (RS_PARTIAL_FULL_WALK=1: always the whole stream, same results).  For streams whose search is deferred to
+ * finish (larger graphs, RS_DECODER=dense|sparse|hash) a partial runs that search over all frames so far: O(frames) per call. */
+int rs_streams_partial(rs_stream *const *streams, int32_t n_streams, rs_result **out);
+int rs_stream_partial(rs_stream *stream, rs_result **out);
 
 /* Result access.  Hypotheses of utterance `utt` are ordered best first, like the keys utt-1..utt-n that
  * lattice-to-nbest writes (lattice-to-nbest.cc:100-106). */

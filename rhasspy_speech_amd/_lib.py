@@ -33,7 +33,8 @@ FIXED_ONLINE, FIXED_DO_ENDPOINTING, FIXED_EXTRA_LEFT_CONTEXT_INITIAL, FIXED_PRUN
 EXPORTS = [
     "rs_default_opts", "rs_last_error", "rs_model_load_files", "rs_model_load", "rs_model_to_device", "rs_model_free",
     "rs_model_describe", "rs_model_check_sample_rate", "rs_decode_batch", "rs_decode_batch_device", "rs_decode_batch_sharded", "rs_shard_gather", "rs_stream_open", "rs_stream_accept",
-    "rs_stream_finish", "rs_stream_free", "rs_streams_accept", "rs_streams_advance", "rs_streams_finish", "rs_result_num_utts", "rs_result_num_hyps",
+    "rs_stream_finish", "rs_stream_free", "rs_streams_accept", "rs_streams_advance", "rs_streams_finish",
+    "rs_streams_partial", "rs_stream_partial", "rs_result_num_utts", "rs_result_num_hyps",
     "rs_result_num_frames", "rs_result_words", "rs_result_costs", "rs_result_text", "rs_result_lattice", "rs_result_matrix",
     "rs_result_counters", "rs_result_timings", "rs_result_pack", "rs_result_free",
     "rs_mkgraph", "rs_fst_tool", "rs_fuzzy_open", "rs_fuzzy_match", "rs_result_fuzzy", "rs_fuzzy_free", "rs_lattice_entry_from_raw",
@@ -71,6 +72,8 @@ def load_library() -> C.CDLL:
     lib.rs_streams_accept.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), i32]
     lib.rs_streams_advance.argtypes = [C.POINTER(vp), i32]
     lib.rs_streams_finish.argtypes = [C.POINTER(vp), i32, i32, f32, C.POINTER(vp)]
+    lib.rs_streams_partial.argtypes = [C.POINTER(vp), i32, C.POINTER(vp)]
+    lib.rs_stream_partial.argtypes = [vp, C.POINTER(vp)]
     lib.rs_result_num_utts.argtypes = [vp]
     lib.rs_result_num_hyps.argtypes = [vp, i32]
     lib.rs_result_num_frames.argtypes = [vp, i32]
@@ -347,6 +350,13 @@ class Stream:
         arr = (C.c_void_p * 1)(self._h)
         _check(lib().rs_streams_advance(arr, 1))
 
+    def partial(self) -> Result:
+        """rs_stream_partial: the device work the audio accepted so far allows (every tick), then the best path over the frames
+        searched so far without final costs (one hypothesis; the stream stays open)."""
+        out = C.c_void_p()
+        _check(lib().rs_stream_partial(self._h, C.byref(out)))
+        return Result(out)
+
     def finish(self, nbest: int = 1, lattice_acoustic_scale: float = 1.0) -> Result:
         out = C.c_void_p()
         _check(lib().rs_stream_finish(self._h, nbest, lattice_acoustic_scale, C.byref(out)))
@@ -408,6 +418,14 @@ def finish_streams(streams: Sequence[Stream], nbest: int = 1, lattice_acoustic_s
     arr = (C.c_void_p * len(streams))(*[s._h for s in streams])
     out = C.c_void_p()
     _check(lib().rs_streams_finish(arr, len(streams), nbest, lattice_acoustic_scale, C.byref(out)))
+    return Result(out)
+
+
+def partial_streams(streams: Sequence[Stream]) -> Result:
+    """rs_streams_partial: per stream the best path so far without final costs, batched; utterance i of the result = streams[i]."""
+    arr = (C.c_void_p * len(streams))(*[s._h for s in streams])
+    out = C.c_void_p()
+    _check(lib().rs_streams_partial(arr, len(streams), C.byref(out)))
     return Result(out)
 
 

@@ -352,6 +352,32 @@ int rs_streams_finish(rs_stream *const *streams, int32_t n_streams, int32_t nbes
   });
 }
 
+int rs_streams_partial(rs_stream *const *streams, int32_t n_streams, rs_result **out) {
+  if (!out) return ArgError("rs_streams_partial: bad argument");
+  const int rc = CheckStreams(streams, n_streams, "rs_streams_partial");
+  if (rc != RS_OK) return rc;
+  if (n_streams == 0) return ArgError("rs_streams_partial: no streams");
+  if (streams[0]->keep_pcm) return ArgError("rs_streams_partial: streams opened with RS_STREAM_BATCH=1 are only decoded at finish");
+  return Guard([&]() {
+    std::unique_ptr<rs_result> res(new rs_result());
+    res->r.reset(new rs::Result());
+    // (like an advance: one that throws may have moved the chunk schedule of some streams without writing their rows)
+    try {
+      streams[0]->model->m->StreamsPartial(streams, n_streams, res->r.get());
+    } catch (...) {
+      for (int i = 0; i < n_streams; i++) streams[i]->failed = true;
+      throw;
+    }
+    *out = res.release();
+    return RS_OK;
+  });
+}
+
+int rs_stream_partial(rs_stream *stream, rs_result **out) {
+  rs_stream *one[1] = {stream};
+  return rs_streams_partial(one, 1, out);
+}
+
 int rs_stream_finish(rs_stream *stream, int32_t nbest, float lattice_acoustic_scale, rs_result **out) {
   rs_stream *one[1] = {stream};
   return rs_streams_finish(one, 1, nbest, lattice_acoustic_scale, out);

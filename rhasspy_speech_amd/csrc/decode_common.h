@@ -221,7 +221,7 @@ __device__ void FinishUtterance(Red<NT / 64> &red, const HclgDev &h, const Batch
                                 const DenseWork &w, const float *cost_cur, const int *bp, const float *finfo, unsigned char *smem,
                                 int smem_bytes, int u, int T, int S, size_t ll_base, int error, unsigned long long n_expanded,
                                 unsigned long long n_arcs, unsigned long long n_insert, unsigned long long n_alive,
-                                int max_active_frames, int min_active_frames, size_t counter_slot) {
+                                int max_active_frames, int min_active_frames, size_t counter_slot, bool no_final = false) {
   constexpr int NW = NT / 64;
   const int tid = threadIdx.x;
   const float INF = INFINITY;
@@ -231,7 +231,7 @@ __device__ void FinishUtterance(Red<NT / 64> &red, const HclgDev &h, const Batch
     for (int s = tid; s < S; s += NT) {
       const float c = cost_cur[s];
       if (!(c < INF)) continue;
-      const float wf = c + h.final_cost[s];
+      const float wf = no_final ? INF : c + h.final_cost[s];      // (no_final: DecodeOptsDev::no_final)
       if (wf < lv1 || (wf == lv1 && s < li1)) { lv1 = wf; li1 = s; }
       if (c < lv2 || (c == lv2 && s < li2)) { lv2 = c; li2 = s; }
     }

@@ -465,7 +465,7 @@ __global__ __launch_bounds__(NT) void DecodeKernel(HclgDev h, DecodeOptsDev o, B
     int li1 = 0x7fffffff, li2 = 0x7fffffff;
     for (int i = tid; i < n_cur; i += NT) {
       const float cst = __int_as_float(cur[i].y);
-      const float wf = cst + h.final_cost[cur[i].x];
+      const float wf = o.no_final ? INF : cst + h.final_cost[cur[i].x];      // (no_final: partial results of streams)
       if (wf < lv1 || (wf == lv1 && i < li1)) { lv1 = wf; li1 = i; }
       if (cst < lv2 || (cst == lv2 && i < li2)) { lv2 = cst; li2 = i; }
     }

@@ -787,7 +787,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     for (int i = tid; i < n_cur; i += NT) {
       const int2 t2 = *reinterpret_cast<const int2 *>(&cur[i]);
       const float cst = __int_as_float(t2.y);
-      const float wf = cst + h.final_cost[t2.x];
+      const float wf = o.no_final ? INF : cst + h.final_cost[t2.x];      // (no_final: partial results of streams)
       if (wf < lv1 || (wf == lv1 && i < li1)) { lv1 = wf; li1 = i; }
       if (cst < lv2 || (cst == lv2 && i < li2)) { lv2 = cst; li2 = i; }
     }

@@ -1301,13 +1301,13 @@ void Model::IvecChunkChain(DeviceArena &arena, const BatchGeom &g, int n, int K,
 // ------------------------------------------------------------------------------------------------ search
 // Which search kernel a call runs and the work buffers it needs (all from the call's arena).  Shared by the batch path
 // (DecodeGroup) and the end of a stream (stream.cc), whose log-likelihoods live in the stream pool.
-size_t Model::PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp) const {
+size_t Model::PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only) const {
   const int S = hclg_.num_states();
   sp->S = S; sp->n_utts = n_utts; sp->maxT = maxT; sp->max_words = 1024;
   // The reference un-scales the lattice's acoustic costs before lattice-to-nbest ranks its paths (online2-wav-nnet3-latgen-
   // faster.cc:290-293), so with a decodable --acoustic-scale other than 1 even the 1-best is chosen on the lattice.
   sp->unscale = opts_.acoustic_scale != 1.0f && opts_.acoustic_scale != 0.0f;
-  sp->want_lattice = (nbest > 1 || lat_scale != 1.0f || opts_.emit_lattice != 0 || sp->unscale);
+  sp->want_lattice = !best_path_only && (nbest > 1 || lat_scale != 1.0f || opts_.emit_lattice != 0 || sp->unscale);      // (best_path_only: partial results)
   sp->use_reg = reg_dev_.nt != 0 && !sp->want_lattice && !force_sparse_ && (decoder_choice_ == 0 || decoder_choice_ == 1);
   sp->use_dense = dense_ok_ && !sp->want_lattice && !force_sparse_ && decoder_choice_ != 3;
   // A lattice needs every token of every frame, which the token-list searches keep and the register-resident one does not (5.8 ms

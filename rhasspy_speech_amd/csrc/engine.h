@@ -154,7 +154,11 @@ class Model {
   void StreamOpen(rs_stream *st);
   void StreamClose(rs_stream *st);
   void StreamsAdvance(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res);
-  void StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res);      // pool_mu_ held
+  void StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res,
+                            bool every_tick = false);      // pool_mu_ held; every_tick: no min_ticks coalescing
+  // rs_streams_partial: the advance the accepted samples allow (every tick), then the best path over the frames searched so far
+  // without final costs, one hypothesis per stream in `res`; the streams stay open
+  void StreamsPartial(rs_stream *const *streams, int n, Result *res);
   void StreamsPoisonAll(const std::string &why = std::string());          // pool_mu_ held
 
  private:
@@ -172,7 +176,7 @@ class Model {
   size_t ImageBytes(int rows) const;
   std::vector<ActImage> AllocImages(DeviceArena &arena, int rows) const;
   std::vector<char> buf_image_, buf_f32_;      // per nnet buffer: has an operand image / is (also) read as plain floats
-  size_t PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp) const;
+  size_t PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only = false) const;
   void AllocSearch(SearchPlan *sp, DeviceArena &arena, hipStream_t s, bool pooled_frames = false) const;
   void LaunchSearch(SearchPlan *sp, DeviceArena &arena, const BatchGeom &g, const float *ll, int ll_ld, hipStream_t s) const;
   void CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const BatchGeom &g, const int *T, const float *ll, int ll_ld, int nbest,
@@ -237,6 +241,7 @@ class Model {
   void StreamsDrain(StreamPool *p, float *extra);
   void IssuerSync(StreamPool *p);     // everything handed to the pool's issuing thread has been queued; ITS failure poisons the open streams, then rethrows
   void StreamGrow(rs_stream *st, int need_frames);
+  void StreamsPartialLocked(rs_stream *const *streams, int n, Result *res);      // pool_mu_ held
   // The split-fp16 layer GEMMs carry activations below 65520 in magnitude (nnet_gemm_b3.hip).  A kernel that meets a larger
   // one sets the flag of the decode context it runs for (DecodeContext::gemm_ovf: host memory the device writes to); a batch
   // call that finds it set after its wait repeats itself on the exact-FP32 kernels (a model whose calls keep doing that changes

@@ -282,6 +282,8 @@ struct DecodeOptsDev {
   int max_active, min_active;
   int exact_order;            // rs_decode_opts.exact_token_order: the reference's order-dependent token creation (decode_reg.hip), where the graph allows it
   int no_commit_hist = 0;     // RS_REG_NO_HIST=1 (tests): RegDecodeKernel's GetCutoff always selects the slow way (KthFromHist)
+  int no_final = 0;           // partial results of streams (rs_streams_partial): the final stage ignores final costs -- the
+                              // "not reached" branch every search kernel already has (GetBestPath(use_final_probs = false))
 };
 struct DecodeWork {
   // per utterance
@@ -418,6 +420,39 @@ struct LatticeWork {
 void LaunchCompactArcs(const LatArc *arcs, int utt_cap, const int *counts, int n_utts, LatArc *dst, hipStream_t s);
 void LaunchLatticePrune(const HclgDev &h, const DecodeOptsDev &o, const BatchGeom &g, const float *loglikes, int ld,
                         const DecodeWork &w, const LatticeWork &lw, hipStream_t s);
+
+// Partial results of register-resident streams (decode_partial.hip, rs_streams_partial): per listed stream, the best path over
+// the frames searched so far without final costs, from the parked frontier costs and the stream's back-pointer rows in the pool.
+// The traceback is bounded by the PREVIOUS call's best path, kept per frame row: back-pointer rows are immutable once written,
+// so where the new best chain arrives in a row at the state the previous path left that row from, everything below is the previous
+// path -- its words and cost sums are taken from the cache instead of being walked again.
+struct PartialRow {           // per pool row f of a stream (moves with the rows): the cached best path at frame f
+  int exit_state;             // the state the path leaves row f from (f = the path's last frame: its frontier state)
+  int nwords;                 // words of the path before that point (PartialWork::anchor_words)
+  double graph, acoustic;     // its cost sums there: double sums over the arcs in path order, first frame first
+};
+struct PartialAnchor {        // per pool slot; read and written by the partial kernel only (no advance or finish reads it)
+  int frames1;                // the cached path's last frame + 1, stream-relative; 0 = no cached path
+  int pad[3];
+};
+struct PartialWork {
+  const float *state_cost;    // pool: parked token costs, 2 S + 4 per slot (DenseWork::state_cost)
+  const int *bp;              // pool: back-pointer rows [row][S]
+  const float *frame_info;    // pool: per-row {cost offset, ...}
+  const float *loglikes;      // pool: log-likelihood rows
+  int ld;
+  const int *slot, *pool_row, *num_frames;      // per listed stream: its slot, first pool row, decoder frames searched
+  PartialAnchor *anchor;      // [slot]
+  PartialRow *rows;           // [pool row]
+  int *anchor_words;          // [slot][max_words]: the cached path's words
+  int *out_words, *out_nwords;                  // result records in CollectResults' layout (DecodeWork::out_*)
+  float *out_costs;
+  long long *counters;        // [u][8]: [0] = back-pointer rows read, [7] = 2 when the search had lost every token
+  int max_words;
+  int *path, path_cap;        // [u][path_cap][2] scratch: (arc, frame) pairs, last arc first
+  int full_walk;              // RS_PARTIAL_FULL_WALK=1: ignore (and leave) the cache, walk the best chain down to frame 0
+};
+void LaunchPartialReg(const HclgDev &h, const PartialWork &w, int n_streams, hipStream_t s);
 
 void LaunchLdsPoison(unsigned *sink, hipStream_t s);   // -DRS_TUNING builds only: profiles/micro/poison_kernels.hip
 

@@ -147,6 +147,12 @@ struct StreamPool {
   int max_slots = 0;
   double *lin = nullptr, *quad = nullptr, *numf = nullptr, *x = nullptr, *cmvn_iv = nullptr, *cmvn_nn = nullptr;
   long long *dec_ctr = nullptr;
+  // rs_streams_partial on register-resident streams (decode_partial.hip): the previous call's best path per row, its length and
+  // words per slot
+  static constexpr int kPartialWords = 1024;          // = SearchPlan::max_words: a partial result holds as many words as a final one
+  PartialRow *prow = nullptr;
+  PartialAnchor *anchor = nullptr;
+  int *anchor_words = nullptr;
   std::vector<int> free_slots;
   std::map<int, int> free_rows;  // start -> length
   std::vector<void *> owned;
@@ -267,6 +273,9 @@ StreamPool *Model::Pool() {
     p->bp = static_cast<int *>(dalloc(R * p->S * 4));
     p->finfo = static_cast<float *>(dalloc(R * 16));
     p->dec_state = static_cast<float *>(dalloc((size_t)p->max_slots * (2 * (size_t)p->S + 4) * 4));
+    p->prow = static_cast<PartialRow *>(dalloc(R * sizeof(PartialRow)));
+    p->anchor = static_cast<PartialAnchor *>(dalloc((size_t)p->max_slots * sizeof(PartialAnchor)));
+    p->anchor_words = static_cast<int *>(dalloc((size_t)p->max_slots * StreamPool::kPartialWords * 4));
   }
   p->dec_ctr = static_cast<long long *>(dalloc((size_t)p->max_slots * 64));
   if (fc_.ie.present) {
@@ -372,6 +381,7 @@ void Model::StreamOpen(rs_stream *st) {
     LaunchIvecInit(ivec_dev_, 1, p->lin + (size_t)st->slot * Di, p->quad + (size_t)st->slot * usz, p->x + (size_t)st->slot * Di, p->numf + st->slot, p->qi);      // (the iVector steps' queue: the estimator state is its)
   }
   RS_HIP(hipMemsetAsync(p->dec_ctr + (size_t)st->slot * 8, 0, 64, p->qc));      // (the search's queue)
+  if (p->anchor) RS_HIP(hipMemsetAsync(p->anchor + st->slot, 0, sizeof(PartialAnchor), p->qc));      // no cached path yet (partials run on qc too)
   st->open = true;
   p->open_streams.push_back(st);
 }
@@ -420,7 +430,7 @@ void Model::StreamGrow(rs_stream *st, int need_frames) {
                                     hipMemcpyDeviceToDevice, p->q));
   };
   mv(p->raw, (size_t)p->ld_c * 4); mv(p->cm, (size_t)p->ld_c * 4); mv(p->nn_in, (size_t)p->ld_c * 4); mv(p->ll, (size_t)p->ld_ll * 4);
-  mv(p->bp, (size_t)p->S * 4); mv(p->finfo, 16);
+  mv(p->bp, (size_t)p->S * 4); mv(p->finfo, 16); mv(p->prow, sizeof(PartialRow));
   if (p->ivec)
     RS_HIP(hipMemcpyAsync(p->ivec + (size_t)(row0 / p->chunk) * p->ld_i, p->ivec + (size_t)(st->row0 / p->chunk) * p->ld_i,
                           (size_t)(st->cap / p->chunk) * p->ld_i * 4, hipMemcpyDeviceToDevice, p->q));
@@ -446,7 +456,7 @@ void Model::StreamsAdvance(rs_stream *const *streams, int n, bool final, int nbe
   }
 }
 
-void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res) {
+void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res, bool every_tick) {
   StreamPool *p = Pool();
   RS_HIP(hipSetDevice(opts_.device_id));
   // queues: qa = features + iVectors (stage A), q = acoustic model + search (stage B, behind stage A's event); consecutive
@@ -456,7 +466,7 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
   // a call that brings less than min_ticks ticks of new audio on every stream leaves it to the next one.  The chunk / iVector
   // schedule is a function of the sample counts, not of the calls (the tick loop below): same rows, same results as with one
   // advance per tick or one at the end (the three delivery patterns of the stream tests).  RS_STREAM_MIN_TICKS=1: every call works.
-  if (!final && p->min_ticks > 1) {
+  if (!final && !every_tick && p->min_ticks > 1) {
     long most = 0;
     for (int i = 0; i < n; i++) most = std::max(most, (long)(streams[i]->n_samples / 1024) - streams[i]->ticks_done);
     if (most < p->min_ticks) return;
@@ -925,6 +935,114 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
     for (float &v : p->host_ms) v = 0.f;
   }
   for (float &v : p->stage_ms) v = 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------------------- partial results
+// rs_streams_partial: what rs_streams_advance does, for every tick the accepted samples complete (no coalescing: a caller that
+// asks for a partial wants the frames its audio allows), then per stream the best path over the decoder frames searched so far
+// without final costs (GetBestPath(end_of_utterance = false)).
+//   * register-resident streams: PartialRegKernel (decode_partial.hip) over the parked frontier and the back-pointer rows in the
+//     pool; the previous call's best path, cached per row, keeps each call's traceback to the frames since that path;
+//   * streams whose search is deferred to finish (graphs the register-resident search cannot hold, RS_DECODER=dense|sparse|hash):
+//     the finish-time search over the log-likelihood rows so far in a scratch arena, its final stage told to ignore final costs
+//     (DecodeOptsDev::no_final).  O(frames so far) per call.
+// Nothing an advance or a finish reads is written: a later rs_streams_finish gives what it gives without the partial calls.
+void Model::StreamsPartial(rs_stream *const *streams, int n, Result *res) {
+  std::lock_guard<std::mutex> lk(pool_mu_);
+  try {
+    StreamsPartialLocked(streams, n, res);
+  } catch (const DeviceError &) {
+    StreamsPoisonAll();
+    throw;
+  } catch (...) {
+    if (pool_) { pool_->issuer.Drain(false); (void)hipStreamSynchronize(pool_->qa); (void)hipStreamSynchronize(pool_->qi); (void)hipStreamSynchronize(pool_->q); (void)hipStreamSynchronize(pool_->qc); }
+    throw;
+  }
+}
+
+void Model::StreamsPartialLocked(rs_stream *const *streams, int n, Result *res) {
+  StreamPool *p = Pool();
+  RS_HIP(hipSetDevice(opts_.device_id));
+  bool more = false;
+  for (int i = 0; i < n; i++) more = more || streams[i]->n_samples / 1024 > streams[i]->ticks_done;
+  if (more) StreamsAdvanceLocked(streams, n, /*final=*/false, 1, 1.0f, nullptr, /*every_tick=*/true);
+  StreamsDrain(p, nullptr);        // every advance has finished: the arena sets are free, the frontier and rows are in place
+  const int fsf = opts_.frame_subsampling_factor, S = p->S;
+  std::vector<int> T(n), slots(n), row0s(n);
+  int maxT = 0;
+  for (int i = 0; i < n; i++) {
+    const rs_stream &st = *streams[i];
+    T[i] = (p->reg && !st.dec_started) ? 0 : (st.ll_done + fsf - 1) / fsf;      // NumFramesDecoded()
+    slots[i] = st.slot;
+    row0s[i] = st.row0;
+    maxT = std::max(maxT, T[i]);
+  }
+  DecodeContext &cx = *static_cast<DecodeContext *>(p->cx);
+  const int par = (int)(p->n_adv % StreamPool::kDepth);
+  DeviceArena &arena = cx.arena[par];
+  HostArena &harena = cx.host_arena[par];
+  hipStream_t qc = p->qc;
+  SearchPlan sp;
+  size_t need = (size_t)n * 3 * 16 + 4096;
+  if (p->reg) {
+    sp.n_utts = n; sp.S = S; sp.maxT = maxT; sp.max_words = StreamPool::kPartialWords;
+    need += (size_t)n * ((size_t)sp.max_words * 4 + 4 + 16 + 64 + (size_t)4 * (maxT + 2) * 8) + 65536;
+  } else {
+    need += PlanSearch(n, maxT, 1, 1.0f, &sp, /*best_path_only=*/true);
+    sp.dopts.no_final = 1;
+  }
+  arena.Reserve(need, qc);
+  arena.Reset();
+  harena.Reset();
+  int *d_idx = arena.AllocT<int>((size_t)3 * n + 16);
+  {
+    int *h = harena.AllocT<int>((size_t)3 * n + 16);
+    for (int i = 0; i < n; i++) { h[i] = T[i]; h[n + i] = slots[i]; h[2 * n + i] = row0s[i]; }
+    RS_HIP(hipMemcpyAsync(d_idx, h, sizeof(int) * 3 * n, hipMemcpyHostToDevice, qc));
+  }
+  BatchGeom gd;
+  gd.n_utts = n; gd.max_frames = maxT; gd.d_num_frames = d_idx; gd.d_row_base = d_idx + 2 * n;
+  if (p->reg) {
+    DecodeWork &w = sp.w;
+    w.max_words = sp.max_words;
+    w.out_words = arena.AllocT<int>((size_t)n * sp.max_words);
+    w.out_nwords = arena.AllocT<int>(n);
+    w.out_costs = arena.AllocT<float>((size_t)n * 4);
+    w.counters = arena.AllocT<long long>((size_t)n * 8);
+    PartialWork pw;
+    std::memset(&pw, 0, sizeof(pw));
+    pw.state_cost = p->dec_state; pw.bp = p->bp; pw.frame_info = p->finfo; pw.loglikes = p->ll; pw.ld = p->ld_ll;
+    pw.num_frames = d_idx; pw.slot = d_idx + n; pw.pool_row = d_idx + 2 * n;
+    pw.anchor = p->anchor; pw.rows = p->prow; pw.anchor_words = p->anchor_words;
+    pw.out_words = w.out_words; pw.out_nwords = w.out_nwords; pw.out_costs = w.out_costs; pw.counters = w.counters;
+    pw.max_words = sp.max_words;
+    pw.path_cap = 4 * (maxT + 2);
+    pw.path = arena.AllocT<int>((size_t)n * pw.path_cap * 2);
+    { const char *e = std::getenv("RS_PARTIAL_FULL_WALK"); pw.full_walk = e && std::atoi(e) != 0 ? 1 : 0; }      // (read per call: tests compare)
+    LaunchPartialReg(hclg_dev_, pw, n, qc);
+  } else {
+    AllocSearch(&sp, arena, qc);
+    LaunchSearch(&sp, arena, gd, p->ll, p->ld_ll, qc);
+  }
+  { const hipError_t le = hipGetLastError(); if (le != hipSuccess) Fail(std::string("a kernel launch failed: ") + hipGetErrorString(le)); }
+  res->utts.assign(n, UttResult());
+  for (int i = 0; i < n; i++) res->utts[i].num_frames = T[i];
+  CollectResults(sp, cx, par, gd, T.data(), p->ll, p->ld_ll, 1, 1.0f, qc, res->utts.data(), res->timings);
+  for (int i = 0; i < n; i++) {
+    UttResult &ur = res->utts[i];
+    if (T[i] == 0) {                 // nothing searched yet: an empty best path (the reference asserts; its callers guard)
+      ur.status = RS_OK;
+      ur.error.clear();
+      ur.hyps.assign(1, Hypothesis());
+      for (int64_t &c : ur.counters) c = 0;
+      continue;
+    }
+    if (!p->reg) {                   // (the deferred search's traceback walks every frame)
+      for (int k = 1; k < 7; k++) ur.counters[k] = 0;
+      ur.counters[0] = T[i] + 1;
+    }
+    if (ur.status != RS_OK && (ur.counters[7] & 8)) ur.error = "partial result: a back-pointer chain missed the stream's traceback anchor";
+  }
 }
 
 }  // namespace rs

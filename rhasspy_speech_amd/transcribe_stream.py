@@ -4,6 +4,8 @@ Same public surface as rhasspy_speech/transcribe_stream.py:18-129: `KaldiNnet3St
 consumes an async iterable of raw s16le 16 kHz mono chunks (the bytes the reference writes to the stdin of
 `online2-cli-nnet3-decode-faster`, :76-82) and returns the decoded texts.  The library re-chunks to the binary's
 fixed 1024-sample ticks, so -- like the reference -- the result does not depend on how the caller slices the audio.
+`async_transcribe_with_partials` also reports the best path so far as the audio arrives (the "temporary transcript" of
+online2-tcp-nnet3-decode-faster.cc:302-318), and returns what `async_transcribe` returns.
 """
 from __future__ import annotations
 
@@ -11,7 +13,7 @@ import asyncio
 import logging
 from collections.abc import AsyncIterable
 from pathlib import Path
-from typing import List, Optional, Union
+from typing import Callable, List, Optional, Union
 
 from . import _lib
 from .meta import decode_meta, int2sym, read_words_txt, texts_from_int2sym
@@ -59,6 +61,21 @@ class KaldiNnet3StreamTranscriber:
         stream.accept(chunk)
         stream.advance()
 
+    @staticmethod
+    def _accept_and_partial(stream, chunk) -> List[int]:
+        stream.accept(chunk)
+        res = stream.partial()
+        try:
+            return res.words(0)
+        finally:
+            res.close()
+
+    def _partial_text(self, words: List[int]) -> str:
+        """A partial's words as the final text is made of them: int2sym, then the meta words decoded (no fuzzy match)."""
+        line = int2sym(("utt-1 " + " ".join(str(w) for w in words) + "\n").encode(), self._words)
+        parts = line.strip().split(maxsplit=1)
+        return decode_meta(parts[1]) if len(parts) > 1 else ""
+
     async def async_transcribe(
         self,
         audio_stream: AsyncIterable[Optional[bytes]],
@@ -67,9 +84,27 @@ class KaldiNnet3StreamTranscriber:
         max_fuzzy_cost: Optional[float] = None,
         require_fuzzy: bool = False,
     ) -> List[str]:
+        return await self._transcribe(audio_stream, lang_dir, nbest, max_fuzzy_cost, require_fuzzy, None)
+
+    async def async_transcribe_with_partials(
+        self,
+        audio_stream: AsyncIterable[Optional[bytes]],
+        lang_dir: Union[str, Path],
+        on_partial: Callable[[str], None],
+        nbest: int = 1,
+        max_fuzzy_cost: Optional[float] = None,
+        require_fuzzy: bool = False,
+    ) -> List[str]:
+        """`async_transcribe`, and after every chunk the best path so far (rs_stream_partial: no final costs): `on_partial(text)` is
+        called whenever its words differ from the last ones reported (none before the first word).  Returns exactly what
+        `async_transcribe` returns for the same audio."""
+        return await self._transcribe(audio_stream, lang_dir, nbest, max_fuzzy_cost, require_fuzzy, on_partial)
+
+    async def _transcribe(self, audio_stream, lang_dir, nbest, max_fuzzy_cost, require_fuzzy, on_partial) -> List[str]:
         lang_dir = Path(lang_dir)
         stream = _lib.Stream(self._ensure_loaded())
         loop = asyncio.get_running_loop()
+        reported: List[int] = []
         try:
             async for chunk in audio_stream:
                 if chunk:
@@ -77,7 +112,13 @@ class KaldiNnet3StreamTranscriber:
                     # decoder decodes as it reads; here: hand the samples over and let the device do what they make possible (MFCC,
                     # iVector, nnet chunks, search) -- in the executor, so the event loop is not held while the library plans and
                     # issues the advance (the calls release the GIL)
-                    await loop.run_in_executor(None, self._accept_and_advance, stream, chunk)
+                    if on_partial is None:
+                        await loop.run_in_executor(None, self._accept_and_advance, stream, chunk)
+                        continue
+                    words = await loop.run_in_executor(None, self._accept_and_partial, stream, chunk)
+                    if words != reported:
+                        reported = words
+                        on_partial(self._partial_text(words))
             _LOGGER.debug("Stream ended")
             try:
                 res = await loop.run_in_executor(None, stream.finish, nbest, self.acoustic_scale)
