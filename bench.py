@@ -8,33 +8,39 @@ each is pinned to the reference's transcript in tests/test_gpu_configs.py):
   mixed   (configs[3]): 1024 utterances naming two zamia-size models, sharded over the ranks, one gather;
   streams (configs[4]): 64 concurrent 30 s streams (rs_streams_* entry points) handed over round-robin in rounds of 8192 samples per stream
           (8 of the reference binary's 1024-sample reads; the library's default coalescing makes every second rs_streams_advance call do
-          the device work of two) -- with `streams_per_tick` (1024-sample rounds, every call advances: SURVEY 8(d)'s wording) and
-          `finish_latency_ms` (p50 / p99 of last-samples-in -> words-out at real-time arrival) beside it;
+          the device work of two) -- with --full, `streams_per_tick` (1024-sample rounds, every call advances: SURVEY 8(d)'s
+          wording) and `finish_latency_ms` (p50 / p99 of last-samples-in -> words-out at real-time arrival) beside it;
 No real zamia model exists offline, so the model is the synthetic "zamia-like-S" of SURVEY.md section 8(d) written in
 genuine Kaldi formats by rhasspy_speech_amd.synth (40-dim hires MFCC, 100-dim iVector with a 512-Gaussian UBM, 7x250
 TDNN + prefinal, 2000 pdfs); audio is synthetic (seeded).
 
 A "step" is one pass of the whole path (MFCC -> iVector -> TDNN -> beam search -> word ids) over the workload's batch.
 `value` is SURVEY.md section 8(d)'s timed region: int16 PCM in pageable HOST memory -> word ids in host memory, model and
-graph resident (rs_decode_batch; rs_decode_batch_sharded at N > 1; rs_stream_* for `streams`) -- PCIe-inclusive.  Beside it,
-each over the same number of steps: `hbm_resident` (the samples already in HBM when the timed region starts,
-rs_decode_batch_device), `reference_output_layer` (host PCM AND the output layer evaluated for all 2000 pdfs, which is
-literally what the reference computes; the library default evaluates the 362 pdfs that occur on HCLG arcs: same words, same
-costs) and `hbm_resident_all_pdfs`.  The K timed steps are submitted from a few host threads (`--inflight`, default 4; 3 on the ARPA graph and for the two-model batch) so
+graph resident (rs_decode_batch; rs_decode_batch_sharded at N > 1; rs_stream_* for `streams`) -- PCIe-inclusive.  The K timed
+steps are submitted from a few host threads (`--inflight`, default 4; 3 on the ARPA graph and for the two-model batch) so
 that consecutive batches overlap on the device, as a serving process would run them.  Every step's records are checked
-against the first step's and -- rank 0 -- against the REFERENCE's transcripts (tests/golden/configs).  Stage times and the
-roofline are taken from un-overlapped calls right after the timed region.
+against the first step's.
+
+A plain run does only what the headline needs: it synthesises the models, graphs and audio from their seeds (the files into a
+directory of its own, removed at exit: no run reads what an earlier one wrote), warms up, times the K steps, writes
+`--dump-outputs` and prints ONE JSON line (rank 0) with the fields the driver expects.  `--full` adds everything else:
+  - rank 0's transcripts checked against the REFERENCE's (tests/golden/configs);
+  - stage times and `roofline`, taken from un-overlapped calls right after the timed region (one GPU);
+  - `cpu_baseline`, the reference's own binaries on this host's cores (unless --no-cpu-baseline);
+  - one GPU, unless --no-side-figures: beside the headline, each over the same number of steps, `hbm_resident` (the samples
+    already in HBM when the timed region starts, rs_decode_batch_device), `reference_output_layer` (host PCM AND the output
+    layer evaluated for all 2000 pdfs, which is literally what the reference computes; the library default evaluates the 362
+    pdfs that occur on HCLG arcs: same words, same costs) and `hbm_resident_all_pdfs`; for the headline workload also
+    `steady_state` (the same steps repeated for at least a second when the requested timed region is shorter than that: the
+    driver's `--steps 20` is 45 ms, inside which the pipeline of calls in flight fills and drains), `nbest5`, `emit_lattice`,
+    `frame_subsampling_factor_3`, `tdnnf_model` and `other_workloads`: short runs (>= 1 s of timed work each, transcripts
+    checked against the reference's goldens like the headline's) of the other three configurations -- arpa, mixed, streams --
+    each with its ms_per_step, value and the roofline of its dominant kernel.
 
 Multi-GPU (driver: `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`): utterances shard
 embarrassingly (utterance i -> rank i % N, rs_decode_batch_sharded), one process per GPU, weak scaling, no data-path
 collective; the fixed-size result records are gathered inside the timed region by ONE ncclAllGather per step issued by the
 library itself (rs_shard_gather on torch.distributed's RCCL communicator; torch's all_gather when that is not available).
-
-Prints ONE JSON line (rank 0) with the fields the driver expects plus `roofline` and `cpu_baseline`.  A default one-GPU run of the
-headline workload also carries `steady_state` (the same steps repeated for at least a second when the requested timed region is
-shorter than that: the driver's `--steps 20` is 45 ms, inside which the pipeline of calls in flight fills and drains) and
-`other_workloads`: short runs (>= 1 s of timed work each, transcripts checked against the reference's goldens like the headline's)
-of the other three configurations -- arpa, mixed, streams -- each with its ms_per_step, value and the roofline of its dominant kernel.
 """
 from __future__ import annotations
 
@@ -92,7 +98,7 @@ def other_workloads(timeout_s: float = 240.0):
     the line keeps of each: value, ms_per_step, steps, the golden check, stage times and the roofline of its dominant kernel."""
     out = {}
     for wl, (steps, warm) in OTHER_WORKLOADS.items():
-        cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", wl, "--steps", str(steps), "--warmup", str(warm), "--no-cpu-baseline", "--no-side-figures"]
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", wl, "--steps", str(steps), "--warmup", str(warm), "--full", "--no-cpu-baseline", "--no-side-figures"]
         if wl == "streams":
             cmd.append("--stream-figures")
         t0 = time.perf_counter()
@@ -250,9 +256,12 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", choices=["grammar", "arpa", "mixed", "streams"], default="grammar")
     ap.add_argument("--utts", type=int, default=None, help="utterances (streams) per GPU; default = the configuration's size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-figures", action="store_true", help="time the headline only (profiling runs)")
-    ap.add_argument("--stream-figures", action="store_true", help="streams: streams_per_tick and finish_latency_ms even with --no-side-figures")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the reference's transcripts checked, stage times and roofline, the side "
+                         "figures, the other workloads and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-side-figures", action="store_true", help="with --full: the golden check, stage times and roofline only (profiling runs)")
+    ap.add_argument("--stream-figures", action="store_true", help="streams, with --full: streams_per_tick and finish_latency_ms even with --no-side-figures")
     ap.add_argument("--inflight", type=int, default=None,
                     help="decode calls in flight per rank (host threads on one model; the library gives each its own decode "
                          "context): the latency-bound search of one batch overlaps the GEMMs of the next.  1 = one call at a time")
@@ -275,11 +284,12 @@ def main() -> None:
     steps = args.steps if args.steps is not None else defaults[0]
     warmup = args.warmup if args.warmup is not None else defaults[1]
     inflight = args.inflight if args.inflight is not None else defaults[2]
+    side_figures = args.full and not args.no_side_figures
 
     # The other three configurations first, while this process has not touched the GPU yet: a second process beside an idle HIP
     # context runs the two-model batch at 11.2 ms per step instead of 7.8 (measured; the runtime time-slices the queues of the two).
     others = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and wl == "grammar" and not args.no_side_figures and not os.environ.get("RS_BENCH_NO_OTHER"):
+    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and wl == "grammar" and side_figures and not os.environ.get("RS_BENCH_NO_OTHER"):
         others = other_workloads()
     # Calls in flight use three HIP streams each; the runtime maps streams onto 4 hardware queues by default and streams that share
     # a queue wait for each other's events in order.  8 queues: headline step 2.45 -> 2.31 ms (the library sets the same default
@@ -327,7 +337,8 @@ def main() -> None:
 
     from rhasspy_speech_amd import _lib, shard
     from tests import configs
-    cache = Path(tempfile.gettempdir()) / f"rs_bench_{wl}_rank{rank}"
+    work = tempfile.TemporaryDirectory(prefix="rs_bench_")      # this run's synthesised models and graphs
+    cache = Path(work.name) / wl
     opts = dict(device_id=local_rank, prune_output_pdfs=0 if args.all_pdfs else 1)
     golden = None
     sharded = world > 1 or wl == "mixed"        # through rs_decode_batch_sharded: records are (global utterances, 68)
@@ -342,18 +353,19 @@ def main() -> None:
         model.to_device()
         models = [model]
         audio_seconds = sum(len(p) for p in pcms) / 16000.0
-        if rank == 0 and n_utts == 256:
+        if args.full and rank == 0 and n_utts == 256:
             golden = configs.load_golden("c1_grammar" if wl == "grammar" else "c2_arpa")
         n_global = n_utts * world
         if not sharded:
-            d_pcm = torch.from_numpy(np.concatenate(pcms)).to(f"cuda:{local_rank}")
-            offsets = np.concatenate([[0], np.cumsum([len(p) for p in pcms])]).astype(np.int64)
-
             def decode():
                 return model.decode_batch(pcms)
 
-            def decode_dev():
-                return model.decode_batch_device(d_pcm.data_ptr(), offsets)
+            if args.full:       # the HBM-resident figures and the stage times
+                d_pcm = torch.from_numpy(np.concatenate(pcms)).to(f"cuda:{local_rank}")
+                offsets = np.concatenate([[0], np.cumsum([len(p) for p in pcms])]).astype(np.int64)
+
+                def decode_dev():
+                    return model.decode_batch_device(d_pcm.data_ptr(), offsets)
         else:
             # weak scaling: 256 utterances per rank; global utterance i belongs to rank i % world and is that rank's utterance i // world
             g_pcms = [pcms[i // world] if i % world == rank else None for i in range(n_global)]
@@ -374,7 +386,7 @@ def main() -> None:
         model.to_device()
         models = [model]
         audio_seconds = sum(len(p) for p in pcms) / 16000.0
-        if rank == 0 and n_utts == 64:
+        if args.full and rank == 0 and n_utts == 64:
             golden = configs.load_golden("c4_streams")
         tick = 1024 * 8          # samples handed over per stream and round: 8 of the binary's 1024-sample reads
         pcms = [np.ascontiguousarray(p, dtype=np.int16) for p in pcms]
@@ -501,7 +513,7 @@ def main() -> None:
         model, model_dir, graph_dir = models[0], md, gd
         n_utts = n_global = len(pcms)
         audio_seconds = sum(len(p) for i, p in enumerate(pcms) if i % world == rank) / 16000.0      # this rank's share (strong split)
-        if rank == 0 and n_per == 512:
+        if args.full and rank == 0 and n_per == 512:
             gd_, gf_ = configs.load_golden("c3_mixed_de"), configs.load_golden("c3_mixed_fr")
             golden = ([None] * n_utts, np.zeros(n_utts, np.float32), np.zeros(n_utts, np.float32))
             it = {"de_DE-like": iter(zip(*gd_)), "fr_FR-like": iter(zip(*gf_))}
@@ -643,13 +655,13 @@ def main() -> None:
     # ---- side figures (one GPU, grammar / arpa), each over the same number of steps as the headline
     side = {}
     all_pdfs_stage = None
-    if world == 1 and elapsed < 1.0 and not args.no_side_figures:
+    if world == 1 and elapsed < 1.0 and side_figures:
         # the requested timed region is shorter than a second (the driver's --steps 20: 45 ms, most of it the pipeline of calls in
         # flight filling and draining): the same steps repeated for at least a second, beside it
         n_steady = max(int(1.2 / max(elapsed / steps, 1e-4)), steps)
         side["steady_state"] = figure(n_steady, timed(n_steady, decode, ref_rec),
                                       f"the same step, {n_steady} times back to back (>= 1 s of timed work): what a serving process sees")
-    if decode_dev is not None and not args.no_side_figures:
+    if decode_dev is not None and side_figures:
         n_warm = max(2, 2 * inflight)      # every decode context of the model has served a call (pinned staging, arena) before the clock starts
         run_steps(n_warm, decode_dev, ref_rec)
         side["hbm_resident"] = figure(steps, timed(steps, decode_dev, ref_rec),
@@ -678,12 +690,12 @@ def main() -> None:
                 full_stage += np.array(full_dev().timings())
             all_pdfs_stage = (float(full_stage[3] / 5), full.describe())
             del full
-    if wl == "streams" and world == 1 and (args.stream_figures or not args.no_side_figures):
+    if wl == "streams" and world == 1 and args.full and (args.stream_figures or not args.no_side_figures):
         side.update(stream_figures(ref_rec))
     # ---- the n-best / lattice tail (what every rescoring or fuzzy-matching call of the Python API asks for: nbest = 5; and the
     # determinised lattice itself): device-side lattice extraction + host determinisation and n-best, utterances of a call on a
     # few host threads.  Short runs: the tail is host work, an order of magnitude slower than the 1-best step.
-    if wl == "grammar" and world == 1 and not args.no_side_figures and not sharded:
+    if wl == "grammar" and world == 1 and side_figures and not sharded:
         n_tail = max(6, min(steps, 24))
 
         def nbest5():
@@ -724,7 +736,7 @@ def main() -> None:
         # The second acoustic model of SURVEY.md section 8(d), "tdnn-f-like", at full size (tests/configs.py: TDNNF_SPEC -- TdnnComponent
         # bottlenecks 1024 / 128 with 0.66-scaled residual sums, 2000 pdfs) on the same batch and graph shape; its first 64 utterances are
         # checked against the reference's transcripts (tests/golden/configs/c5_tdnnf.npz), all of them in tests/test_gpu_configs.py.
-        f_md, f_gd = configs.build_tdnnf_model(Path(tempfile.gettempdir()) / f"rs_bench_tdnnf_rank{rank}")
+        f_md, f_gd = configs.build_tdnnf_model(Path(work.name) / "tdnnf")
         f_model = _lib.Model(f_md, f_gd, _lib.default_opts(device_id=local_rank, prune_output_pdfs=0 if args.all_pdfs else 1))
         f_model.to_device()
 
@@ -751,7 +763,7 @@ def main() -> None:
     # Stage times and the roofline come from un-overlapped calls made right after the timed region: same process, same
     # buffers, one call at a time.
     stage, counters, n_iso = np.zeros(8), np.zeros(8), 0
-    staged = not sharded and world == 1
+    staged = args.full and not sharded and world == 1
     if staged:
         n_iso = 5 if wl != "streams" else 2
         iso = decode_dev if decode_dev is not None else decode
@@ -767,10 +779,6 @@ def main() -> None:
         value = (world if wl != "mixed" else 1) * audio_seconds * steps / elapsed
         if wl == "mixed":
             value = sum(len(p) for p in pcms) / 16000.0 * steps / elapsed     # the whole 1024-utterance batch per step, all ranks together
-        desc = model.describe()
-        frames = sum(1 + (len(p) - 400) // 160 for p in pcms) if wl != "mixed" else 0
-        flops = nnet_flops_per_row(desc) * frames       # algorithmic: the real frames only (halo rows are overhead)
-        n_gemm = sum(1 for l in desc.splitlines() if l.startswith("op: gemm"))
         out = {
             "metric": "audio-seconds decoded/sec (RTF^-1) en_US-zamia grammar HCLG", "value": value, "unit": "audio-seconds/s",
             "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": ms_per_step,
@@ -790,6 +798,10 @@ def main() -> None:
         }
         out.update(side)
         if staged:
+            desc = model.describe()
+            frames = sum(1 + (len(p) - 400) // 160 for p in pcms)
+            flops = nnet_flops_per_row(desc) * frames       # algorithmic: the real frames only (halo rows are overhead)
+            n_gemm = sum(1 for l in desc.splitlines() if l.startswith("op: gemm"))
             # decoder algorithmic bytes: arcs examined x (16 B arc + 4 B loglike), token insertions x 16 B,
             # tokens alive x 16 B token record
             dec_bytes = counters[1] * 20.0 + counters[2] * 16.0 + counters[3] * 16.0
@@ -829,18 +841,19 @@ def main() -> None:
             out["stages_ms"] = {"mfcc": float(stage[1]), "ivector": float(stage[2]), "nnet": float(stage[3]), "decode": float(stage[4]),
                                 "d2h+host": float(stage[5]), "total_call": float(stage[6])}
             out["other_roofline"] = roof_dec if roofline is roof_mfma else roof_mfma
-        else:
+        elif args.full:
             out["roofline"] = None
             out["roofline_note"] = ("the mixed batch runs the grammar workload's kernels on two models side by side; see --workload grammar for the roofline"
                                     if wl == "mixed" else "stage times and the roofline are measured at N = 1 (un-overlapped calls)")
         if others is not None:
             out["other_workloads"] = others
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(model_dir, graph_dir, pcms if wl != "mixed" else [p for nm, p in zip(names, pcms) if nm == list(by_name)[-1]],
                                                streaming=(wl == "streams"))
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+    work.cleanup()
 
 
 if __name__ == "__main__":

@@ -15,7 +15,7 @@ case $WL in
   streams) KT_STEPS=2;  PMC_STEPS=1;;
   mixed)   KT_STEPS=6;  PMC_STEPS=2;;
 esac
-B="python bench.py --workload $WL --no-cpu-baseline"
+B="python bench.py --full --workload $WL --no-cpu-baseline"
 P="$B --no-side-figures"      # under the profiler: the headline steps and the un-overlapped stage calls only
 $B --steps 2 --warmup 1 > /dev/null 2>&1      # page the image in
 # (bench.py measures stage times and the roofline on un-overlapped calls, so the kernel trace and the counters are taken with one call
@@ -25,7 +25,7 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- $
 timeout 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $P --steps $PMC_STEPS --warmup 1 --inflight 1 > /dev/null 2> $OUT/pmc_fetch.log
 timeout 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- $P --steps $PMC_STEPS --warmup 1 --inflight 1 > /dev/null 2> $OUT/pmc_write.log
 timeout 400 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_sq -- $P --steps $PMC_STEPS --warmup 1 --inflight 1 > /dev/null 2> $OUT/pmc_sq.log
-python bench.py --workload $WL > $OUT/bench_line.json 2> $OUT/bench.log                       # the default invocation, as the driver runs it
+python bench.py --full --workload $WL > $OUT/bench_line.json 2> $OUT/bench.log                # the default invocation with every figure beside the headline
 if [ "$WL" = grammar ]; then
   $B --all-pdfs > $OUT/bench_line_all_pdfs.json 2>> $OUT/bench.log
   $B --inflight 1 > $OUT/bench_line_one_call_in_flight.json 2>> $OUT/bench.log

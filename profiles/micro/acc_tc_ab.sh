@@ -10,6 +10,6 @@ for tc in 320 160 320 160; do
   rm -f /tmp/rstune/rhasspy_speech_amd/csrc/ivector_kernels.o
   make -C /tmp/rstune/rhasspy_speech_amd/csrc -j32 EXTRA="-DRS_ACC_TC=$tc" > $OUT/make.log 2>&1 || { tail $OUT/make.log; exit 1; }
   cp /tmp/rstune/rhasspy_speech_amd/librhasspy_speech_hip.so rhasspy_speech_amd/librhasspy_speech_hip.so
-  python bench.py --no-cpu-baseline --no-side-figures --steps 400 --warmup 20 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('TC $tc: ms/step', round(d['ms_per_step'],3), 'ivector stage alone', round(d['stages_ms']['ivector'],3))"
+  python bench.py --full --no-cpu-baseline --no-side-figures --steps 400 --warmup 20 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('TC $tc: ms/step', round(d['ms_per_step'],3), 'ivector stage alone', round(d['stages_ms']['ivector'],3))"
 done
 cp /tmp/librs_orig.so rhasspy_speech_amd/librhasspy_speech_hip.so

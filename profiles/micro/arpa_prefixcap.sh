@@ -1,6 +1,6 @@
 # token-list search: LDS prefix capacity (tokens per expansion chunk) against workgroups per CU; scratch builds with -DRS_PREFIX_CAP=n
 cd "$GRAFT_REPO_ROOT"
-run() { for k in 2 3; do python bench.py --workload arpa --no-cpu-baseline --steps 16 --inflight $k 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 inflight', $k, round(d['ms_per_step'],2), round(d['value']), round(d['stages_ms']['decode'],1))"; done; }
+run() { for k in 2 3; do python bench.py --full --workload arpa --no-cpu-baseline --steps 16 --inflight $k 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$1 inflight', $k, round(d['ms_per_step'],2), round(d['value']), round(d['stages_ms']['decode'],1))"; done; }
 python bench.py --workload arpa --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
 mkdir -p /tmp/rsab && cp -r rhasspy_speech_amd include /tmp/rsab/
 cp rhasspy_speech_amd/librhasspy_speech_hip.so /tmp/orig.so

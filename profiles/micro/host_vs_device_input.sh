@@ -5,7 +5,7 @@
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${1:-host_vs_device}
 mkdir -p $OUT
-RS_BENCH_TRACE=1 timeout 600 python bench.py --no-cpu-baseline --steps 200 --warmup 8 > $OUT/line.json 2> $OUT/trace.txt
+RS_BENCH_TRACE=1 timeout 600 python bench.py --full --no-cpu-baseline --steps 200 --warmup 8 > $OUT/line.json 2> $OUT/trace.txt
 python - <<PY
 import re, json
 runs, cur = [], []

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${1:-kt_quick}
 mkdir -p $OUT
 if [ -n "$2" ]; then timeout 1200 python -m pytest tests/test_gpu_parity.py -x -q -k "$2" > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $OUT/pytest.log; fi
-B="python bench.py --no-cpu-baseline --no-side-figures ${3:-}"
+B="python bench.py --full --no-cpu-baseline --no-side-figures ${3:-}"
 $B --steps 300 --warmup 20 > $OUT/line.json 2> $OUT/line.err
 python - <<PY
 import json

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${1:-live_variants}; shift
 mkdir -p $OUT
 cp rhasspy_speech_amd/librhasspy_speech_hip.so /tmp/librs_orig.so
-B="python bench.py --workload arpa --no-cpu-baseline --no-side-figures --steps 30 --warmup 4"
+B="python bench.py --full --workload arpa --no-cpu-baseline --no-side-figures --steps 30 --warmup 4"
 i=0
 for flags in "$@"; do
   i=$((i+1))

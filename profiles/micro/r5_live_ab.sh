@@ -9,7 +9,7 @@ tail -5 $OUT/pytest_parity.log
 timeout 900 python -m pytest tests/test_gpu_configs.py -x -q -k "config2" > $OUT/pytest_c2.log 2>&1
 echo "config2 rc=$?" | tee -a $OUT/summary.txt
 tail -5 $OUT/pytest_c2.log
-B="python bench.py --workload arpa --no-cpu-baseline --no-side-figures"
+B="python bench.py --full --workload arpa --no-cpu-baseline --no-side-figures"
 run() { # name, env...
   name=$1; shift
   env "$@" timeout 300 $B --steps 30 --warmup 4 > $OUT/$name.json 2> $OUT/$name.err

@@ -10,7 +10,7 @@ for pr in 3 1 0; do
   make -C /tmp/rsprof/rhasspy_speech_amd/csrc EXTRA=-DRS_REG_PRIO=$pr > $OUT/make.log 2>&1
   cp /tmp/rsprof/rhasspy_speech_amd/librhasspy_speech_hip.so rhasspy_speech_amd/librhasspy_speech_hip.so
   for infl in 1 4; do
-    line=$(timeout 300 python bench.py --steps 200 --warmup 12 --inflight $infl --no-cpu-baseline --no-side-figures 2>/dev/null | tail -n 1)
+    line=$(timeout 300 python bench.py --full --steps 200 --warmup 12 --inflight $infl --no-cpu-baseline --no-side-figures 2>/dev/null | tail -n 1)
     echo "s_setprio $pr, $infl in flight: $(echo "$line" | python -c 'import json,sys; l=json.loads(sys.stdin.read()); print("%.3f ms/step  stages %s" % (l["ms_per_step"], {k: round(v, 2) for k, v in l["stages_ms"].items()}))')" | tee -a $OUT/search_prio.txt
   done
 done

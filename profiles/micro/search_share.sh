@@ -11,7 +11,7 @@ for n in 100000 150 8; do
   make -C /tmp/rsprof/rhasspy_speech_amd/csrc EXTRA=-DRS_DEBUG_SEARCH_FRAMES=$n > $OUT/make.log 2>&1
   cp /tmp/rsprof/rhasspy_speech_amd/librhasspy_speech_hip.so rhasspy_speech_amd/librhasspy_speech_hip.so
   for infl in 1 4; do
-    line=$(RS_BENCH_DEBUG_UNCHECKED=1 python bench.py --steps 200 --warmup 12 --inflight $infl --no-cpu-baseline --no-side-figures 2>/dev/null | tail -n 1)
+    line=$(RS_BENCH_DEBUG_UNCHECKED=1 python bench.py --full --steps 200 --warmup 12 --inflight $infl --no-cpu-baseline --no-side-figures 2>/dev/null | tail -n 1)
     echo "search stops after $n frames, $infl in flight: $(echo "$line" | python -c 'import json,sys; l=json.loads(sys.stdin.read()); print("%.3f ms/step  stages %s" % (l["ms_per_step"], {k: round(v, 2) for k, v in l["stages_ms"].items()}))')" | tee -a $OUT/search_share.txt
   done
 done

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -k "gemm or offline_
 rm -rf /tmp/rstune && mkdir -p /tmp/rstune/profiles && cp -r rhasspy_speech_amd include /tmp/rstune/ && cp -r profiles/micro /tmp/rstune/profiles/ && rm -f /tmp/rstune/rhasspy_speech_amd/csrc/*.o
 make -C /tmp/rstune/rhasspy_speech_amd/csrc -j16 EXTRA=-DRS_TUNING > $OUT/make.log 2>&1 || { tail $OUT/make.log; exit 1; }
 cp rhasspy_speech_amd/librhasspy_speech_hip.so /tmp/librs_orig.so; cp /tmp/rstune/rhasspy_speech_amd/librhasspy_speech_hip.so rhasspy_speech_amd/librhasspy_speech_hip.so
-B="python bench.py --no-cpu-baseline --no-side-figures"
+B="python bench.py --full --no-cpu-baseline --no-side-figures"
 for strip in 1 0; do
   RS_GEMM_B3J_STRIP=$strip $B --steps 300 --warmup 20 > $OUT/line_strip$strip.json 2> $OUT/line_strip$strip.err
   python - <<PY

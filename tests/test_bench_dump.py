@@ -53,16 +53,16 @@ def test_dump_of_sharded_records_is_in_utterance_order(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_dumps_the_last_timed_step(tmp_path):
-    """The headline workload with a few timed steps: the line reports exactly those steps, and the dumped transcripts are the
-    reference's (tests/golden/configs/c1_grammar)."""
+    """The headline workload with a few timed steps: the line reports exactly those steps and, without --full, nothing beside
+    them; the dumped transcripts are the reference's (tests/golden/configs/c1_grammar)."""
     from tests import configs
     out = tmp_path / "out"
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-side-figures", "--no-cpu-baseline",
-           "--dump-outputs", str(out)]
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["steps"] == 3 and line["ms_per_step"] == pytest.approx(1000.0 * line["timed_seconds"] / 3)
+    assert not set(line) & {"roofline", "stages_ms", "cpu_baseline", "other_workloads", "steady_state", "hbm_resident", "nbest5", "tdnnf_model"}
     ref_words, _, _ = configs.load_golden("c1_grammar")
     words = np.load(out / "words.npy")
     assert words.shape[0] == len(ref_words) == 256

@@ -4,7 +4,8 @@ The driver starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 bench.py --gpus N ...`, one rank per GPU over RCCL.  A test box has ONE GPU and RCCL refuses two ranks on a device, so the
 same launch line is run here with bench.py's test hook RS_BENCH_BACKEND=gloo: two ranks share the GPU, the barrier / MAX
 over ranks / record gather travel through host memory, everything else (utterance sharding i mod N, per-rank model, the
-transcripts of rank 0 checked against the reference's goldens inside the run, one JSON line from rank 0) is the N > 1 path.
+transcripts of rank 0 checked against the reference's goldens inside the run, which `--full` asks for, one JSON line from
+rank 0) is the N > 1 path.
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ def test_bench_two_ranks(workload, scaling, units):
     env = dict(os.environ, RS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--workload", workload, "--no-cpu-baseline"]
+           "bench.py", "--gpus", "2", "--steps", "6", "--warmup", "2", "--workload", workload, "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
