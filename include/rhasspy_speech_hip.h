@@ -171,6 +171,87 @@ int rs_streams_finish(rs_stream *const *streams, int32_t n_streams, int32_t nbes
 int rs_streams_partial(rs_stream *const *streams, int32_t n_streams, rs_result **out);
 int rs_stream_partial(rs_stream *stream, rs_result **out);
 
+/* Endpointing = online2/online-endpoint.{h,cc}: has the speaker stopped?  Five rules over the trailing silence of the best path so
+ * far, the final relative cost and the utterance length (OnlineEndpointConfig, online-endpoint.h:128-186).  The reference's stream
+ * binary registers the config on the parser that reads online.conf (online2-cli-nnet3-decode-faster.cc:76), which is why
+ * --endpoint.* lines may stand there; online2-wav-nnet3-latgen-faster asks after every chunk and breaks at a detection (:270-274).
+ * --do-endpointing=true / --online=true in online.conf are still refused at load: the entry points below are how a caller asks. */
+typedef struct rs_endpoint_rule {          /* OnlineEndpointRule, online-endpoint.h:52-71 */
+  int32_t must_contain_nonsilence;         /* --endpoint.ruleN.must-contain-nonsilence */
+  float min_trailing_silence;              /* --endpoint.ruleN.min-trailing-silence, seconds */
+  float max_relative_cost;                 /* --endpoint.ruleN.max-relative-cost */
+  float min_utterance_length;              /* --endpoint.ruleN.min-utterance-length, seconds */
+} rs_endpoint_rule;
+#define RS_ENDPOINT_SILENCE_CHARS 4096
+typedef struct rs_endpoint_opts {
+  rs_endpoint_rule rule[5];                /* rule1 .. rule5 */
+  char silence_phones[RS_ENDPOINT_SILENCE_CHARS]; /* --endpoint.silence-phones: colon-separated phone ids, NUL-terminated ("" = none given) */
+  int32_t reserved[4];
+} rs_endpoint_opts;
+/* The defaults of online-endpoint.h:152-157: rule1 {false, 5.0, inf, 0}, rule2 {true, 0.5, 2.0, 0}, rule3 {true, 1.0, 8.0, 0},
+ * rule4 {true, 2.0, inf, 0}, rule5 {false, 0, inf, 20.0}; no silence phones. */
+int rs_default_endpoint_opts(rs_endpoint_opts *opts);
+/* The defaults overridden by the --endpoint.silence-phones / --endpoint.rule{1..5}.{must-contain-nonsilence, min-trailing-silence,
+ * max-relative-cost, min-utterance-length} lines of the model's online.conf (booleans and numbers parsed like the file's other
+ * options; a repeated option: the last one wins).  A value that does not parse does not fail the model load: it fails this call,
+ * and every endpoint call that uses the model's options, with the parser's message. */
+int rs_model_endpoint_opts(const rs_model *model, rs_endpoint_opts *opts);
+/* EndpointDetected(config, num_frames_decoded, trailing_silence_frames, frame_shift_in_seconds, final_relative_cost)
+ * (online-endpoint.cc:46-72) on the host, no device involved: 0, or the number 1..5 of the first rule that fires.  In float like
+ * the reference (BaseFloat): utterance_length = frames * shift, trailing_silence = silence frames * shift, contains_nonsilence =
+ * utterance_length > trailing_silence (RuleActivated, :26-44).  The silence list is not looked at.  -1 for a null `opts`. */
+int rs_endpoint_rule_fired(const rs_endpoint_opts *opts, int32_t num_frames_decoded, int32_t trailing_silence_frames,
+                           float frame_shift_seconds, float final_relative_cost);
+typedef struct rs_endpoint_status {
+  int32_t detected;                /* 0, or the first rule that fired (1..5) */
+  int32_t num_frames_decoded;      /* NumFramesDecoded() */
+  int32_t trailing_silence_frames; /* TrailingSilenceLength() */
+  float   final_relative_cost;     /* FinalRelativeCost(); +inf if no frontier token is final */
+  float   frame_shift_seconds;     /* feature frame shift x frame-subsampling-factor */
+  int32_t rows_read;               /* back-pointer rows (frames) the trailing-silence walk read: trailing_silence_frames + 1 on grammar
+                                    * graphs (0 before the first decoded frame), the counterpart of a partial's rs_result_counters out[0] */
+} rs_endpoint_status;
+/* EndpointDetected(config, tmodel, frame_shift, decoder) (online-endpoint.cc:109-126; SingleUtteranceNnet3Decoder::EndpointDetected,
+ * online-nnet3-decoding.cc:88-95) for the listed streams of one model.  The call first does what rs_streams_partial does first: the
+ * device work of every completed 1024-sample tick, no coalescing, batched -- so the answer is a function of the samples accepted,
+ * not of how the caller called.  Then per stream (out[i] = streams[i]):
+ *   num_frames_decoded      = decoder frames searched so far.  0: detected = 0, no silence, cost +inf, RS_OK (:115);
+ *   final_relative_cost     = min over the frontier's tokens of cost + Final(state), minus the min of cost; +inf when no frontier state
+ *                             is final or no token survives (lattice-faster-decoder.cc:536-569);
+ *   trailing_silence_frames = from the best frontier token WITHOUT final costs (rs_streams_partial's token, ties to the lowest state)
+ *                             backwards: input-epsilon arcs are skipped, an emitting arc whose transition-id belongs to a phone of the
+ *                             silence list counts one, the first other emitting arc ends the walk (online-endpoint.cc:89-106);
+ *   frame_shift_seconds     = mfcc.conf's --frame-shift in seconds x --frame-subsampling-factor (online-nnet3-decoding.cc:88-95);
+ *   detected                = rs_endpoint_rule_fired of these.
+ * opts = NULL: the model's (rs_model_endpoint_opts).  An empty silence list fails with RS_ERR_ARG "Endpointing requires nonempty
+ * --endpoint.silence-phones option", one that does not parse or holds a phone twice with "Bad --silence-phones option in endpointing
+ * config: ..." (online-endpoint.cc:79-86).  Nothing a partial, an advance or a finish reads is written: what they return afterwards
+ * is bit for bit what they return without the endpoint calls.  Finished, freed, failed and RS_STREAM_BATCH=1 streams are refused
+ * as by rs_streams_partial.  A stream whose search has failed (a partial reports RS_ERR_DECODE for that utterance: no surviving
+ * tokens, token capacity exceeded, epsilon cycle) has no answer: the call returns RS_ERR_DECODE with "rs_streams_endpoint: stream i:
+ * <the partial's message>", every record's `detected` is 0, and the streams stay usable as after such a partial.  A frontier that
+ * is healthy but holds no final state gives cost +inf and RS_OK.
+ * Cost: on grammar graphs the register-resident search holds, one workgroup per stream reduces the parked frontier twice and walks
+ * the back-pointer rows of the trailing silence plus one.  The walk is serial -- one lane, one dependent load chain per row -- and
+ * nothing is cached between calls, so a query costs time linear in the trailing silence at that moment: short while somebody
+ * speaks, growing by one row per frame for as long as a pause lasts (500 rows at 10 ms frames when rule1's default 5 s fire), and
+ * the whole stream if the silence list covers every phone of the best path.  The "is silence" table it reads is a device
+ * bitmap over the graph's arcs (the device arcs carry pdf ids, so the arc's transition-id -> phone lookup is done when the bitmap is
+ * built), made once per model and silence list and kept while the list stays the same.  For streams whose search is deferred to
+ * finish (larger graphs, RS_DECODER=dense|sparse|hash) the call runs the token-list search over all frames so far and reads that
+ * search's last frame and back pointers: O(frames) per call, like their partials. */
+int rs_streams_endpoint(rs_stream *const *streams, int32_t n_streams, const rs_endpoint_opts *opts, rs_endpoint_status *out);
+int rs_stream_endpoint(rs_stream *stream, const rs_endpoint_opts *opts, rs_endpoint_status *out);
+/* What the reference does once an endpoint is detected: it stops reading audio and calls FinalizeDecoding() + GetLattice(true) on the
+ * frames decoded so far WITHOUT InputFinished() (online2-wav-nnet3-latgen-faster.cc:270-278) -- no flush of the feature tail, which
+ * rs_streams_finish always does.  rs_streams_finalize does the catch-up of rs_streams_endpoint, then everything rs_streams_finish
+ * does after its flush (final costs, lattice, determinisation, n-best, emit_lattice) over exactly the decoder frames searched;
+ * rs_result_num_frames reports them.  Samples beyond the last complete tick are ignored as if never accepted.  The streams are
+ * finished afterwards.  A stream without a decoded frame fails like the decode of an empty utterance. */
+int rs_streams_finalize(rs_stream *const *streams, int32_t n_streams, int32_t nbest, float lattice_acoustic_scale,
+                        rs_result **out);
+int rs_stream_finalize(rs_stream *stream, int32_t nbest, float lattice_acoustic_scale, rs_result **out);
+
 /* Result access.  Hypotheses of utterance `utt` are ordered best first, like the keys utt-1..utt-n that
  * lattice-to-nbest writes (lattice-to-nbest.cc:100-106). */
 int32_t rs_result_num_utts(const rs_result *r);

@@ -28,13 +28,43 @@ class DecodeOpts(C.Structure):
     ]
 
 
+class EndpointRule(C.Structure):
+    """rs_endpoint_rule = OnlineEndpointRule (online-endpoint.h:52-71)."""
+    _fields_ = [("must_contain_nonsilence", C.c_int32), ("min_trailing_silence", C.c_float), ("max_relative_cost", C.c_float),
+                ("min_utterance_length", C.c_float)]
+
+
+ENDPOINT_SILENCE_CHARS = 4096     # RS_ENDPOINT_SILENCE_CHARS
+
+
+class EndpointOpts(C.Structure):
+    """rs_endpoint_opts = OnlineEndpointConfig: rule[0..4] = rule1..rule5, silence_phones = "1:2:3" (bytes)."""
+    _fields_ = [("rule", EndpointRule * 5), ("silence_phones", C.c_char * ENDPOINT_SILENCE_CHARS), ("reserved", C.c_int32 * 4)]
+
+
+class EndpointStatus(C.Structure):
+    """rs_endpoint_status: the record an endpoint query returns per stream."""
+    _fields_ = [("detected", C.c_int32), ("num_frames_decoded", C.c_int32), ("trailing_silence_frames", C.c_int32),
+                ("final_relative_cost", C.c_float), ("frame_shift_seconds", C.c_float), ("rows_read", C.c_int32)]
+
+    def as_tuple(self):
+        return (self.detected, self.num_frames_decoded, self.trailing_silence_frames, self.final_relative_cost, self.frame_shift_seconds,
+                self.rows_read)
+
+    def __repr__(self):
+        return ("EndpointStatus(detected=%d, num_frames_decoded=%d, trailing_silence_frames=%d, final_relative_cost=%r, "
+                "frame_shift_seconds=%r, rows_read=%d)" % self.as_tuple())
+
+
 FIXED_ONLINE, FIXED_DO_ENDPOINTING, FIXED_EXTRA_LEFT_CONTEXT_INITIAL, FIXED_PRUNE_INTERVAL, FIXED_DETERMINIZE_LATTICE = 1, 2, 4, 8, 16      # RS_FIXED_*
 
 EXPORTS = [
     "rs_default_opts", "rs_last_error", "rs_model_load_files", "rs_model_load", "rs_model_to_device", "rs_model_free",
     "rs_model_describe", "rs_model_check_sample_rate", "rs_decode_batch", "rs_decode_batch_device", "rs_decode_batch_sharded", "rs_shard_gather", "rs_stream_open", "rs_stream_accept",
     "rs_stream_finish", "rs_stream_free", "rs_streams_accept", "rs_streams_advance", "rs_streams_finish",
-    "rs_streams_partial", "rs_stream_partial", "rs_result_num_utts", "rs_result_num_hyps",
+    "rs_streams_partial", "rs_stream_partial",
+    "rs_default_endpoint_opts", "rs_model_endpoint_opts", "rs_endpoint_rule_fired", "rs_streams_endpoint", "rs_stream_endpoint",
+    "rs_streams_finalize", "rs_stream_finalize", "rs_result_num_utts", "rs_result_num_hyps",
     "rs_result_num_frames", "rs_result_words", "rs_result_costs", "rs_result_text", "rs_result_lattice", "rs_result_matrix",
     "rs_result_counters", "rs_result_timings", "rs_result_pack", "rs_result_free",
     "rs_mkgraph", "rs_fst_tool", "rs_fuzzy_open", "rs_fuzzy_match", "rs_result_fuzzy", "rs_fuzzy_free", "rs_lattice_entry_from_raw",
@@ -74,6 +104,13 @@ def load_library() -> C.CDLL:
     lib.rs_streams_finish.argtypes = [C.POINTER(vp), i32, i32, f32, C.POINTER(vp)]
     lib.rs_streams_partial.argtypes = [C.POINTER(vp), i32, C.POINTER(vp)]
     lib.rs_stream_partial.argtypes = [vp, C.POINTER(vp)]
+    lib.rs_default_endpoint_opts.argtypes = [C.POINTER(EndpointOpts)]
+    lib.rs_model_endpoint_opts.argtypes = [vp, C.POINTER(EndpointOpts)]
+    lib.rs_endpoint_rule_fired.argtypes = [C.POINTER(EndpointOpts), i32, i32, f32, f32]
+    lib.rs_streams_endpoint.argtypes = [C.POINTER(vp), i32, C.POINTER(EndpointOpts), C.POINTER(EndpointStatus)]
+    lib.rs_stream_endpoint.argtypes = [vp, C.POINTER(EndpointOpts), C.POINTER(EndpointStatus)]
+    lib.rs_streams_finalize.argtypes = [C.POINTER(vp), i32, i32, f32, C.POINTER(vp)]
+    lib.rs_stream_finalize.argtypes = [vp, i32, f32, C.POINTER(vp)]
     lib.rs_result_num_utts.argtypes = [vp]
     lib.rs_result_num_hyps.argtypes = [vp, i32]
     lib.rs_result_num_frames.argtypes = [vp, i32]
@@ -136,6 +173,21 @@ def default_opts(**overrides) -> DecodeOpts:
             raise TypeError(f"unknown decode option {k}")
         setattr(o, k, v)
     return o
+
+
+def default_endpoint_opts(silence_phones: Optional[str] = None) -> EndpointOpts:
+    """rs_default_endpoint_opts: the rules of online-endpoint.h:152-157, no silence phones unless given ("1:2:3")."""
+    o = EndpointOpts()
+    _check(lib().rs_default_endpoint_opts(C.byref(o)))
+    if silence_phones is not None:
+        o.silence_phones = silence_phones.encode()
+    return o
+
+
+def endpoint_rule_fired(opts: EndpointOpts, num_frames_decoded: int, trailing_silence_frames: int, frame_shift_seconds: float,
+                        final_relative_cost: float) -> int:
+    """rs_endpoint_rule_fired: EndpointDetected's rules on the host; 0 or the first rule (1..5) that fires."""
+    return lib().rs_endpoint_rule_fired(C.byref(opts), num_frames_decoded, trailing_silence_frames, frame_shift_seconds, final_relative_cost)
 
 
 class Result:
@@ -248,6 +300,12 @@ class Model:
         lib().rs_model_describe(self._h, buf, n + 1)
         return buf.value.decode()
 
+    def endpoint_opts(self) -> EndpointOpts:
+        """rs_model_endpoint_opts: the reference's endpointing defaults overridden by the --endpoint.* lines of online.conf."""
+        o = EndpointOpts()
+        _check(lib().rs_model_endpoint_opts(self._h, C.byref(o)))
+        return o
+
     def check_sample_rate(self, sample_rate: float) -> None:
         """Raises RsError with Kaldi's "Sampling frequency mismatch ..." unless `sample_rate` is the model's --sample-frequency."""
         _check(lib().rs_model_check_sample_rate(self._h, float(sample_rate)))
@@ -357,9 +415,23 @@ class Stream:
         _check(lib().rs_stream_partial(self._h, C.byref(out)))
         return Result(out)
 
+    def endpoint(self, opts: Optional[EndpointOpts] = None) -> EndpointStatus:
+        """rs_stream_endpoint: the device work the audio accepted so far allows (every tick), then EndpointDetected on the frames
+        searched so far (opts None: the model's); `.detected` = 0 or the rule that fired.  The stream stays open."""
+        out = EndpointStatus()
+        _check(lib().rs_stream_endpoint(self._h, None if opts is None else C.byref(opts), C.byref(out)))
+        return out
+
     def finish(self, nbest: int = 1, lattice_acoustic_scale: float = 1.0) -> Result:
         out = C.c_void_p()
         _check(lib().rs_stream_finish(self._h, nbest, lattice_acoustic_scale, C.byref(out)))
+        return Result(out)
+
+    def finalize(self, nbest: int = 1, lattice_acoustic_scale: float = 1.0) -> Result:
+        """rs_stream_finalize: the end of the stream as the reference reaches it after an endpoint -- results over the decoder frames
+        searched, the feature tail is not flushed.  The stream is finished afterwards."""
+        out = C.c_void_p()
+        _check(lib().rs_stream_finalize(self._h, nbest, lattice_acoustic_scale, C.byref(out)))
         return Result(out)
 
     def close(self) -> None:
@@ -426,6 +498,23 @@ def partial_streams(streams: Sequence[Stream]) -> Result:
     arr = (C.c_void_p * len(streams))(*[s._h for s in streams])
     out = C.c_void_p()
     _check(lib().rs_streams_partial(arr, len(streams), C.byref(out)))
+    return Result(out)
+
+
+def endpoint_streams(streams: Sequence[Stream], opts: Optional[EndpointOpts] = None) -> List[EndpointStatus]:
+    """rs_streams_endpoint: one endpoint record per stream, batched; record i = streams[i]."""
+    n = len(streams)
+    arr = (C.c_void_p * n)(*[s._h for s in streams])
+    out = (EndpointStatus * max(n, 1))()
+    _check(lib().rs_streams_endpoint(arr, n, None if opts is None else C.byref(opts), out))
+    return [out[i] for i in range(n)]
+
+
+def finalize_streams(streams: Sequence[Stream], nbest: int = 1, lattice_acoustic_scale: float = 1.0) -> Result:
+    """rs_streams_finalize: ends all streams without flushing their feature tails; utterance i of the result = streams[i]."""
+    arr = (C.c_void_p * len(streams))(*[s._h for s in streams])
+    out = C.c_void_p()
+    _check(lib().rs_streams_finalize(arr, len(streams), nbest, lattice_acoustic_scale, C.byref(out)))
     return Result(out)
 
 

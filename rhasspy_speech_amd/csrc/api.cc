@@ -6,6 +6,8 @@
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
+#include <climits>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -376,6 +378,120 @@ int rs_streams_partial(rs_stream *const *streams, int32_t n_streams, rs_result *
 int rs_stream_partial(rs_stream *stream, rs_result **out) {
   rs_stream *one[1] = {stream};
   return rs_streams_partial(one, 1, out);
+}
+
+// ---- endpointing (online2/online-endpoint.{h,cc})
+int rs_default_endpoint_opts(rs_endpoint_opts *opts) {
+  if (!opts) return ArgError("rs_default_endpoint_opts: null pointer");
+  g_last_error.clear();
+  rs::DefaultEndpointOpts(opts);
+  return RS_OK;
+}
+
+int rs_model_endpoint_opts(const rs_model *model, rs_endpoint_opts *opts) {
+  if (!model || !opts) return ArgError("rs_model_endpoint_opts: null argument");
+  return Guard([&]() { model->m->EndpointOpts(opts); return RS_OK; });
+}
+
+int rs_endpoint_rule_fired(const rs_endpoint_opts *opts, int32_t num_frames_decoded, int32_t trailing_silence_frames, float frame_shift_seconds,
+                           float final_relative_cost) {
+  if (!opts) return ArgError("rs_endpoint_rule_fired: null pointer");
+  return rs::EndpointRuleFired(*opts, num_frames_decoded, trailing_silence_frames, frame_shift_seconds, final_relative_cost);
+}
+
+// The checks TrailingSilenceLength makes on --endpoint.silence-phones (online-endpoint.cc:78-86): SplitStringToIntegers(str, ":",
+// omit_empty_strings = false), sorted and unique, not empty.  "" on success, else the message.
+static std::string ParseSilencePhones(const rs_endpoint_opts &o, std::vector<int32_t> *phones) {
+  const size_t len = strnlen(o.silence_phones, sizeof(o.silence_phones));
+  if (len == sizeof(o.silence_phones)) return "Bad --silence-phones option in endpointing config: the string is not terminated";
+  const std::string str(o.silence_phones, len);
+  const std::string bad = "Bad --silence-phones option in endpointing config: " + str;
+  phones->clear();
+  if (!str.empty()) {
+    size_t b = 0;
+    for (;;) {
+      const size_t e = str.find(':', b);
+      const std::string f = str.substr(b, e == std::string::npos ? std::string::npos : e - b);
+      char *end = nullptr;
+      errno = 0;
+      const long long v = f.empty() ? 0 : std::strtoll(f.c_str(), &end, 10);
+      if (f.empty() || std::isspace((unsigned char)f[0]) || *end != 0 || errno != 0 || v < INT32_MIN || v > INT32_MAX) return bad;
+      phones->push_back((int32_t)v);
+      if (e == std::string::npos) break;
+      b = e + 1;
+    }
+  }
+  std::sort(phones->begin(), phones->end());
+  if (std::adjacent_find(phones->begin(), phones->end()) != phones->end()) return bad + " (Duplicates in --silence-phones option in endpointing config)";
+  if (phones->empty()) return "Endpointing requires nonempty --endpoint.silence-phones option";
+  return std::string();
+}
+
+int rs_streams_endpoint(rs_stream *const *streams, int32_t n_streams, const rs_endpoint_opts *opts, rs_endpoint_status *out) {
+  if (!out) return ArgError("rs_streams_endpoint: bad argument");
+  const int rc = CheckStreams(streams, n_streams, "rs_streams_endpoint");
+  if (rc != RS_OK) return rc;
+  if (n_streams == 0) return ArgError("rs_streams_endpoint: no streams");
+  if (streams[0]->keep_pcm) return ArgError("rs_streams_endpoint: streams opened with RS_STREAM_BATCH=1 are only decoded at finish");
+  rs_endpoint_opts own;
+  if (!opts) {      // the model's: a value of online.conf that does not parse is reported here, not by the load
+    const int orc = Guard([&]() { streams[0]->model->m->EndpointOpts(&own); return RS_OK; });
+    if (orc != RS_OK) return orc;
+    opts = &own;
+  }
+  std::vector<int32_t> phones;
+  const std::string perr = ParseSilencePhones(*opts, &phones);
+  if (!perr.empty()) return ArgError(perr.c_str());
+  return Guard([&]() {
+    std::string search_error;
+    // (like an advance: one that throws may have moved the chunk schedule of some streams without writing their rows)
+    try {
+      streams[0]->model->m->StreamsEndpoint(streams, n_streams, phones, out, &search_error);
+    } catch (...) {
+      for (int i = 0; i < n_streams; i++) streams[i]->failed = true;
+      throw;
+    }
+    if (!search_error.empty()) {      // a failed search: what a partial reports as the utterance's status
+      g_last_error = "rs_streams_endpoint: " + search_error;
+      return RS_ERR_DECODE;
+    }
+    for (int i = 0; i < n_streams; i++)
+      out[i].detected = out[i].num_frames_decoded == 0 ? 0      // online-endpoint.cc:115
+                                                       : rs::EndpointRuleFired(*opts, out[i].num_frames_decoded, out[i].trailing_silence_frames,
+                                                                               out[i].frame_shift_seconds, out[i].final_relative_cost);
+    return RS_OK;
+  });
+}
+
+int rs_stream_endpoint(rs_stream *stream, const rs_endpoint_opts *opts, rs_endpoint_status *out) {
+  rs_stream *one[1] = {stream};
+  return rs_streams_endpoint(one, 1, opts, out);
+}
+
+int rs_streams_finalize(rs_stream *const *streams, int32_t n_streams, int32_t nbest, float lattice_acoustic_scale, rs_result **out) {
+  if (!out) return ArgError("rs_streams_finalize: bad argument");
+  const int rc = CheckStreams(streams, n_streams, "rs_streams_finalize");
+  if (rc != RS_OK) return rc;
+  if (n_streams == 0) return ArgError("rs_streams_finalize: no streams");
+  if (nbest < 1) return ArgError("rs_streams_finalize: nbest must be >= 1");
+  if (streams[0]->keep_pcm) return ArgError("rs_streams_finalize: streams opened with RS_STREAM_BATCH=1 are only decoded at finish");
+  return Guard([&]() {
+    std::unique_ptr<rs_result> res(new rs_result());
+    res->r.reset(new rs::Result());
+    for (int i = 0; i < n_streams; i++) streams[i]->finished = true;      // whatever happens below, these streams are over
+    streams[0]->model->m->StreamsFinalize(streams, n_streams, nbest, lattice_acoustic_scale, res->r.get());
+    for (int i = 0; i < n_streams; i++) {
+      std::vector<int16_t>().swap(streams[i]->pcm);
+      streams[i]->model->m->StreamClose(streams[i]);
+    }
+    *out = res.release();
+    return RS_OK;
+  });
+}
+
+int rs_stream_finalize(rs_stream *stream, int32_t nbest, float lattice_acoustic_scale, rs_result **out) {
+  rs_stream *one[1] = {stream};
+  return rs_streams_finalize(one, 1, nbest, lattice_acoustic_scale, out);
 }
 
 int rs_stream_finish(rs_stream *stream, int32_t nbest, float lattice_acoustic_scale, rs_result **out) {

@@ -166,6 +166,55 @@ void Model::ResolveDecoderOptions() {
   while (opts_.frames_per_chunk % opts_.frame_subsampling_factor != 0) opts_.frames_per_chunk++;
 }
 
+// OnlineEndpointConfig's defaults (online-endpoint.h:152-157)
+void DefaultEndpointOpts(rs_endpoint_opts *o) {
+  std::memset(o, 0, sizeof(*o));
+  const float inf = std::numeric_limits<float>::infinity();
+  o->rule[0] = {0, 5.0f, inf, 0.0f};
+  o->rule[1] = {1, 0.5f, 2.0f, 0.0f};
+  o->rule[2] = {1, 1.0f, 8.0f, 0.0f};
+  o->rule[3] = {1, 2.0f, inf, 0.0f};
+  o->rule[4] = {0, 0.0f, inf, 20.0f};
+}
+
+// EndpointDetected (online-endpoint.cc:46-72) over RuleActivated (:26-44), in BaseFloat = float; volatile keeps the two products
+// rounded to float before they are compared, whatever the host compiler would like to contract
+int EndpointRuleFired(const rs_endpoint_opts &o, int num_frames_decoded, int trailing_silence_frames, float frame_shift, float final_relative_cost) {
+  const volatile float utterance_length = (float)num_frames_decoded * frame_shift, trailing_silence = (float)trailing_silence_frames * frame_shift;
+  const float ul = utterance_length, ts = trailing_silence;
+  const bool contains_nonsilence = ul > ts;
+  for (int i = 0; i < 5; i++) {
+    const rs_endpoint_rule &r = o.rule[i];
+    if ((contains_nonsilence || !r.must_contain_nonsilence) && ts >= r.min_trailing_silence && final_relative_cost <= r.max_relative_cost &&
+        ul >= r.min_utterance_length)
+      return i + 1;
+  }
+  return 0;
+}
+
+// The --endpoint.* lines of online.conf over the defaults (OnlineEndpointConfig::Register, online-endpoint.h:159-186: the rules
+// register under the prefixes rule1 .. rule5).  Parsed here, not at load: a line the load used to skip must not start failing it.
+void Model::EndpointOpts(rs_endpoint_opts *o) const {
+  DefaultEndpointOpts(o);
+  for (auto &kv : fc_.endpoint_conf) {
+    const std::string &k = kv.first, &v = kv.second;
+    if (k == "endpoint.silence-phones") {
+      if (v.size() >= sizeof(o->silence_phones)) Fail("--endpoint.silence-phones is longer than " + std::to_string(sizeof(o->silence_phones) - 1) + " characters (online.conf: " + fc_.conf_path + ")");
+      std::memset(o->silence_phones, 0, sizeof(o->silence_phones));
+      std::memcpy(o->silence_phones, v.data(), v.size());
+      continue;
+    }
+    rs_endpoint_rule *r = nullptr;
+    if (k.size() > 15 && k.compare(0, 13, "endpoint.rule") == 0 && k[13] >= '1' && k[13] <= '5' && k[14] == '.') r = &o->rule[k[13] - '1'];
+    const std::string f = r ? k.substr(15) : std::string();
+    if (f == "must-contain-nonsilence") r->must_contain_nonsilence = ConfBool(v) ? 1 : 0;
+    else if (f == "min-trailing-silence") r->min_trailing_silence = ConfFloat(v);
+    else if (f == "max-relative-cost") r->max_relative_cost = ConfFloat(v);
+    else if (f == "min-utterance-length") r->min_utterance_length = ConfFloat(v);
+    else Fail("Invalid option --" + k + "=" + v + " in config file " + fc_.conf_path);
+  }
+}
+
 Model::Model(const std::string &final_mdl, const std::string &hclg, const std::string &online_conf,
              const rs_decode_opts &opts)
     : opts_(opts) {
@@ -1301,7 +1350,7 @@ void Model::IvecChunkChain(DeviceArena &arena, const BatchGeom &g, int n, int K,
 // ------------------------------------------------------------------------------------------------ search
 // Which search kernel a call runs and the work buffers it needs (all from the call's arena).  Shared by the batch path
 // (DecodeGroup) and the end of a stream (stream.cc), whose log-likelihoods live in the stream pool.
-size_t Model::PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only) const {
+size_t Model::PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only, bool token_lists) const {
   const int S = hclg_.num_states();
   sp->S = S; sp->n_utts = n_utts; sp->maxT = maxT; sp->max_words = 1024;
   // The reference un-scales the lattice's acoustic costs before lattice-to-nbest ranks its paths (online2-wav-nnet3-latgen-
@@ -1310,6 +1359,7 @@ size_t Model::PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, Searc
   sp->want_lattice = !best_path_only && (nbest > 1 || lat_scale != 1.0f || opts_.emit_lattice != 0 || sp->unscale);      // (best_path_only: partial results)
   sp->use_reg = reg_dev_.nt != 0 && !sp->want_lattice && !force_sparse_ && (decoder_choice_ == 0 || decoder_choice_ == 1);
   sp->use_dense = dense_ok_ && !sp->want_lattice && !force_sparse_ && decoder_choice_ != 3;
+  if (token_lists) sp->use_reg = sp->use_dense = false;      // (endpoint queries of deferred streams read the token lists: stream.cc)
   // A lattice needs every token of every frame, which the token-list searches keep and the register-resident one does not (5.8 ms
   // against 1.1 for the headline batch): it leaves the costs of all (frame, state) pairs beside its back-pointer rows instead and a
   // compaction kernel writes the token lists LatticeKernel reads (RS_LATTICE_SEARCH=tokens: the token-list search, as before round 4)

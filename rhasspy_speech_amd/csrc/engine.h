@@ -124,6 +124,10 @@ struct SearchPlan {
   DenseWork dw{};
 };
 
+// Endpointing on the host (online2/online-endpoint.{h,cc}): the defaults, and EndpointDetected's five rules in float
+void DefaultEndpointOpts(rs_endpoint_opts *o);
+int EndpointRuleFired(const rs_endpoint_opts &o, int num_frames_decoded, int trailing_silence_frames, float frame_shift, float final_relative_cost);
+
 class Model {
  public:
   Model(const std::string &final_mdl, const std::string &hclg, const std::string &online_conf, const rs_decode_opts &opts);
@@ -155,10 +159,18 @@ class Model {
   void StreamClose(rs_stream *st);
   void StreamsAdvance(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res);
   void StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res,
-                            bool every_tick = false);      // pool_mu_ held; every_tick: no min_ticks coalescing
+                            bool every_tick = false, bool no_flush = false);      // pool_mu_ held; every_tick: no min_ticks coalescing; no_flush (with final): rs_streams_finalize
   // rs_streams_partial: the advance the accepted samples allow (every tick), then the best path over the frames searched so far
   // without final costs, one hypothesis per stream in `res`; the streams stay open
   void StreamsPartial(rs_stream *const *streams, int n, Result *res);
+  // rs_streams_endpoint: the same catch-up, then per stream {trailing silence frames, rows read, flags, final relative cost} from the
+  // frontier and the back pointers (decode_endpoint.hip); sil_phones: sorted, unique, not empty.  The streams stay open.
+  void StreamsEndpoint(rs_stream *const *streams, int n, const std::vector<int32_t> &sil_phones, rs_endpoint_status *out, std::string *search_error);
+  // rs_streams_finalize: the catch-up, then the end of a stream WITHOUT the flush of the feature tail (FinalizeDecoding without
+  // InputFinished): results over the decoder frames searched
+  void StreamsFinalize(rs_stream *const *streams, int n, int nbest, float lat_scale, Result *res);
+  void EndpointOpts(rs_endpoint_opts *o) const;      // defaults <- online.conf's --endpoint.* lines; throws on a value that does not parse
+  float EndpointFrameShift() const { return fc_.mfcc.opts.frame_shift_ms / 1000.0f * (float)opts_.frame_subsampling_factor; }      // online-nnet3-decoding.cc:90-92
   void StreamsPoisonAll(const std::string &why = std::string());          // pool_mu_ held
 
  private:
@@ -176,7 +188,7 @@ class Model {
   size_t ImageBytes(int rows) const;
   std::vector<ActImage> AllocImages(DeviceArena &arena, int rows) const;
   std::vector<char> buf_image_, buf_f32_;      // per nnet buffer: has an operand image / is (also) read as plain floats
-  size_t PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only = false) const;
+  size_t PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only = false, bool token_lists = false) const;
   void AllocSearch(SearchPlan *sp, DeviceArena &arena, hipStream_t s, bool pooled_frames = false) const;
   void LaunchSearch(SearchPlan *sp, DeviceArena &arena, const BatchGeom &g, const float *ll, int ll_ld, hipStream_t s) const;
   void CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const BatchGeom &g, const int *T, const float *ll, int ll_ld, int nbest,
@@ -242,6 +254,12 @@ class Model {
   void IssuerSync(StreamPool *p);     // everything handed to the pool's issuing thread has been queued; ITS failure poisons the open streams, then rethrows
   void StreamGrow(rs_stream *st, int need_frames);
   void StreamsPartialLocked(rs_stream *const *streams, int n, Result *res);      // pool_mu_ held
+  void StreamsEndpointLocked(rs_stream *const *streams, int n, const std::vector<int32_t> &sil_phones, rs_endpoint_status *out, std::string *search_error);      // pool_mu_ held
+  // "the arc's transition-id belongs to a silence phone", one bit per HCLG arc, on the device; rebuilt when the phone list changes
+  const unsigned *SilenceArcBitmap(const std::vector<int32_t> &sil_phones, hipStream_t s);      // pool_mu_ held
+  std::vector<int32_t> sil_bitmap_phones_;
+  unsigned *d_sil_bitmap_ = nullptr;
+  std::vector<unsigned> h_sil_bitmap_;
   // The split-fp16 layer GEMMs carry activations below 65520 in magnitude (nnet_gemm_b3.hip).  A kernel that meets a larger
   // one sets the flag of the decode context it runs for (DecodeContext::gemm_ovf: host memory the device writes to); a batch
   // call that finds it set after its wait repeats itself on the exact-FP32 kernels (a model whose calls keep doing that changes

@@ -454,6 +454,26 @@ struct PartialWork {
 };
 void LaunchPartialReg(const HclgDev &h, const PartialWork &w, int n_streams, hipStream_t s);
 
+// Endpoint queries of streams (decode_endpoint.hip, rs_streams_endpoint): per listed stream the two quantities of
+// online-endpoint.cc:109-126 -- FinalRelativeCost() and TrailingSilenceLength() -- from the frontier and the back pointers.
+// Read-only on everything but its own result records.
+struct EndpointWork {
+  const unsigned *sil_arc;    // bit a: HCLG arc a is an emitting arc whose transition-id belongs to a silence phone
+  const int *num_frames;      // per listed stream: decoder frames searched
+  int4 *out;                  // per listed stream: {trailing silence frames, rows read, flags (2: no token survives, 8: broken chain), bits of the final relative cost}
+  // register-resident streams: the pool (as PartialWork)
+  const float *state_cost;
+  const int *bp;
+  const int *slot, *pool_row;
+  // deferred streams: the token lists the token-list search of this call left (DecodeWork)
+  const int4 *tokens;         // [u][tok_cap]: {state, cost bits, back pointer (index in the previous list; the same list for epsilon arcs), arc}
+  const int *frame_tok_off;   // [u][max_frames + 2]
+  const long long *counters;  // [u][8]: [7] = the search's error flags
+  int tok_cap, max_frames;
+};
+void LaunchEndpointReg(const HclgDev &h, const EndpointWork &w, int n_streams, hipStream_t s);
+void LaunchEndpointTokens(const HclgDev &h, const EndpointWork &w, int n_streams, hipStream_t s);
+
 void LaunchLdsPoison(unsigned *sink, hipStream_t s);   // -DRS_TUNING builds only: profiles/micro/poison_kernels.hip
 
 }  // namespace rs

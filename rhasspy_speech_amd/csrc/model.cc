@@ -331,7 +331,10 @@ void ReadFeatureConfig(const std::string &online_conf, FeatureConfig *fc) {
     else if (k == "global-cmvn-stats") gstats = v;
     else if (k == "add-pitch") { if (ParseBool(v, k)) Fail("--add-pitch=true is not supported"); }
     else if (k == "plp-config" || k == "fbank-config" || k == "online-pitch-config") {}
-    else if (k.compare(0, 9, "endpoint.") == 0 || k.compare(0, 26, "ivector-silence-weighting.") == 0) {}
+    // OnlineEndpointConfig (online-endpoint.h:159-186): kept as written; parsed by the first endpoint call, so that a model that
+    // loaded before still loads whatever these lines say (Model::EndpointOpts)
+    else if (k.compare(0, 9, "endpoint.") == 0) fc->endpoint_conf.emplace_back(k, v);
+    else if (k.compare(0, 26, "ivector-silence-weighting.") == 0) {}
     // decodable / decoder options registered on the same parser (NnetSimpleLoopedComputationOptions, decodable-simple-looped.h:68-81;
     // LatticeFasterDecoderConfig + its det_opts, lattice-faster-decoder.h:67-85; the binaries' own --online, --do-endpointing,
     // --chunk-length ...): kept, and applied or refused by Model::Model -- never dropped

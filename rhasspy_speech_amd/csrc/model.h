@@ -91,6 +91,7 @@ struct FeatureConfig {
   // (online2-wav-nnet3-latgen-faster.cc:131-137, online2-cli-nnet3-decode-faster.cc:73-78), so they take effect there unless the
   // command line repeats them (util/parse-options.cc:328-345: the config file is read first).  Model::Model applies them.
   std::vector<std::pair<std::string, std::string>> decoder_conf;
+  std::vector<std::pair<std::string, std::string>> endpoint_conf;      // the --endpoint.* lines, in file order (Model::EndpointOpts)
   std::string conf_path;
 };
 void ReadFeatureConfig(const std::string &online_conf, FeatureConfig *fc);

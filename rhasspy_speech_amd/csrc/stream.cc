@@ -456,7 +456,11 @@ void Model::StreamsAdvance(rs_stream *const *streams, int n, bool final, int nbe
   }
 }
 
-void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res, bool every_tick) {
+void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res, bool every_tick, bool no_flush) {
+  // no_flush (rs_streams_finalize): the end of the streams as the reference reaches it after an endpoint -- FinalizeDecoding() without
+  // InputFinished() (online2-wav-nnet3-latgen-faster.cc:270-278): the ticks completed are scheduled like by any advance, nothing is
+  // flushed, and the final stage runs over the decoder frames those ticks give
+  const bool flush = final && !no_flush;
   StreamPool *p = Pool();
   RS_HIP(hipSetDevice(opts_.device_id));
   // queues: qa = features + iVectors (stage A), q = acoustic model + search (stage B, behind stage A's event); consecutive
@@ -519,28 +523,28 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
     if (a.avail + 2 > st.cap) StreamGrow(&st, a.avail + 2);
     a.mf0 = st.frames_mfcc;
     // the tick schedule (DecodeGroup's, resumed): ticks completed by the samples so far; the partial last read counts at EOF
-    const long ticks = final ? (ns + 1023) / 1024 : ns / 1024;
+    const long ticks = flush ? (ns + 1023) / 1024 : ns / 1024;
     const int nch_final = (a.avail + chunk - 1) / chunk;
     for (long j = st.ticks_done; j < ticks; j++) {
       const int fr = NumFrames(std::min<long>(1024 * (j + 1), ns), fc_.mfcc.opts);
       const int ready = std::max(0, fr - Rm) / chunk;
-      while (st.chunks_sched < ready && (!final || st.chunks_sched < nch_final)) {
+      while (st.chunks_sched < ready && (!flush || st.chunks_sched < nch_final)) {
         a.chunks.push_back({st.chunks_sched, std::min(fr - 1, fr - sr - 1)});
         st.chunks_sched++;
       }
     }
     st.ticks_done = ticks;
-    if (final) while (st.chunks_sched < nch_final) { a.chunks.push_back({st.chunks_sched, a.avail - 1}); st.chunks_sched++; }
+    if (flush) while (st.chunks_sched < nch_final) { a.chunks.push_back({st.chunks_sched, a.avail - 1}); st.chunks_sched++; }
     max_new_chunks = std::max(max_new_chunks, (int)a.chunks.size());
     a.sa = a.sb = st.stats_done;
     for (auto &c : a.chunks) a.sb = std::max(a.sb, c.second + 1);
     a.t0 = st.ll_done;
-    a.t1 = final ? a.avail : std::min(chunk * st.chunks_sched, a.avail);
+    a.t1 = flush ? a.avail : std::min(chunk * st.chunks_sched, a.avail);
   }
   // ---------------------------------------------------------------- transient geometry of the stages, index arrays
   IntStage is;
   std::vector<int> slots(n), row0s(n), avails(n);
-  for (int i = 0; i < n; i++) { slots[i] = streams[i]->slot; row0s[i] = streams[i]->row0; avails[i] = (pl[i].avail + fsf - 1) / fsf; }
+  for (int i = 0; i < n; i++) { slots[i] = streams[i]->slot; row0s[i] = streams[i]->row0; avails[i] = ((flush ? pl[i].avail : pl[i].t1) + fsf - 1) / fsf; }      // (the frames a final stage covers)
   // stage 1: MFCC over the new frames (dense rows, no halo), rows -> pool
   std::vector<int> m_T, m_rb{0}, m_out, m_f0;
   std::vector<int64_t> m_so{0};
@@ -895,7 +899,7 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
   }
   // ---------------------------------------------------------------- results
   res->utts.resize(n);
-  for (int i = 0; i < n; i++) res->utts[i].num_frames = dec_frames(pl[i].avail);
+  for (int i = 0; i < n; i++) res->utts[i].num_frames = avails[i];
   Timer tmr(qc);
   tmr.Mark();
   CollectResults(sp, cx, par, gd, avails.data(), p->ll, p->ld_ll, nbest, lat_scale, qc, res->utts.data(), res->timings);
@@ -905,7 +909,7 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
     for (int i = 0; i < n; i++) {
       UttResult &ur = res->utts[i];
       const rs_stream &st = *streams[i];
-      const int T = pl[i].avail, nch = std::max((T + chunk - 1) / chunk, 1);
+      const int T = flush ? pl[i].avail : pl[i].t1, nch = std::max((T + chunk - 1) / chunk, 1);
       ur.feat_dim = C; ur.num_pdfs = P; ur.ivec_dim = Di; ur.ivec_rows = has_iv ? nch : 0;
       if (T == 0) continue;
       ur.feats.resize((size_t)T * C);
@@ -1042,6 +1046,145 @@ void Model::StreamsPartialLocked(rs_stream *const *streams, int n, Result *res) 
       ur.counters[0] = T[i] + 1;
     }
     if (ur.status != RS_OK && (ur.counters[7] & 8)) ur.error = "partial result: a back-pointer chain missed the stream's traceback anchor";
+  }
+}
+
+
+// ---------------------------------------------------------------------------------------------------------- endpointing
+// "The arc's transition-id belongs to a silence phone", one bit per HCLG arc (the device arcs carry pdf ids, so TransitionIdToPhone
+// is applied here, once per model and phone list).  Callers hold pool_mu_ and wait for their kernel before they return, so nothing
+// reads the bitmap while a changed list rewrites it.
+const unsigned *Model::SilenceArcBitmap(const std::vector<int32_t> &sil_phones, hipStream_t s) {
+  if (d_sil_bitmap_ && sil_phones == sil_bitmap_phones_) return d_sil_bitmap_;
+  const size_t A = hclg_.arcs.size(), words = A / 32 + 1;
+  h_sil_bitmap_.assign(words, 0u);
+  const std::vector<int32_t> &id2phone = am_.trans.id2phone;
+  for (size_t a = 0; a < A; a++) {
+    const int tid = hclg_.arcs[a].ilabel;
+    if (tid <= 0 || tid >= (int)id2phone.size()) continue;
+    if (std::binary_search(sil_phones.begin(), sil_phones.end(), id2phone[tid])) h_sil_bitmap_[a >> 5] |= 1u << (a & 31);
+  }
+  if (!d_sil_bitmap_) {
+    void *d = nullptr;
+    RS_HIP(hipMalloc(&d, words * 4));
+    owned_.push_back(d);
+    d_sil_bitmap_ = static_cast<unsigned *>(d);
+  }
+  RS_HIP(hipMemcpyAsync(d_sil_bitmap_, h_sil_bitmap_.data(), words * 4, hipMemcpyHostToDevice, s));
+  RS_HIP(hipStreamSynchronize(s));      // (h_sil_bitmap_ is pageable and reused)
+  sil_bitmap_phones_ = sil_phones;
+  return d_sil_bitmap_;
+}
+
+// rs_streams_endpoint: the catch-up of a partial (every completed tick, batched), then per stream FinalRelativeCost() and
+// TrailingSilenceLength() (online-endpoint.cc:109-126):
+//   * register-resident streams: EndpointRegKernel (decode_endpoint.hip) over the parked frontier and the back-pointer rows of the
+//     trailing silence;
+//   * streams whose search is deferred to finish: the token-list search over the log-likelihood rows so far in a scratch arena, then
+//     EndpointTokensKernel over its last token list and back pointers.  O(frames so far) per call.
+// The rules are evaluated on the host (EndpointRuleFired) by the caller.  Nothing an advance, a partial or a finish reads is written.
+// A stream whose search has failed (what a partial reports as that utterance's RS_ERR_DECODE) has no answer: *search_error names the
+// first such stream with the partial's message, its record says "nothing detected", and the streams stay usable as after a partial.
+void Model::StreamsEndpoint(rs_stream *const *streams, int n, const std::vector<int32_t> &sil_phones, rs_endpoint_status *out, std::string *search_error) {
+  std::lock_guard<std::mutex> lk(pool_mu_);
+  try {
+    StreamsEndpointLocked(streams, n, sil_phones, out, search_error);
+  } catch (const DeviceError &) {
+    StreamsPoisonAll();
+    throw;
+  } catch (...) {
+    if (pool_) { pool_->issuer.Drain(false); (void)hipStreamSynchronize(pool_->qa); (void)hipStreamSynchronize(pool_->qi); (void)hipStreamSynchronize(pool_->q); (void)hipStreamSynchronize(pool_->qc); }
+    throw;
+  }
+}
+
+void Model::StreamsEndpointLocked(rs_stream *const *streams, int n, const std::vector<int32_t> &sil_phones, rs_endpoint_status *out, std::string *search_error) {
+  StreamPool *p = Pool();
+  RS_HIP(hipSetDevice(opts_.device_id));
+  bool more = false;
+  for (int i = 0; i < n; i++) more = more || streams[i]->n_samples / 1024 > streams[i]->ticks_done;
+  if (more) StreamsAdvanceLocked(streams, n, /*final=*/false, 1, 1.0f, nullptr, /*every_tick=*/true);
+  StreamsDrain(p, nullptr);        // every advance has finished: the arena sets are free, the frontier and rows are in place
+  const int fsf = opts_.frame_subsampling_factor;
+  std::vector<int> T(n);
+  int maxT = 0;
+  for (int i = 0; i < n; i++) {
+    const rs_stream &st = *streams[i];
+    T[i] = (p->reg && !st.dec_started) ? 0 : (st.ll_done + fsf - 1) / fsf;      // NumFramesDecoded()
+    maxT = std::max(maxT, T[i]);
+  }
+  DecodeContext &cx = *static_cast<DecodeContext *>(p->cx);
+  const int par = (int)(p->n_adv % StreamPool::kDepth);
+  DeviceArena &arena = cx.arena[par];
+  HostArena &harena = cx.host_arena[par];
+  hipStream_t qc = p->qc;
+  SearchPlan sp;
+  size_t need = (size_t)n * (3 * 16 + 16) + 8192;
+  if (!p->reg) need += PlanSearch(n, maxT, 1, 1.0f, &sp, /*best_path_only=*/true, /*token_lists=*/true);
+  arena.Reserve(need, qc);
+  arena.Reset();
+  harena.Reset();
+  EndpointWork ew;
+  std::memset(&ew, 0, sizeof(ew));
+  ew.sil_arc = SilenceArcBitmap(sil_phones, qc);
+  int *d_idx = arena.AllocT<int>((size_t)3 * n + 16);
+  {
+    int *h = harena.AllocT<int>((size_t)3 * n + 16);
+    for (int i = 0; i < n; i++) { h[i] = T[i]; h[n + i] = streams[i]->slot; h[2 * n + i] = streams[i]->row0; }
+    RS_HIP(hipMemcpyAsync(d_idx, h, sizeof(int) * 3 * n, hipMemcpyHostToDevice, qc));
+  }
+  ew.num_frames = d_idx;
+  ew.out = arena.AllocT<int4>(n);
+  if (p->reg) {
+    ew.state_cost = p->dec_state; ew.bp = p->bp; ew.slot = d_idx + n; ew.pool_row = d_idx + 2 * n;
+    LaunchEndpointReg(hclg_dev_, ew, n, qc);
+  } else {
+    BatchGeom gd;
+    gd.n_utts = n; gd.max_frames = maxT; gd.d_num_frames = d_idx; gd.d_row_base = d_idx + 2 * n;
+    // (the search also adds final costs and traces its best path back into out_words / out_costs, which nobody reads here:
+    // EndpointTokensKernel needs the best token without final costs and the first non-silence arc, so it reduces the last token list
+    // and walks the back pointers itself.  The extra traceback is one walk of the path, small beside the search over all frames.)
+    AllocSearch(&sp, arena, qc);
+    LaunchSearch(&sp, arena, gd, p->ll, p->ld_ll, qc);
+    ew.tokens = sp.w.tokens; ew.frame_tok_off = sp.w.frame_tok_off; ew.counters = sp.w.counters;
+    ew.tok_cap = sp.w.tok_cap; ew.max_frames = maxT;
+    LaunchEndpointTokens(hclg_dev_, ew, n, qc);
+  }
+  { const hipError_t le = hipGetLastError(); if (le != hipSuccess) Fail(std::string("a kernel launch failed: ") + hipGetErrorString(le)); }
+  int4 *h_out = harena.AllocT<int4>(n);
+  RS_HIP(hipMemcpyAsync(h_out, ew.out, sizeof(int4) * n, hipMemcpyDeviceToHost, qc));
+  RS_HIP(hipStreamSynchronize(qc));
+  const float shift = EndpointFrameShift();
+  for (int i = 0; i < n; i++) {
+    rs_endpoint_status &o = out[i];
+    const int fl = h_out[i].z;
+    if (fl & 8) Fail("endpoint query: a back-pointer chain of the best token is broken");
+    if ((fl & 2) && search_error && search_error->empty()) {      // the messages of a partial (CollectResults)
+      const int sf = fl >> 4;
+      *search_error = "stream " + std::to_string(i) + ": " +
+                      (sf & 1 ? "decoder token capacity exceeded (raise rs_decode_opts.max_tokens_per_frame)"
+                              : sf & 4 ? "epsilon cycle in the decoding graph" : "no surviving tokens (search error)");
+    }
+    o.detected = 0;
+    o.num_frames_decoded = T[i];
+    o.trailing_silence_frames = h_out[i].x;
+    std::memcpy(&o.final_relative_cost, &h_out[i].w, 4);
+    o.frame_shift_seconds = shift;
+    o.rows_read = T[i] == 0 ? 0 : (p->reg ? h_out[i].y : T[i] + 1);      // (the deferred search itself reads every frame)
+  }
+}
+
+// rs_streams_finalize: see StreamsAdvanceLocked(no_flush)
+void Model::StreamsFinalize(rs_stream *const *streams, int n, int nbest, float lat_scale, Result *res) {
+  std::lock_guard<std::mutex> lk(pool_mu_);
+  try {
+    StreamsAdvanceLocked(streams, n, /*final=*/true, nbest, lat_scale, res, /*every_tick=*/true, /*no_flush=*/true);
+  } catch (const DeviceError &) {
+    StreamsPoisonAll();
+    throw;
+  } catch (...) {
+    if (pool_) { pool_->issuer.Drain(false); (void)hipStreamSynchronize(pool_->qa); (void)hipStreamSynchronize(pool_->qi); (void)hipStreamSynchronize(pool_->q); (void)hipStreamSynchronize(pool_->qc); }
+    throw;
   }
 }
 

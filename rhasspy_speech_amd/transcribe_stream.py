@@ -6,6 +6,9 @@ consumes an async iterable of raw s16le 16 kHz mono chunks (the bytes the refere
 fixed 1024-sample ticks, so -- like the reference -- the result does not depend on how the caller slices the audio.
 `async_transcribe_with_partials` also reports the best path so far as the audio arrives (the "temporary transcript" of
 online2-tcp-nnet3-decode-faster.cc:302-318), and returns what `async_transcribe` returns.
+`async_transcribe_until_endpoint` also asks, after every chunk, whether the reference's endpointing rules fire
+(online2/online-endpoint.cc; rs_stream_endpoint) and, when they do, stops reading audio and finalizes the frames decoded so far
+like online2-wav-nnet3-latgen-faster.cc:270-278 does.
 """
 from __future__ import annotations
 
@@ -47,6 +50,7 @@ class KaldiNnet3StreamTranscriber:
         self._words = None
         self._lat_model: Optional[_lib.Model] = None      # the same files, results keep their lattices (rescoring path)
         self._rescorers = {}
+        self.last_endpoint_rule = 0      # async_transcribe_until_endpoint: the rule (1..5) that ended the last call, 0 = the audio ended first
 
     def _ensure_loaded(self) -> _lib.Model:
         if self._model is None:
@@ -69,6 +73,19 @@ class KaldiNnet3StreamTranscriber:
             return res.words(0)
         finally:
             res.close()
+
+    @staticmethod
+    def _accept_and_endpoint(stream, chunk, want_partial: bool, endpoint_opts):
+        """One chunk of async_transcribe_until_endpoint: -> (the partial's words or None, the rule that fired or 0)."""
+        stream.accept(chunk)
+        words = None
+        if want_partial:
+            res = stream.partial()
+            try:
+                words = res.words(0)
+            finally:
+                res.close()
+        return words, int(stream.endpoint(endpoint_opts).detected)
 
     def _partial_text(self, words: List[int]) -> str:
         """A partial's words as the final text is made of them: int2sym, then the meta words decoded (no fuzzy match)."""
@@ -100,13 +117,47 @@ class KaldiNnet3StreamTranscriber:
         `async_transcribe` returns for the same audio."""
         return await self._transcribe(audio_stream, lang_dir, nbest, max_fuzzy_cost, require_fuzzy, on_partial)
 
-    async def _transcribe(self, audio_stream, lang_dir, nbest, max_fuzzy_cost, require_fuzzy, on_partial) -> List[str]:
+    async def async_transcribe_until_endpoint(
+        self,
+        audio_stream: AsyncIterable[Optional[bytes]],
+        lang_dir: Union[str, Path],
+        nbest: int = 1,
+        max_fuzzy_cost: Optional[float] = None,
+        require_fuzzy: bool = False,
+        on_partial: Optional[Callable[[str], None]] = None,
+        endpoint_opts=None,
+    ) -> List[str]:
+        """`async_transcribe` that stops at the speaker's end: after every accepted chunk the stream is asked for an endpoint
+        (rs_stream_endpoint; `endpoint_opts` None = the model's online.conf over the reference's defaults).  On a detection no more
+        audio is taken from `audio_stream`, the frames decoded so far are finalized (rs_stream_finalize: no flush of the feature tail)
+        and post-processed exactly like `async_transcribe` does; if the audio ends first, this IS `async_transcribe`.  With
+        `on_partial`, partials are reported as by `async_transcribe_with_partials`.  `self.last_endpoint_rule` holds the rule (1..5)
+        that fired, 0 if none did."""
+        return await self._transcribe(audio_stream, lang_dir, nbest, max_fuzzy_cost, require_fuzzy, on_partial, until_endpoint=True,
+                                      endpoint_opts=endpoint_opts)
+
+    async def _transcribe(self, audio_stream, lang_dir, nbest, max_fuzzy_cost, require_fuzzy, on_partial, until_endpoint=False,
+                          endpoint_opts=None) -> List[str]:
         lang_dir = Path(lang_dir)
         stream = _lib.Stream(self._ensure_loaded())
         loop = asyncio.get_running_loop()
         reported: List[int] = []
+        fired = 0
+        if until_endpoint:
+            self.last_endpoint_rule = 0
         try:
             async for chunk in audio_stream:
+                if chunk and until_endpoint:
+                    words, fired = await loop.run_in_executor(None, self._accept_and_endpoint, stream, chunk, on_partial is not None,
+                                                              endpoint_opts)
+                    if words is not None and words != reported:
+                        reported = words
+                        on_partial(self._partial_text(words))
+                    if fired:      # online2-wav-nnet3-latgen-faster.cc:270-274: break out of the chunk loop
+                        self.last_endpoint_rule = fired
+                        _LOGGER.debug("Endpoint detected by rule %d", fired)
+                        break
+                    continue
                 if chunk:
                     # the reference writes the chunk to the decoder's stdin and awaits the drain (transcribe_stream.py:73-76) while the
                     # decoder decodes as it reads; here: hand the samples over and let the device do what they make possible (MFCC,
@@ -121,7 +172,7 @@ class KaldiNnet3StreamTranscriber:
                         on_partial(self._partial_text(words))
             _LOGGER.debug("Stream ended")
             try:
-                res = await loop.run_in_executor(None, stream.finish, nbest, self.acoustic_scale)
+                res = await loop.run_in_executor(None, stream.finalize if fired else stream.finish, nbest, self.acoustic_scale)
                 nbest_stdout = res.text(0, "utt")
             except _lib.RsError as e:
                 # The reference never checks the decoder's exit status (transcribe_stream.py:82) and then fails in
