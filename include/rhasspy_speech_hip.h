@@ -252,6 +252,55 @@ int rs_streams_finalize(rs_stream *const *streams, int32_t n_streams, int32_t nb
                         rs_result **out);
 int rs_stream_finalize(rs_stream *stream, int32_t nbest, float lattice_acoustic_scale, rs_result **out);
 
+/* Speaker adaptation = what online2-wav-nnet3-latgen-faster carries from one utterance of a speaker to the next
+ * (OnlineIvectorExtractorAdaptationState + OnlineCmvnState, :203-205 construct them per speaker, :220-221 set them on the feature
+ * pipeline before an utterance, :287-288 read them back after it).  A state is a small host object of doubles:
+ *   RS_ADAPT_IVECTOR_LINEAR     the iVector estimator's linear term, ivector_dim;
+ *   RS_ADAPT_IVECTOR_QUADRATIC  its quadratic term, the packed lower triangle row by row, ivector_dim (ivector_dim + 1) / 2;
+ *   RS_ADAPT_IVECTOR_COUNT      its num_frames, 1;
+ *   RS_ADAPT_CMVN_IVECTOR       speaker CMVN statistics of the iVector branch, 2 x (feat_dim + 1): row 0 = sum x | count, row 1 = sum x^2 | 0;
+ *   RS_ADAPT_CMVN_NNET          the same for the nnet-input CMVN (--cmvn-config in online.conf), where the model has one.
+ * Blocks the model has no use for (no extractor: the first four; no nnet-input CMVN: the last) are empty.
+ *
+ * rs_adaptation_new: the fresh-speaker state (the estimator as constructed, no speaker statistics).  No device involved.
+ * rs_streams_adaptation: one new state per listed stream (out[i] = streams[i]; free each with rs_adaptation_free), in one batched
+ *   device pass and one copy to the host.  The streams have ENDED -- rs_streams_finish or rs_streams_finalize returned RS_OK for
+ *   them -- and are not freed yet.  What it computes (OnlineIvectorFeature::GetAdaptationState, online-ivector-feature.cc:386-396):
+ *     - the CMVN statistics the stream was opened with plus (1, x, x^2) per raw MFCC frame in frame order, in double
+ *       (OnlineCmvn::GetState, online-feature.cc:467-487): every frame after a finish; after a finalize the frames of the complete
+ *       ticks (samples beyond the last complete tick are ignored there too);
+ *     - the estimator's statistics as they stand;
+ *     - LimitFrames(--max-remembered-frames, --posterior-scale) (online-ivector-feature.cc:109-127): the iVector-branch CMVN block
+ *       is scaled by max_remembered_frames / count where the count is above it, the estimator's statistics by max_remembered_frames x
+ *       posterior_scale / num_frames where above that, with the prior term re-added on element 0 and the diagonal
+ *       (OnlineIvectorEstimationStats::Scale, ivector-extractor.cc:671-693: --max-count = 0 and > 0).  The nnet-input block is never
+ *       limited.  The scalings are done in double (the reference rounds the CMVN factor to float: 6e-8 relative).
+ *   An ended stream keeps its place in the model's stream pool until rs_stream_free.  Should the pool run out of slots or rows
+ *   meanwhile, the oldest ended streams give theirs up, and asking for their state then fails with RS_ERR_ARG -- so take the state
+ *   before opening many more streams, and free ended streams as before.
+ * rs_stream_open_adapted: rs_stream_open with the state set before the first frame (SetAdaptationState, :445-453: the estimator's
+ *   statistics are replaced, its solution starts from [prior_offset, 0, ...] as always; SetCmvnState).  From then on the stream's
+ *   CMVN adds min(cmn_window - n, speaker_frames, speaker count) / speaker count x the speaker statistics before the global part
+ *   (SmoothOnlineCmvnStats, online-feature.cc:372-419).  state == NULL is rs_stream_open; a fresh state gives the same stream bit
+ *   for bit.  The state is copied: it may be freed or reused for other streams at once.  Dither noise is the fresh-process
+ *   sequence for every stream, adapted or not.
+ * rs_adaptation_export: block `what` into buf (cap doubles); *n = its length, also when buf is NULL or cap too small (RS_ERR_ARG then).
+ * rs_adaptation_import: a state from such arrays (a NULL pointer with length 0 = an empty block), to carry a speaker across
+ *   processes.  Lengths must be the model's, counts not negative, every value finite.
+ * Refused with RS_ERR_ARG and a message, the streams staying as usable as they were: a stream that has not ended, a failed stream,
+ * an RS_STREAM_BATCH=1 stream (and opening one with a state other than NULL), a state whose dimensions are not the model's. */
+typedef struct rs_adaptation rs_adaptation;
+enum { RS_ADAPT_IVECTOR_LINEAR = 0, RS_ADAPT_IVECTOR_QUADRATIC = 1, RS_ADAPT_IVECTOR_COUNT = 2, RS_ADAPT_CMVN_IVECTOR = 3, RS_ADAPT_CMVN_NNET = 4 };
+int rs_adaptation_new(const rs_model *model, rs_adaptation **out);
+int rs_streams_adaptation(rs_stream *const *streams, int32_t n_streams, rs_adaptation **out);
+int rs_stream_adaptation(rs_stream *stream, rs_adaptation **out);
+int rs_stream_open_adapted(rs_model *model, const rs_adaptation *state, rs_stream **out);
+int rs_adaptation_export(const rs_adaptation *a, int32_t what, double *buf, int64_t cap, int64_t *n);
+int rs_adaptation_import(const rs_model *model, const double *ivector_linear, int64_t n_linear, const double *ivector_quadratic, int64_t n_quadratic,
+                         double ivector_count, const double *cmvn_ivector, int64_t n_cmvn_ivector, const double *cmvn_nnet, int64_t n_cmvn_nnet,
+                         rs_adaptation **out);
+void rs_adaptation_free(rs_adaptation *a);
+
 /* Result access.  Hypotheses of utterance `utt` are ordered best first, like the keys utt-1..utt-n that
  * lattice-to-nbest writes (lattice-to-nbest.cc:100-106). */
 int32_t rs_result_num_utts(const rs_result *r);

@@ -64,7 +64,9 @@ EXPORTS = [
     "rs_stream_finish", "rs_stream_free", "rs_streams_accept", "rs_streams_advance", "rs_streams_finish",
     "rs_streams_partial", "rs_stream_partial",
     "rs_default_endpoint_opts", "rs_model_endpoint_opts", "rs_endpoint_rule_fired", "rs_streams_endpoint", "rs_stream_endpoint",
-    "rs_streams_finalize", "rs_stream_finalize", "rs_result_num_utts", "rs_result_num_hyps",
+    "rs_streams_finalize", "rs_stream_finalize",
+    "rs_adaptation_new", "rs_streams_adaptation", "rs_stream_adaptation", "rs_stream_open_adapted", "rs_adaptation_export", "rs_adaptation_import",
+    "rs_adaptation_free", "rs_result_num_utts", "rs_result_num_hyps",
     "rs_result_num_frames", "rs_result_words", "rs_result_costs", "rs_result_text", "rs_result_lattice", "rs_result_matrix",
     "rs_result_counters", "rs_result_timings", "rs_result_pack", "rs_result_free",
     "rs_mkgraph", "rs_fst_tool", "rs_fuzzy_open", "rs_fuzzy_match", "rs_result_fuzzy", "rs_fuzzy_free", "rs_lattice_entry_from_raw",
@@ -111,6 +113,15 @@ def load_library() -> C.CDLL:
     lib.rs_stream_endpoint.argtypes = [vp, C.POINTER(EndpointOpts), C.POINTER(EndpointStatus)]
     lib.rs_streams_finalize.argtypes = [C.POINTER(vp), i32, i32, f32, C.POINTER(vp)]
     lib.rs_stream_finalize.argtypes = [vp, i32, f32, C.POINTER(vp)]
+    pd, i64 = C.POINTER(C.c_double), C.c_int64
+    lib.rs_adaptation_new.argtypes = [vp, C.POINTER(vp)]
+    lib.rs_streams_adaptation.argtypes = [C.POINTER(vp), i32, C.POINTER(vp)]
+    lib.rs_stream_adaptation.argtypes = [vp, C.POINTER(vp)]
+    lib.rs_stream_open_adapted.argtypes = [vp, vp, C.POINTER(vp)]
+    lib.rs_adaptation_export.argtypes = [vp, i32, pd, i64, C.POINTER(i64)]
+    lib.rs_adaptation_import.argtypes = [vp, pd, i64, pd, i64, C.c_double, pd, i64, pd, i64, C.POINTER(vp)]
+    lib.rs_adaptation_free.argtypes = [vp]
+    lib.rs_adaptation_free.restype = None
     lib.rs_result_num_utts.argtypes = [vp]
     lib.rs_result_num_hyps.argtypes = [vp, i32]
     lib.rs_result_num_frames.argtypes = [vp, i32]
@@ -391,13 +402,74 @@ def bind_host_thread(device_id: int) -> int:
     return n
 
 
-class Stream:
-    """Owns an rs_stream: the stdin of one online2-cli-nnet3-decode-faster process."""
+ADAPT_IVECTOR_LINEAR, ADAPT_IVECTOR_QUADRATIC, ADAPT_IVECTOR_COUNT, ADAPT_CMVN_IVECTOR, ADAPT_CMVN_NNET = range(5)      # RS_ADAPT_*
+_ADAPT_BLOCKS = ("ivector_linear", "ivector_quadratic", "ivector_count", "cmvn_ivector", "cmvn_nnet")
 
-    def __init__(self, model: Model):
+
+class Adaptation:
+    """Owns an rs_adaptation: what the reference carries from one utterance of a speaker to the next (the iVector estimator's
+    statistics and the speaker CMVN statistics).  Adaptation(model) is the fresh-speaker state; Stream.adaptation() /
+    adaptation_of_streams() give the state after an utterance; Stream(model, adaptation=state) opens the next one with it."""
+
+    def __init__(self, model: Model, _handle: Optional[C.c_void_p] = None):
         self.model = model
         self._h = C.c_void_p()
-        _check(lib().rs_stream_open(model._h, C.byref(self._h)))
+        if _handle is not None:
+            self._h = _handle
+        else:
+            _check(lib().rs_adaptation_new(model._h, C.byref(self._h)))
+
+    def block(self, what: int) -> np.ndarray:
+        n = C.c_int64()
+        lib().rs_adaptation_export(self._h, what, None, 0, C.byref(n))      # (the length; the status says "buffer too small")
+        out = np.zeros(n.value, dtype=np.float64)
+        _check(lib().rs_adaptation_export(self._h, what, out.ctypes.data_as(C.POINTER(C.c_double)), n.value, C.byref(n)))
+        return out
+
+    def arrays(self) -> dict:
+        """The state as float64 arrays: ivector_linear, ivector_quadratic (packed lower triangle), ivector_count (1 value),
+        cmvn_ivector and cmvn_nnet (2 x (feat_dim + 1), flattened); blocks the model has no use for are empty."""
+        return {name: self.block(k) for k, name in enumerate(_ADAPT_BLOCKS)}
+
+    @classmethod
+    def from_arrays(cls, model: Model, arrays: dict) -> "Adaptation":
+        """rs_adaptation_import: the inverse of arrays() (lengths must be the model's, counts >= 0, values finite)."""
+        a = {name: np.ascontiguousarray(arrays.get(name, ()), dtype=np.float64).reshape(-1) for name in _ADAPT_BLOCKS}
+        if a["ivector_count"].shape[0] > 1:
+            raise ValueError("ivector_count holds one value")
+        ptr = lambda v: v.ctypes.data_as(C.POINTER(C.c_double)) if v.shape[0] else None
+        h = C.c_void_p()
+        _check(lib().rs_adaptation_import(model._h, ptr(a["ivector_linear"]), a["ivector_linear"].shape[0], ptr(a["ivector_quadratic"]),
+                                          a["ivector_quadratic"].shape[0], float(a["ivector_count"][0]) if a["ivector_count"].shape[0] else 0.0,
+                                          ptr(a["cmvn_ivector"]), a["cmvn_ivector"].shape[0], ptr(a["cmvn_nnet"]), a["cmvn_nnet"].shape[0], C.byref(h)))
+        return cls(model, _handle=h)
+
+    def close(self) -> None:
+        if self._h:
+            lib().rs_adaptation_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+class Stream:
+    """Owns an rs_stream: the stdin of one online2-cli-nnet3-decode-faster process.  adaptation: the speaker's state from the
+    utterances before (rs_stream_open_adapted); None = a fresh process, as before."""
+
+    def __init__(self, model: Model, adaptation: Optional[Adaptation] = None):
+        self.model = model
+        self._h = C.c_void_p()
+        if adaptation is None:
+            _check(lib().rs_stream_open(model._h, C.byref(self._h)))
+        else:
+            _check(lib().rs_stream_open_adapted(model._h, adaptation._h, C.byref(self._h)))
+
+    def adaptation(self) -> Adaptation:
+        """rs_stream_adaptation: the speaker's state after this utterance (the stream has ended through finish() / finalize() and
+        is not closed yet)."""
+        out = C.c_void_p()
+        _check(lib().rs_stream_adaptation(self._h, C.byref(out)))
+        return Adaptation(self.model, _handle=out)
 
     def accept(self, pcm) -> None:
         a = np.ascontiguousarray(np.frombuffer(pcm, dtype="<i2") if isinstance(pcm, (bytes, bytearray, memoryview)) else pcm, dtype=np.int16)
@@ -516,6 +588,15 @@ def finalize_streams(streams: Sequence[Stream], nbest: int = 1, lattice_acoustic
     out = C.c_void_p()
     _check(lib().rs_streams_finalize(arr, len(streams), nbest, lattice_acoustic_scale, C.byref(out)))
     return Result(out)
+
+
+def adaptation_of_streams(streams: Sequence[Stream]) -> List[Adaptation]:
+    """rs_streams_adaptation: one state per ended stream, in one batched device pass; state i = streams[i]."""
+    n = len(streams)
+    arr = (C.c_void_p * n)(*[s._h for s in streams])
+    out = (C.c_void_p * n)()
+    _check(lib().rs_streams_adaptation(arr, n, out))
+    return [Adaptation(streams[i].model, _handle=C.c_void_p(out[i])) for i in range(n)]
 
 
 def mkgraph(lang_dir, model_dir, graph_dir, self_loop_scale: float = 0.1, transition_scale: float = 1.0, dump_dir=None) -> None:

@@ -7,6 +7,7 @@
 #include <cctype>
 #include <cerrno>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -250,18 +251,30 @@ int rs_bind_host_thread(int32_t device_id) {
   });
 }
 
-int rs_stream_open(rs_model *model, rs_stream **out) {
-  if (!model || !out) return ArgError("rs_stream_open: null argument");
+static int StreamOpenImpl(const char *who, rs_model *model, const rs_adaptation *state, rs_stream **out) {
+  if (!model || !out) return ArgError((std::string(who) + ": null argument").c_str());
+  // RS_STREAM_BATCH=1: the cross-check path -- buffer everything, replay the stream as one batch at finish
+  const char *e = std::getenv("RS_STREAM_BATCH");
+  const bool keep_pcm = e && std::atoi(e) != 0;
+  if (state) {
+    if (keep_pcm) return ArgError((std::string(who) + ": streams opened with RS_STREAM_BATCH=1 are replayed as a batch, which has no adaptation state").c_str());
+    const std::string bad = model->m->AdaptationMismatch(*state);
+    if (!bad.empty()) return ArgError((std::string(who) + ": " + bad).c_str());
+  }
   return Guard([&]() {
     std::unique_ptr<rs_stream> st(new rs_stream());
     st->model = model;
-    // RS_STREAM_BATCH=1: the cross-check path -- buffer everything, replay the stream as one batch at finish
-    const char *e = std::getenv("RS_STREAM_BATCH");
-    st->keep_pcm = e && std::atoi(e) != 0;
-    if (!st->keep_pcm) model->m->StreamOpen(st.get());
+    st->keep_pcm = keep_pcm;
+    if (!st->keep_pcm) model->m->StreamOpen(st.get(), state);
     *out = st.release();
     return RS_OK;
   });
+}
+
+int rs_stream_open(rs_model *model, rs_stream **out) { return StreamOpenImpl("rs_stream_open", model, nullptr, out); }
+
+int rs_stream_open_adapted(rs_model *model, const rs_adaptation *state, rs_stream **out) {
+  return StreamOpenImpl("rs_stream_open_adapted", model, state, out);
 }
 
 static std::string FailedStream(const char *who, const rs_stream *st) {
@@ -347,7 +360,7 @@ int rs_streams_finish(rs_stream *const *streams, int32_t n_streams, int32_t nbes
     for (int i = 0; i < n_streams; i++) {
       streams[i]->finished = true;
       std::vector<int16_t>().swap(streams[i]->pcm);
-      if (!streams[i]->keep_pcm) streams[i]->model->m->StreamClose(streams[i]);
+      if (!streams[i]->keep_pcm) streams[i]->model->m->StreamEnd(streams[i], /*flushed=*/true);      // (slot and rows stay until rs_stream_free: rs_streams_adaptation)
     }
     *out = res.release();
     return RS_OK;
@@ -482,7 +495,7 @@ int rs_streams_finalize(rs_stream *const *streams, int32_t n_streams, int32_t nb
     streams[0]->model->m->StreamsFinalize(streams, n_streams, nbest, lattice_acoustic_scale, res->r.get());
     for (int i = 0; i < n_streams; i++) {
       std::vector<int16_t>().swap(streams[i]->pcm);
-      streams[i]->model->m->StreamClose(streams[i]);
+      streams[i]->model->m->StreamEnd(streams[i], /*flushed=*/false);
     }
     *out = res.release();
     return RS_OK;
@@ -501,9 +514,109 @@ int rs_stream_finish(rs_stream *stream, int32_t nbest, float lattice_acoustic_sc
 
 void rs_stream_free(rs_stream *stream) {
   if (!stream) return;
-  if (stream->open && stream->model) { try { stream->model->m->StreamClose(stream); } catch (...) {} }
+  if ((stream->open || stream->ended) && stream->model) { try { stream->model->m->StreamClose(stream); } catch (...) {} }
   delete stream;
 }
+
+// ---- speaker adaptation (online2-wav-nnet3-latgen-faster.cc:203-205,220-221,287-288)
+int rs_adaptation_new(const rs_model *model, rs_adaptation **out) {
+  if (!model || !out) return ArgError("rs_adaptation_new: null argument");
+  return Guard([&]() {
+    std::unique_ptr<rs_adaptation> a(new rs_adaptation());
+    model->m->AdaptationFresh(a.get());
+    *out = a.release();
+    return RS_OK;
+  });
+}
+
+int rs_streams_adaptation(rs_stream *const *streams, int32_t n_streams, rs_adaptation **out) {
+  const char *who = "rs_streams_adaptation";
+  if (!out || n_streams < 0 || (n_streams > 0 && !streams)) return ArgError("rs_streams_adaptation: bad argument");
+  if (n_streams == 0) return ArgError("rs_streams_adaptation: no streams");
+  for (int i = 0; i < n_streams; i++) {
+    const rs_stream *st = streams[i];
+    if (!st || !st->model) return ArgError("rs_streams_adaptation: null stream");
+    if (st->model != streams[0]->model) return ArgError("rs_streams_adaptation: all streams must belong to one model");
+    if (st->failed) return ArgError(FailedStream(who, st).c_str());
+    if (st->keep_pcm) return ArgError("rs_streams_adaptation: streams opened with RS_STREAM_BATCH=1 are replayed as a batch, which has no adaptation state");
+    if (st->reclaimed) return ArgError("rs_streams_adaptation: the stream ended, but the pool has since needed its slot and rows for other streams; its state is gone");
+    if (!st->ended) return ArgError(st->finished ? "rs_streams_adaptation: the stream's finish failed; it has no adaptation state"
+                                                  : "rs_streams_adaptation: stream has not ended (rs_streams_finish / rs_streams_finalize first)");
+    for (int j = 0; j < i; j++) if (streams[j] == st) return ArgError("rs_streams_adaptation: a stream is listed twice");
+  }
+  return Guard([&]() {
+    std::vector<std::unique_ptr<rs_adaptation>> own(n_streams);
+    std::vector<rs_adaptation *> ptr(n_streams);
+    for (int i = 0; i < n_streams; i++) { own[i].reset(new rs_adaptation()); ptr[i] = own[i].get(); }
+    streams[0]->model->m->StreamsAdaptation(streams, n_streams, ptr.data());
+    for (int i = 0; i < n_streams; i++) out[i] = own[i].release();
+    return RS_OK;
+  });
+}
+
+int rs_stream_adaptation(rs_stream *stream, rs_adaptation **out) {
+  rs_stream *one[1] = {stream};
+  return rs_streams_adaptation(one, 1, out);
+}
+
+static const std::vector<double> *AdaptBlock(const rs_adaptation *a, int32_t what, std::vector<double> *tmp) {
+  switch (what) {
+    case RS_ADAPT_IVECTOR_LINEAR: return &a->lin;
+    case RS_ADAPT_IVECTOR_QUADRATIC: return &a->quad;
+    case RS_ADAPT_IVECTOR_COUNT: if (a->has_iv) tmp->assign(1, a->num_frames); return tmp;
+    case RS_ADAPT_CMVN_IVECTOR: return &a->cmvn_iv;
+    case RS_ADAPT_CMVN_NNET: return &a->cmvn_nn;
+    default: return nullptr;
+  }
+}
+
+int rs_adaptation_export(const rs_adaptation *a, int32_t what, double *buf, int64_t cap, int64_t *n) {
+  if (!a || !n) return ArgError("rs_adaptation_export: null argument");
+  std::vector<double> tmp;
+  const std::vector<double> *v = AdaptBlock(a, what, &tmp);
+  if (!v) return ArgError("rs_adaptation_export: no such block");
+  *n = (int64_t)v->size();
+  if (*n > 0 && (!buf || cap < *n)) return ArgError("rs_adaptation_export: buffer too small");
+  g_last_error.clear();
+  if (!v->empty()) std::memcpy(buf, v->data(), 8 * v->size());
+  return RS_OK;
+}
+
+int rs_adaptation_import(const rs_model *model, const double *ivector_linear, int64_t n_linear, const double *ivector_quadratic, int64_t n_quadratic,
+                         double ivector_count, const double *cmvn_ivector, int64_t n_cmvn_ivector, const double *cmvn_nnet, int64_t n_cmvn_nnet,
+                         rs_adaptation **out) {
+  if (!model || !out) return ArgError("rs_adaptation_import: null argument");
+  if (n_linear < 0 || n_quadratic < 0 || n_cmvn_ivector < 0 || n_cmvn_nnet < 0 || (n_linear > 0 && !ivector_linear) || (n_quadratic > 0 && !ivector_quadratic) ||
+      (n_cmvn_ivector > 0 && !cmvn_ivector) || (n_cmvn_nnet > 0 && !cmvn_nnet))
+    return ArgError("rs_adaptation_import: bad argument");
+  return Guard([&]() {
+    std::unique_ptr<rs_adaptation> a(new rs_adaptation());
+    model->m->AdaptationFresh(a.get());
+    if ((int64_t)a->lin.size() != n_linear || (int64_t)a->quad.size() != n_quadratic || (int64_t)a->cmvn_iv.size() != n_cmvn_ivector ||
+        (int64_t)a->cmvn_nn.size() != n_cmvn_nnet)
+      return ArgError(("rs_adaptation_import: the arrays do not have the model's sizes (iVector linear " + std::to_string(a->lin.size()) + ", quadratic " +
+                       std::to_string(a->quad.size()) + ", iVector-branch CMVN " + std::to_string(a->cmvn_iv.size()) + ", nnet-input CMVN " +
+                       std::to_string(a->cmvn_nn.size()) + ")").c_str());
+    auto finite = [](const double *p, int64_t n) { for (int64_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false; return true; };
+    if (!finite(ivector_linear, n_linear) || !finite(ivector_quadratic, n_quadratic) || !finite(cmvn_ivector, n_cmvn_ivector) || !finite(cmvn_nnet, n_cmvn_nnet) ||
+        !std::isfinite(ivector_count))
+      return ArgError("rs_adaptation_import: a value is not finite");
+    const int C = a->feat_dim;
+    if (ivector_count < 0.0 || (n_cmvn_ivector > 0 && cmvn_ivector[C] < 0.0) || (n_cmvn_nnet > 0 && cmvn_nnet[C] < 0.0))
+      return ArgError("rs_adaptation_import: a count is negative");
+    if (a->has_iv) {
+      a->lin.assign(ivector_linear, ivector_linear + n_linear);
+      a->quad.assign(ivector_quadratic, ivector_quadratic + n_quadratic);
+      a->num_frames = ivector_count;
+      a->cmvn_iv.assign(cmvn_ivector, cmvn_ivector + n_cmvn_ivector);
+    }
+    if (a->has_nn) a->cmvn_nn.assign(cmvn_nnet, cmvn_nnet + n_cmvn_nnet);
+    *out = a.release();
+    return (int)RS_OK;
+  });
+}
+
+void rs_adaptation_free(rs_adaptation *a) { delete a; }
 
 int32_t rs_result_num_utts(const rs_result *r) { return r ? (int32_t)r->r->utts.size() : 0; }
 

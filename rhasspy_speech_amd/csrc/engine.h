@@ -155,8 +155,14 @@ class Model {
   const Hclg &hclg() const { return hclg_; }
   // Streams (stream.cc): a stream owns a slot and a row range of the model's pool from open to close; advance runs the
   // device work the accepted audio makes possible, batched over the given streams; final = end of input, results to res.
-  void StreamOpen(rs_stream *st);
+  void StreamOpen(rs_stream *st, const rs_adaptation *state = nullptr);      // state: checked by the caller (AdaptationMismatch)
   void StreamClose(rs_stream *st);
+  // Speaker adaptation (stream.cc): a stream that ended through a finish / finalize keeps its slot and rows until it is freed (or the
+  // pool needs them), so that StreamsAdaptation can take what OnlineIvectorFeature::GetAdaptationState / GetCmvnState return
+  void StreamEnd(rs_stream *st, bool flushed);
+  void StreamsAdaptation(rs_stream *const *streams, int n, rs_adaptation **out);      // out[i]: allocated by the caller
+  void AdaptationFresh(rs_adaptation *a) const;                                        // what the reference constructs per speaker
+  std::string AdaptationMismatch(const rs_adaptation &a) const;                         // "" = the state fits this model
   void StreamsAdvance(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res);
   void StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res,
                             bool every_tick = false, bool no_flush = false);      // pool_mu_ held; every_tick: no min_ticks coalescing; no_flush (with final): rs_streams_finalize
@@ -328,4 +334,18 @@ struct rs_stream {
   int ll_done = 0;                 // frames with log-likelihoods in the pool
   int frames_decoded = 0;          // frames the incremental search has consumed
   bool dec_started = false;
+  // speaker adaptation
+  bool ended = false;              // finished / finalized, slot and rows still held for rs_streams_adaptation
+  bool reclaimed = false;          // ... no longer: the pool needed them
+  int adapt_frames = 0;            // raw MFCC frames the state's CMVN statistics cover
+  std::vector<double> spk0;        // speaker CMVN statistics the stream was opened with: [2 x (C + 1) iVector branch | 2 x (C + 1) nnet input], empty: none
+  bool spk_iv = false, spk_nn = false;      // ... with a count above zero: the CMVN of that branch reads them from the slot
+};
+// online2/online-ivector-feature.h: OnlineIvectorExtractorAdaptationState, plus the nnet-input OnlineCmvnState where the model has one
+struct rs_adaptation {
+  int feat_dim = 0, ivec_dim = 0;
+  bool has_iv = false, has_nn = false;
+  std::vector<double> lin, quad;   // the estimator's linear term, its quadratic term (packed lower triangle, row by row)
+  double num_frames = 0.0;
+  std::vector<double> cmvn_iv, cmvn_nn;      // speaker CMVN statistics, 2 x (feat_dim + 1): iVector branch (limited), nnet input (not limited)
 };

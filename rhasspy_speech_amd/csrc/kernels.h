@@ -116,8 +116,28 @@ struct CmvnDev {
 // in/out: total_rows x ld, same layout.  Halo rows of `out` replicate its edge frames.
 // Streams: t_begin[u] = first frame to produce (frames before it were produced by earlier launches), state = parked running
 // sums + window count, (dim + 1) doubles per slot, slot of utterance u = state_slot[u].  No halo rows are written then.
+// Speaker statistics (streams opened with an adaptation state; spk != null selects the kernel that has the term): spk = the carried
+// sums and their count, (dim + 1) doubles per slot, spk_slot[u] = the slot of utterance u or -1 for a stream without them.
 void LaunchOnlineCmvn(const CmvnDev &c, const BatchGeom &g, const float *in, float *out, int ld, hipStream_t s, const int *t_begin = nullptr,
-                      double *state = nullptr, const int *state_slot = nullptr);
+                      double *state = nullptr, const int *state_slot = nullptr, const double *spk = nullptr, const int *spk_slot = nullptr);
+
+// ---------------------------------------------------------------- speaker adaptation state of ended streams (adapt_kernels.hip)
+// Per listed stream: the speaker CMVN statistics it started with (carried: [2 x (dim + 1) iVector branch | 2 x (dim + 1) nnet-input
+// branch] doubles, zeros where there are none) plus (1, x, x^2) of its raw MFCC rows [row0, row0 + frames), in frame order; the
+// estimator's statistics from its slot; LimitFrames on the iVector branch's block and on the estimator's statistics.
+// out (out_stride doubles per stream): [linear ivec_dim | quadratic, packed | num_frames] (has_iv), then the iVector branch's block
+// (has_iv), then the nnet-input branch's (has_nn).
+struct AdaptWork {
+  int n_streams, dim, ld, ivec_dim, has_iv, has_nn;
+  const float *raw;
+  const int *row0, *frames, *slot;
+  const double *carried;
+  const double *lin, *quad, *numf;
+  double max_remembered, max_remembered_scaled, max_count, prior_offset;      // _scaled: x posterior_scale, in float like the reference
+  double *out;
+  long out_stride;
+};
+void LaunchAdaptGet(const AdaptWork &w, hipStream_t s);
 
 // ---------------------------------------------------------------- generic segmented GEMM (FP32 MFMA)
 constexpr int kGemmBM = 128, kGemmBN = 128, kGemmBK = 32;

@@ -146,6 +146,17 @@ struct StreamPool {
   int *bp = nullptr;
   int max_slots = 0;
   double *lin = nullptr, *quad = nullptr, *numf = nullptr, *x = nullptr, *cmvn_iv = nullptr, *cmvn_nn = nullptr;
+  // Speaker adaptation (rs_stream_open_adapted / rs_streams_adaptation): the speaker CMVN sums + count a stream was opened with,
+  // (C + 1) doubles per slot and CMVN object (read only by streams that have them: rs_stream::spk_iv / spk_nn)
+  double *spk_iv = nullptr, *spk_nn = nullptr;
+  // ... a pinned buffer the carried state of one open is staged in, and the event behind the copies out of it
+  double *seed_h = nullptr;
+  size_t seed_cap = 0;
+  hipEvent_t seed_ev = nullptr;
+  bool seed_pending = false;
+  // Streams that have ended (finish / finalize) but are not freed: they keep their slot and rows, so that their adaptation state can
+  // still be taken, until they are freed or an open / a growing stream needs the room (oldest first)
+  std::vector<rs_stream *> ended;
   long long *dec_ctr = nullptr;
   // rs_streams_partial on register-resident streams (decode_partial.hip): the previous call's best path per row, its length and
   // words per slot
@@ -193,6 +204,9 @@ void StreamPoolDeleter::operator()(StreamPool *p) const {
     for (hipEvent_t e : {p->ev_a[k], p->ev_b[k], p->ev_done[k], p->ev_f[k], p->ev_i[k]}) if (e) (void)hipEventDestroy(e);
   }
   for (void *d : p->owned) (void)hipFree(d);
+  if (p->seed_h) (void)hipHostFree(p->seed_h);
+  if (p->seed_ev) (void)hipEventDestroy(p->seed_ev);
+  for (rs_stream *st : p->ended) { st->ended = false; st->reclaimed = true; }      // (freed after their model: nothing left to release)
   if (p->q) (void)hipStreamDestroy(p->q);
   if (p->qa) (void)hipStreamDestroy(p->qa);
   if (p->qc) (void)hipStreamDestroy(p->qc);
@@ -287,8 +301,13 @@ StreamPool *Model::Pool() {
     p->numf = static_cast<double *>(dalloc((size_t)p->max_slots * 8));
     p->x = static_cast<double *>(dalloc((size_t)p->max_slots * Di * 8));
     p->cmvn_iv = static_cast<double *>(dalloc((size_t)p->max_slots * (C + 1) * 8));
+    p->spk_iv = static_cast<double *>(dalloc((size_t)p->max_slots * (C + 1) * 8));
   }
-  if (fc_.use_cmvn) p->cmvn_nn = static_cast<double *>(dalloc((size_t)p->max_slots * (C + 1) * 8));
+  if (fc_.use_cmvn) {
+    p->cmvn_nn = static_cast<double *>(dalloc((size_t)p->max_slots * (C + 1) * 8));
+    p->spk_nn = static_cast<double *>(dalloc((size_t)p->max_slots * (C + 1) * 8));
+  }
+  RS_HIP(hipEventCreateWithFlags(&p->seed_ev, hipEventDisableTiming));
   for (int s = p->max_slots - 1; s >= 0; s--) p->free_slots.push_back(s);
   p->free_rows[0] = p->rows;
   std::unique_ptr<DecodeContext> c(new DecodeContext());
@@ -360,23 +379,111 @@ void Model::StreamsCheckRange() {
   }
 }
 
-void Model::StreamOpen(rs_stream *st) {
+// An ended stream gives its slot and rows back: nothing is in flight on them (the call that ended it waited for everything)
+static void ReleaseEnded(StreamPool *p, rs_stream *st, bool reclaimed) {
+  p->FreeRows(st->row0, st->cap);
+  p->free_slots.push_back(st->slot);
+  st->ended = false;
+  st->reclaimed = reclaimed;
+  p->ended.erase(std::remove(p->ended.begin(), p->ended.end(), st), p->ended.end());
+}
+
+// rows for a stream; ended streams that still hold theirs make room, oldest first
+static int AllocRowsReclaiming(StreamPool *p, int want) {
+  int row0 = p->AllocRows(want);
+  while (row0 < 0 && !p->ended.empty()) { ReleaseEnded(p, p->ended.front(), true); row0 = p->AllocRows(want); }
+  return row0;
+}
+
+void Model::AdaptationFresh(rs_adaptation *a) const {
+  const int C = fc_.mfcc.nceps;
+  *a = rs_adaptation();
+  a->feat_dim = C;
+  a->has_iv = fc_.ie.present;
+  a->has_nn = fc_.use_cmvn;
+  if (a->has_iv) {
+    // the estimator as its constructor leaves it (ivector-extractor.cc: quadratic = I, linear = [prior_offset, 0, ...], no frames)
+    const int Di = fc_.ie.ivector_dim();
+    a->ivec_dim = Di;
+    a->lin.assign(Di, 0.0);
+    a->lin[0] = fc_.ie.prior_offset;
+    a->quad.assign((size_t)Di * (Di + 1) / 2, 0.0);
+    for (int r = 0; r < Di; r++) a->quad[(size_t)r * (r + 1) / 2 + r] = 1.0;
+    a->cmvn_iv.assign(2 * (size_t)(C + 1), 0.0);
+  }
+  if (a->has_nn) a->cmvn_nn.assign(2 * (size_t)(C + 1), 0.0);
+}
+
+std::string Model::AdaptationMismatch(const rs_adaptation &a) const {
+  const int C = fc_.mfcc.nceps, Di = fc_.ie.present ? fc_.ie.ivector_dim() : 0;
+  if (a.has_iv != fc_.ie.present || a.ivec_dim != Di) return "the state's iVector dimension (" + std::to_string(a.ivec_dim) + ") is not the model's (" + std::to_string(Di) + ")";
+  if (a.has_nn != fc_.use_cmvn) return std::string("the state ") + (a.has_nn ? "has" : "lacks") + " nnet-input CMVN statistics and the model " + (fc_.use_cmvn ? "has" : "lacks") + " that CMVN";
+  if ((a.has_iv || a.has_nn) && a.feat_dim != C) return "the state's feature dimension (" + std::to_string(a.feat_dim) + ") is not the model's (" + std::to_string(C) + ")";
+  if (a.lin.size() != (size_t)Di || a.quad.size() != (size_t)Di * (Di + 1) / 2 || a.cmvn_iv.size() != (a.has_iv ? 2 * (size_t)(C + 1) : 0) ||
+      a.cmvn_nn.size() != (a.has_nn ? 2 * (size_t)(C + 1) : 0))
+    return "the state's arrays do not have the model's sizes";
+  return std::string();
+}
+
+void Model::StreamOpen(rs_stream *st, const rs_adaptation *state) {
   std::lock_guard<std::mutex> lk(pool_mu_);
   StreamPool *p = Pool();
   RS_HIP(hipSetDevice(opts_.device_id));
   // (this call queues on qi / qc itself.  A failure of an earlier advance's deferred work belongs to the streams that are open, not to
   // the one being opened: they are poisoned with its message and refuse their next call; the open goes ahead on the drained pool)
   try { IssuerSync(p); } catch (...) {}
+  if (p->free_slots.empty() && !p->ended.empty()) ReleaseEnded(p, p->ended.front(), true);
   if (p->free_slots.empty()) Fail("too many live streams on this model (RS_STREAM_SLOTS=" + std::to_string(p->max_slots) + ")");
   const int want = RoundUp(std::max(EnvInt("RS_STREAM_INIT_FRAMES", 4096), 2 * p->chunk), p->chunk);
-  const int row0 = p->AllocRows(want);
+  const int row0 = AllocRowsReclaiming(p, want);
   if (row0 < 0) Fail("stream pool exhausted (RS_STREAM_POOL_ROWS=" + std::to_string(p->rows) + " frame rows of live audio)");
   st->slot = p->free_slots.back();
   p->free_slots.pop_back();
   st->row0 = row0;
   st->cap = want;
-  // fresh estimator / search state in the slot
-  if (fc_.ie.present) {
+  // fresh estimator / search state in the slot -- or the carried one (SetAdaptationState, online-ivector-feature.cc:445-453:
+  // the statistics are replaced, the CG solution keeps its constructor value [prior_offset, 0, ...]; SetCmvnState)
+  if (state) {
+    const int C = fc_.mfcc.nceps, C1 = C + 1, Di = state->ivec_dim, usz = Di * (Di + 1) / 2;
+    const size_t need = (size_t)2 * Di + usz + 1 + 2 * (size_t)C1;
+    if (p->seed_pending) { RS_HIP(hipEventSynchronize(p->seed_ev)); p->seed_pending = false; }      // (the previous open's copies have left the buffer)
+    if (p->seed_cap < need) {
+      if (p->seed_h) RS_HIP(hipHostFree(p->seed_h));
+      p->seed_h = nullptr; p->seed_cap = 0;
+      RS_HIP(hipHostMalloc((void **)&p->seed_h, need * 8, hipHostMallocDefault));
+      p->seed_cap = need;
+    }
+    double *h_lin = p->seed_h, *h_quad = h_lin + Di, *h_numf = h_quad + usz, *h_x = h_numf + 1, *h_iv = h_x + Di, *h_nn = h_iv + C1;
+    st->spk0.assign(4 * (size_t)C1, 0.0);
+    if (state->has_iv) {
+      std::memcpy(h_lin, state->lin.data(), 8 * (size_t)Di);
+      std::memcpy(h_quad, state->quad.data(), 8 * (size_t)usz);
+      *h_numf = state->num_frames;
+      for (int i = 0; i < Di; i++) h_x[i] = i == 0 ? fc_.ie.prior_offset : 0.0;
+      std::memcpy(h_iv, state->cmvn_iv.data(), 8 * (size_t)C1);
+      std::memcpy(st->spk0.data(), state->cmvn_iv.data(), 8 * 2 * (size_t)C1);
+      st->spk_iv = state->cmvn_iv[C] > 0.0;
+      // (the estimator's state on the iVector steps' queue, the speaker sums on the features' queue: the queues that read them)
+      RS_HIP(hipMemcpyAsync(p->lin + (size_t)st->slot * Di, h_lin, 8 * (size_t)Di, hipMemcpyHostToDevice, p->qi));
+      RS_HIP(hipMemcpyAsync(p->quad + (size_t)st->slot * usz, h_quad, 8 * (size_t)usz, hipMemcpyHostToDevice, p->qi));
+      RS_HIP(hipMemcpyAsync(p->numf + st->slot, h_numf, 8, hipMemcpyHostToDevice, p->qi));
+      RS_HIP(hipMemcpyAsync(p->x + (size_t)st->slot * Di, h_x, 8 * (size_t)Di, hipMemcpyHostToDevice, p->qi));
+      if (st->spk_iv) RS_HIP(hipMemcpyAsync(p->spk_iv + (size_t)st->slot * C1, h_iv, 8 * (size_t)C1, hipMemcpyHostToDevice, p->qa));
+    }
+    if (state->has_nn) {
+      std::memcpy(h_nn, state->cmvn_nn.data(), 8 * (size_t)C1);
+      std::memcpy(st->spk0.data() + 2 * C1, state->cmvn_nn.data(), 8 * 2 * (size_t)C1);
+      st->spk_nn = state->cmvn_nn[C] > 0.0;
+      if (st->spk_nn) RS_HIP(hipMemcpyAsync(p->spk_nn + (size_t)st->slot * C1, h_nn, 8 * (size_t)C1, hipMemcpyHostToDevice, p->qa));
+    }
+    // one event behind both queues' copies: qa waits for qi's, the event is recorded on qa
+    if (state->has_iv || state->has_nn) {
+      RS_HIP(hipEventRecord(p->seed_ev, p->qi));
+      RS_HIP(hipStreamWaitEvent(p->qa, p->seed_ev, 0));
+      RS_HIP(hipEventRecord(p->seed_ev, p->qa));
+      p->seed_pending = true;
+    }
+  } else if (fc_.ie.present) {
     const int Di = fc_.ie.ivector_dim(), usz = Di * (Di + 1) / 2;
     LaunchIvecInit(ivec_dev_, 1, p->lin + (size_t)st->slot * Di, p->quad + (size_t)st->slot * usz, p->x + (size_t)st->slot * Di, p->numf + st->slot, p->qi);      // (the iVector steps' queue: the estimator state is its)
   }
@@ -386,10 +493,27 @@ void Model::StreamOpen(rs_stream *st) {
   p->open_streams.push_back(st);
 }
 
-void Model::StreamClose(rs_stream *st) {
+// The stream ended through a finish or a finalize that succeeded.  It keeps its slot and rows (see StreamPool::ended): nothing of
+// the pool reads or writes them any more, and no later advance can fail on its behalf.
+void Model::StreamEnd(rs_stream *st, bool flushed) {
   if (!st->open) return;
   std::lock_guard<std::mutex> lk(pool_mu_);
   if (!pool_) return;
+  // the frames GetState covers: all of them after a finish; after a finalize those of the complete ticks (what lies beyond the last
+  // complete tick is ignored, as by the results)
+  st->adapt_frames = flushed ? st->frames_mfcc : std::min(st->frames_mfcc, NumFrames(1024L * st->ticks_done, fc_.mfcc.opts));
+  st->open = false;
+  st->ended = true;
+  auto &os = pool_->open_streams;
+  os.erase(std::remove(os.begin(), os.end(), st), os.end());
+  pool_->ended.push_back(st);
+}
+
+void Model::StreamClose(rs_stream *st) {
+  if (!st->open && !st->ended) return;
+  std::lock_guard<std::mutex> lk(pool_mu_);
+  if (!pool_) return;
+  if (st->ended) { ReleaseEnded(pool_.get(), st, false); return; }
   // an advance that still uses the stream's rows / slot finishes first (a device error of it is the other streams' to report:
   // this one is going away either way)
   try { StreamsDrain(pool_.get(), nullptr); } catch (...) { pool_->issuer.Drain(false); (void)hipStreamSynchronize(pool_->qa); (void)hipStreamSynchronize(pool_->qi); (void)hipStreamSynchronize(pool_->q); (void)hipStreamSynchronize(pool_->qc); }
@@ -422,7 +546,7 @@ void Model::StreamGrow(rs_stream *st, int need_frames) {
   StreamsDrain(p, nullptr);                 // both queues idle: the rows move under nobody's feet
   int want = st->cap;
   while (want < need_frames) want *= 2;
-  const int row0 = p->AllocRows(want);
+  const int row0 = AllocRowsReclaiming(p, want);
   if (row0 < 0) Fail("stream pool exhausted (RS_STREAM_POOL_ROWS=" + std::to_string(p->rows) + " frame rows of live audio)");
   const size_t n = (size_t)st->cap;
   auto mv = [&](void *base, size_t row_bytes) {
@@ -565,9 +689,15 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
   m_T.push_back(0);
   m_f0.push_back(0);
   // stage 2: CMVN resumed (same streams)
-  std::vector<int> c_T, c_rb, c_tb, c_slot;
+  std::vector<int> c_T, c_rb, c_tb, c_slot, c_spk_iv, c_spk_nn;
+  bool any_spk_iv = false, any_spk_nn = false;      // a stream of the call carries speaker statistics: the CMVN kernel with that term
   for (int i = 0; i < n; i++)
-    if (pl[i].avail > pl[i].mf0) { c_T.push_back(pl[i].avail); c_rb.push_back(streams[i]->row0); c_tb.push_back(pl[i].mf0); c_slot.push_back(streams[i]->slot); }
+    if (pl[i].avail > pl[i].mf0) {
+      const rs_stream &st = *streams[i];
+      c_T.push_back(pl[i].avail); c_rb.push_back(st.row0); c_tb.push_back(pl[i].mf0); c_slot.push_back(st.slot);
+      c_spk_iv.push_back(st.spk_iv ? st.slot : -1); c_spk_nn.push_back(st.spk_nn ? st.slot : -1);
+      any_spk_iv = any_spk_iv || st.spk_iv; any_spk_nn = any_spk_nn || st.spk_nn;
+    }
   c_rb.push_back(0);
   // stage 3: iVector segments
   std::vector<int> I_idx;
@@ -666,6 +796,7 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
   }
   const size_t o_mT = is.Add(m_T), o_mrb = is.Add(m_rb), o_mout = is.Add(m_out), o_mf0 = is.Add(m_f0), o_mso = is.Add64(m_so);
   const size_t o_cT = is.Add(c_T), o_crb = is.Add(c_rb), o_ctb = is.Add(c_tb), o_cslot = is.Add(c_slot);
+  const size_t o_cspki = any_spk_iv ? is.Add(c_spk_iv) : 0, o_cspkn = any_spk_nn ? is.Add(c_spk_nn) : 0;
   const size_t o_iT = is.Add(i_T), o_irb = is.Add(i_rb), o_isrc = is.Add(i_src), o_islot = is.Add(i_slot);
   const size_t o_sfb = is.Add(s_fb), o_sfe = is.Add(s_fe), o_sor = is.Add(s_or), o_sac = is.Add(s_ac);
   is.Add(n_T);
@@ -730,8 +861,9 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
     // ---------------------------------------------------------------- 2. CMVN, resumed
     BatchGeom gc;
     gc.n_utts = nM; gc.d_num_frames = D(o_cT); gc.d_row_base = D(o_crb);
-    if (has_iv) LaunchOnlineCmvn(cmvn_iv_dev_, gc, p->raw, p->cm, ld_c, qa, D(o_ctb), p->cmvn_iv, D(o_cslot));
-    if (fc_.use_cmvn) LaunchOnlineCmvn(cmvn_nnet_dev_, gc, p->raw, p->nn_in, ld_c, qa, D(o_ctb), p->cmvn_nn, D(o_cslot));
+    if (has_iv) LaunchOnlineCmvn(cmvn_iv_dev_, gc, p->raw, p->cm, ld_c, qa, D(o_ctb), p->cmvn_iv, D(o_cslot), any_spk_iv ? p->spk_iv : nullptr, any_spk_iv ? D(o_cspki) : nullptr);
+    if (fc_.use_cmvn)
+      LaunchOnlineCmvn(cmvn_nnet_dev_, gc, p->raw, p->nn_in, ld_c, qa, D(o_ctb), p->cmvn_nn, D(o_cslot), any_spk_nn ? p->spk_nn : nullptr, any_spk_nn ? D(o_cspkn) : nullptr);
   }
   TM_MARK(tma);
   // ---------------------------------------------------------------- 3. iVectors of the new chunks
@@ -1184,6 +1316,79 @@ void Model::StreamsFinalize(rs_stream *const *streams, int n, int nbest, float l
     throw;
   } catch (...) {
     if (pool_) { pool_->issuer.Drain(false); (void)hipStreamSynchronize(pool_->qa); (void)hipStreamSynchronize(pool_->qi); (void)hipStreamSynchronize(pool_->q); (void)hipStreamSynchronize(pool_->qc); }
+    throw;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------- speaker adaptation
+// rs_streams_adaptation: the reference's GetAdaptationState / GetCmvnState (online2-wav-nnet3-latgen-faster.cc:287-288) of streams
+// that have ended, in one launch over the listed streams (adapt_kernels.hip) and one copy to the host.  The streams still hold
+// their slots and rows (StreamEnd); everything that wrote them has been waited for by the call that ended them.
+void Model::StreamsAdaptation(rs_stream *const *streams, int n, rs_adaptation **out) {
+  std::lock_guard<std::mutex> lk(pool_mu_);
+  try {
+    StreamPool *p = Pool();
+    RS_HIP(hipSetDevice(opts_.device_id));
+    const bool has_iv = fc_.ie.present, has_nn = fc_.use_cmvn;
+    const int C = fc_.mfcc.nceps, C1 = C + 1, Di = has_iv ? fc_.ie.ivector_dim() : 0, usz = Di * (Di + 1) / 2;
+    const size_t stride = (has_iv ? (size_t)Di + usz + 1 + 2 * C1 : 0) + (has_nn ? 2 * (size_t)C1 : 0);
+    if (stride == 0) {      // no extractor, no nnet-input CMVN: the state is empty
+      for (int i = 0; i < n; i++) AdaptationFresh(out[i]);
+      return;
+    }
+    StreamsDrain(p, nullptr);      // the arena sets are free (advances of other streams may have been in flight)
+    DecodeContext &cx = *static_cast<DecodeContext *>(p->cx);
+    const int par = (int)(p->n_adv % StreamPool::kDepth);
+    DeviceArena &arena = cx.arena[par];
+    HostArena &harena = cx.host_arena[par];
+    hipStream_t qc = p->qc;
+    arena.Reserve((size_t)n * (3 * 4 + (4 * (size_t)C1 + stride) * 8) + 8192, qc);
+    arena.Reset();
+    harena.Reset();
+    int *d_idx = arena.AllocT<int>((size_t)3 * n + 16);
+    double *d_car = arena.AllocT<double>((size_t)n * 4 * C1 + 8), *d_out = arena.AllocT<double>((size_t)n * stride + 8);
+    {
+      int *h = harena.AllocT<int>((size_t)3 * n + 16);
+      double *hc = harena.AllocT<double>((size_t)n * 4 * C1 + 8);
+      for (int i = 0; i < n; i++) {
+        const rs_stream &st = *streams[i];
+        h[i] = st.row0; h[n + i] = st.adapt_frames; h[2 * n + i] = st.slot;
+        if (st.spk0.empty()) std::memset(hc + (size_t)i * 4 * C1, 0, 8 * 4 * (size_t)C1);
+        else std::memcpy(hc + (size_t)i * 4 * C1, st.spk0.data(), 8 * 4 * (size_t)C1);
+      }
+      RS_HIP(hipMemcpyAsync(d_idx, h, sizeof(int) * 3 * n, hipMemcpyHostToDevice, qc));
+      RS_HIP(hipMemcpyAsync(d_car, hc, 8 * (size_t)n * 4 * C1, hipMemcpyHostToDevice, qc));
+    }
+    AdaptWork w;
+    std::memset(&w, 0, sizeof(w));
+    w.n_streams = n; w.dim = C; w.ld = p->ld_c; w.ivec_dim = Di; w.has_iv = has_iv ? 1 : 0; w.has_nn = has_nn ? 1 : 0;
+    w.raw = p->raw; w.row0 = d_idx; w.frames = d_idx + n; w.slot = d_idx + 2 * n;
+    w.carried = d_car; w.lin = p->lin; w.quad = p->quad; w.numf = p->numf;
+    // LimitFrames(max_remembered_frames, posterior_scale): the iVector statistics' target count is the FLOAT product, as there
+    w.max_remembered = (double)fc_.ie.max_remembered_frames;
+    w.max_remembered_scaled = (double)(float)(fc_.ie.max_remembered_frames * fc_.ie.posterior_scale);
+    w.max_count = (double)fc_.ie.max_count; w.prior_offset = fc_.ie.prior_offset;
+    w.out = d_out; w.out_stride = (long)stride;
+    LaunchAdaptGet(w, qc);
+    { const hipError_t le = hipGetLastError(); if (le != hipSuccess) Fail(std::string("a kernel launch failed: ") + hipGetErrorString(le)); }
+    double *h_out = harena.AllocT<double>((size_t)n * stride + 8);
+    RS_HIP(hipMemcpyAsync(h_out, d_out, 8 * (size_t)n * stride, hipMemcpyDeviceToHost, qc));
+    RS_HIP(hipStreamSynchronize(qc));
+    for (int i = 0; i < n; i++) {
+      rs_adaptation &a = *out[i];
+      AdaptationFresh(&a);
+      const double *o = h_out + (size_t)i * stride;
+      if (has_iv) {
+        std::memcpy(a.lin.data(), o, 8 * (size_t)Di);
+        std::memcpy(a.quad.data(), o + Di, 8 * (size_t)usz);
+        a.num_frames = o[Di + usz];
+        std::memcpy(a.cmvn_iv.data(), o + Di + usz + 1, 8 * 2 * (size_t)C1);
+        o += (size_t)Di + usz + 1 + 2 * C1;
+      }
+      if (has_nn) std::memcpy(a.cmvn_nn.data(), o, 8 * 2 * (size_t)C1);
+    }
+  } catch (const DeviceError &) {
+    StreamsPoisonAll();
     throw;
   }
 }

@@ -9,6 +9,8 @@ online2-tcp-nnet3-decode-faster.cc:302-318), and returns what `async_transcribe`
 `async_transcribe_until_endpoint` also asks, after every chunk, whether the reference's endpointing rules fire
 (online2/online-endpoint.cc; rs_stream_endpoint) and, when they do, stops reading audio and finalizes the frames decoded so far
 like online2-wav-nnet3-latgen-faster.cc:270-278 does.
+`async_transcribe_continuous` keeps listening after an endpoint: one transcript per utterance, every utterance after the first
+opened with the speaker adaptation state of the ones before (online2-wav-nnet3-latgen-faster.cc:203-205, 220-221, 287-288).
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import asyncio
 import logging
 from collections.abc import AsyncIterable
 from pathlib import Path
-from typing import Callable, List, Optional, Union
+from typing import AsyncIterator, Callable, List, Optional, Union
 
 from . import _lib
 from .meta import decode_meta, int2sym, read_words_txt, texts_from_int2sym
@@ -51,6 +53,7 @@ class KaldiNnet3StreamTranscriber:
         self._lat_model: Optional[_lib.Model] = None      # the same files, results keep their lattices (rescoring path)
         self._rescorers = {}
         self.last_endpoint_rule = 0      # async_transcribe_until_endpoint: the rule (1..5) that ended the last call, 0 = the audio ended first
+        self.last_adaptation: Optional[_lib.Adaptation] = None      # async_transcribe_continuous: the speaker's state after the last utterance
 
     def _ensure_loaded(self) -> _lib.Model:
         if self._model is None:
@@ -180,6 +183,10 @@ class KaldiNnet3StreamTranscriber:
                 raise RuntimeError(f"Unexpected error running command online2-cli-nnet3-decode-faster (HIP): {e}") from e
         finally:
             stream.close()
+        return self._texts(nbest_stdout, lang_dir, max_fuzzy_cost, require_fuzzy)
+
+    def _texts(self, nbest_stdout: bytes, lang_dir: Path, max_fuzzy_cost, require_fuzzy) -> List[str]:
+        """The n-best list of one utterance -> its texts (the post-processing every entry point shares)."""
         int2sym_stdout = int2sym(nbest_stdout, self._words)
         _LOGGER.debug("nbest: %s", int2sym_stdout)
         fuzzy_result = get_fuzzy_text(nbest_stdout, lang_dir)      # transcribe_stream.py:111-116
@@ -191,6 +198,81 @@ class KaldiNnet3StreamTranscriber:
         if require_fuzzy:
             return []
         return texts_from_int2sym(int2sym_stdout)
+
+    # ---- one speaker, utterance after utterance
+    @staticmethod
+    def _accept_tick(stream, tick, endpoint_opts) -> int:
+        stream.accept(tick)
+        return int(stream.endpoint(endpoint_opts).detected)
+
+    @staticmethod
+    def _end_utterance(stream, fired: bool, nbest: int, acoustic_scale: float):
+        """-> (the n-best list, the speaker's state after the utterance)"""
+        res = (stream.finalize if fired else stream.finish)(nbest, acoustic_scale)
+        try:
+            return res.text(0, "utt"), stream.adaptation()
+        finally:
+            res.close()
+
+    async def async_transcribe_continuous(
+        self,
+        audio_stream: AsyncIterable[Optional[bytes]],
+        lang_dir: Union[str, Path],
+        nbest: int = 1,
+        max_fuzzy_cost: Optional[float] = None,
+        require_fuzzy: bool = False,
+        endpoint_opts=None,
+        adaptation: Optional[_lib.Adaptation] = None,
+    ) -> AsyncIterator[List[str]]:
+        """An async generator over ONE speaker's audio: yields what `async_transcribe` returns, once per utterance.  The audio is
+        cut into the 1024-sample ticks of the stream binary; after every tick the stream is asked for an endpoint
+        (rs_stream_endpoint, `endpoint_opts` None = the model's).  On a detection the utterance is finalized at that tick
+        (rs_stream_finalize), its adaptation state is taken (rs_stream_adaptation) and the next utterance is opened with it
+        (rs_stream_open_adapted); audio that arrived after the deciding tick goes to the next utterance, in order.  The last
+        utterance ends with the audio (rs_stream_finish: the feature tail is flushed); nothing is yielded for an utterance without
+        audio.  `adaptation`: the speaker's state from an earlier call or process (None = a new speaker); `self.last_adaptation` holds
+        the state after the last utterance yielded."""
+        lang_dir = Path(lang_dir)
+        model = self._ensure_loaded()
+        loop = asyncio.get_running_loop()
+        tick_bytes = 2 * 1024
+        state = adaptation
+        stream = _lib.Stream(model, adaptation=state)
+        pending = bytearray()
+        fed = 0                # bytes the current utterance has got
+
+        async def end(fired: bool):
+            nonlocal stream, state, fed
+            try:
+                nbest_stdout, state = await loop.run_in_executor(None, self._end_utterance, stream, fired, nbest, self.acoustic_scale)
+            except _lib.RsError as e:
+                raise RuntimeError(f"Unexpected error running command online2-cli-nnet3-decode-faster (HIP): {e}") from e
+            finally:
+                stream.close()
+            self.last_adaptation = state
+            stream, fed = _lib.Stream(model, adaptation=state), 0
+            return self._texts(nbest_stdout, lang_dir, max_fuzzy_cost, require_fuzzy)
+
+        try:
+            async for chunk in audio_stream:
+                if not chunk:
+                    continue
+                pending += chunk
+                while len(pending) >= tick_bytes:
+                    tick = bytes(pending[:tick_bytes])
+                    del pending[:tick_bytes]
+                    fed += tick_bytes
+                    fired = await loop.run_in_executor(None, self._accept_tick, stream, tick, endpoint_opts)
+                    if fired:
+                        _LOGGER.debug("Endpoint detected by rule %d", fired)
+                        yield await end(True)
+            if pending:
+                await loop.run_in_executor(None, stream.accept, bytes(pending))
+                fed += len(pending)
+            if fed:
+                yield await end(False)
+        finally:
+            stream.close()
 
     # ---- rescoring path (transcribe_stream.py:131-274): stream through the old graph, re-rank the lattice with a NEW lexicon + LM
     async def async_transcribe_rescore(
