@@ -58,6 +58,56 @@ def parse_vec_ark(text: str):
     return out
 
 
+def run_reference(case: dict, root: Path, model_dir: Path, graph_dir: Path, wav: Path, pcm: np.ndarray, env: dict) -> dict:
+    """The reference's binaries on one utterance, offline and streamed: exit status (with the end of stderr when it is not 0), n-best
+    text and costs, and rs-dump's features, iVectors, chunk ticks and log-likelihoods (in full)."""
+    conf = model_dir / "model" / "online" / "conf" / "online.conf"
+    mdl = model_dir / "model" / "model" / "final.mdl"
+    out = {}
+    for mode in ("offline", "stream"):
+        lat = root / f"{mode}.lat"
+        if mode == "offline":
+            cmd = ["online2-wav-nnet3-latgen-faster", "--online=false", "--do-endpointing=false",
+                   f"--word-symbol-table={graph_dir / 'words.txt'}", f"--config={conf}", *decoder_args(case),
+                   str(mdl), str(graph_dir / "HCLG.fst"), "ark:echo utt utt|", f"scp:echo utt {wav}|", f"ark:{lat}"]
+            p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        else:
+            cmd = ["online2-cli-nnet3-decode-faster", f"--config={conf}", *decoder_args(case), str(mdl),
+                   str(graph_dir / "HCLG.fst"), str(graph_dir / "words.txt"), f"ark:{lat}"]
+            p = subprocess.run(cmd, env=env, input=pcm.astype("<i2").tobytes(), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        if p.returncode != 0:
+            out[f"{mode}_status"] = np.int32(p.returncode)
+            out[f"{mode}_stderr"] = np.frombuffer(p.stderr[-400:], dtype=np.uint8)
+            continue
+        out[f"{mode}_status"] = np.int32(0)
+        sh = (f"lattice-to-nbest --n={NBEST} --acoustic-scale=1.0 ark:{lat} ark:- | "
+              f"nbest-to-linear ark:- ark:/dev/null ark,t:- ark,t:{root}/lm.txt ark,t:{root}/ac.txt")
+        q = run(["bash", "-c", sh], env=env)
+        out[f"{mode}_nbest_text"] = np.frombuffer(q.stdout, dtype=np.uint8)
+        lm = parse_vec_ark((root / "lm.txt").read_text())
+        ac = parse_vec_ark((root / "ac.txt").read_text())
+        keys = sorted(lm, key=lambda k: int(k.split("-")[1]))
+        out[f"{mode}_graph_cost"] = np.array([lm[k][0] for k in keys], np.float32)
+        out[f"{mode}_acoustic_cost"] = np.array([ac[k][0] for k in keys], np.float32)
+        dump = root / f"dump_{mode}"
+        dump.mkdir()
+        run(["rs-dump", f"--config={conf}", "--acoustic-scale=1.0", mode, str(mdl), str(wav), str(dump)], env=env)
+        ll = np.load(dump / "loglikes.npy")
+        out[f"{mode}_num_frames"] = np.int32(ll.shape[0])
+        out[f"{mode}_loglikes"] = ll
+        if mode == "offline":
+            out["input"] = np.load(dump / "input.npy")
+        if (dump / "ivector.npy").exists():
+            iv = np.load(dump / "ivector.npy")
+            out[f"{mode}_ivector"] = iv[:1] if mode == "offline" else iv
+            out[f"{mode}_chunk_tick"] = np.load(dump / "chunk_tick.npy")[0].astype(np.int32)
+        if mode == "offline" and (dump / "lda_norm.npy").exists() and not case.get("big"):
+            out["cmvn"] = np.load(dump / "cmvn.npy")
+            out["lda"] = np.load(dump / "lda.npy")
+            out["lda_norm"] = np.load(dump / "lda_norm.npy")
+    return out
+
+
 def gen_case(name: str, case: dict) -> None:
     env = dict(os.environ, PATH=f"{BIN}:{os.environ['PATH']}")
     with tempfile.TemporaryDirectory() as td:
@@ -65,53 +115,12 @@ def gen_case(name: str, case: dict) -> None:
         model_dir, graph_dir, wav, pcm = build_case_files(case, root)
         conf = model_dir / "model" / "online" / "conf" / "online.conf"
         mdl = model_dir / "model" / "model" / "final.mdl"
-        out = {}
+        out = run_reference(case, root, model_dir, graph_dir, wav, pcm, env)
+        stride = (8, 4) if case.get("big") else (1, 1)      # the big cases keep a strided sample of the log-likelihood matrix
         for mode in ("offline", "stream"):
-            lat = root / f"{mode}.lat"
-            if mode == "offline":
-                cmd = ["online2-wav-nnet3-latgen-faster", "--online=false", "--do-endpointing=false",
-                       f"--word-symbol-table={graph_dir / 'words.txt'}", f"--config={conf}", *decoder_args(case),
-                       str(mdl), str(graph_dir / "HCLG.fst"), "ark:echo utt utt|", f"scp:echo utt {wav}|", f"ark:{lat}"]
-                p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-            else:
-                cmd = ["online2-cli-nnet3-decode-faster", f"--config={conf}", *decoder_args(case), str(mdl),
-                       str(graph_dir / "HCLG.fst"), str(graph_dir / "words.txt"), f"ark:{lat}"]
-                p = subprocess.run(cmd, env=env, input=pcm.astype("<i2").tobytes(), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-            if p.returncode != 0:
-                out[f"{mode}_status"] = np.int32(p.returncode)
-                out[f"{mode}_stderr"] = np.frombuffer(p.stderr[-400:], dtype=np.uint8)
-                continue
-            out[f"{mode}_status"] = np.int32(0)
-            sh = (f"lattice-to-nbest --n={NBEST} --acoustic-scale=1.0 ark:{lat} ark:- | "
-                  f"nbest-to-linear ark:- ark:/dev/null ark,t:- ark,t:{root}/lm.txt ark,t:{root}/ac.txt")
-            q = run(["bash", "-c", sh], env=env)
-            out[f"{mode}_nbest_text"] = np.frombuffer(q.stdout, dtype=np.uint8)
-            lm = parse_vec_ark((root / "lm.txt").read_text())
-            ac = parse_vec_ark((root / "ac.txt").read_text())
-            keys = sorted(lm, key=lambda k: int(k.split("-")[1]))
-            out[f"{mode}_graph_cost"] = np.array([lm[k][0] for k in keys], np.float32)
-            out[f"{mode}_acoustic_cost"] = np.array([ac[k][0] for k in keys], np.float32)
-            dump = root / f"dump_{mode}"
-            dump.mkdir()
-            run(["rs-dump", f"--config={conf}", "--acoustic-scale=1.0", mode, str(mdl), str(wav), str(dump)], env=env)
-            ll = np.load(dump / "loglikes.npy")
-            out[f"{mode}_num_frames"] = np.int32(ll.shape[0])
-            if case.get("big"):
-                out[f"{mode}_loglikes"] = ll[::8, ::4].copy()
-                out["loglikes_stride"] = np.array([8, 4], np.int32)
-            else:
-                out[f"{mode}_loglikes"] = ll
-                out["loglikes_stride"] = np.array([1, 1], np.int32)
-            if mode == "offline":
-                out["input"] = np.load(dump / "input.npy")
-            if (dump / "ivector.npy").exists():
-                iv = np.load(dump / "ivector.npy")
-                out[f"{mode}_ivector"] = iv[:1] if mode == "offline" else iv
-                out[f"{mode}_chunk_tick"] = np.load(dump / "chunk_tick.npy")[0].astype(np.int32)
-            if mode == "offline" and (dump / "lda_norm.npy").exists() and not case.get("big"):
-                out["cmvn"] = np.load(dump / "cmvn.npy")
-                out["lda"] = np.load(dump / "lda.npy")
-                out["lda_norm"] = np.load(dump / "lda_norm.npy")
+            if f"{mode}_loglikes" in out:
+                out[f"{mode}_loglikes"] = out[f"{mode}_loglikes"][::stride[0], ::stride[1]].copy()
+                out["loglikes_stride"] = np.array(stride, np.int32)
         # rand() calls of the reference's model set-up (decides the dither seeds): oracle/nnet3_rand.py and
         # rhasspy_speech_amd/csrc/nnet3_setup.cc are checked against this
         rp = run(["rs-dump", f"--config={conf}", "randpos", str(mdl), "-", "-"], env=env)
