@@ -887,20 +887,23 @@ class Oracle:
             out[0] = F32(np.float64(out[0]) - ie["ext"].prior_offset)
             ivs.append(out)
         ivs = np.stack(ivs)
-        # which chunk supplied the iVector "slot" of every padded row (nnet-compile-looped.cc:164-231)
         H = self.nnet.halo
-        ts = np.arange(-H, T + H)
+        idx = self.stream_ivector_rows(len(sched), np.arange(-H, T + H))
+        return nn_in, ivs, self.nnet.forward(nn_in, ivs[idx], self.acoustic_scale)
+
+    def stream_ivector_rows(self, n_chunks: int, ts: np.ndarray) -> np.ndarray:
+        """Which of n_chunks chunks supplied the iVector "slot" of the rows at times ts (nnet-compile-looped.cc:164-231)."""
+        L, R = self.nnet.context()
         slot = (ts // self.chunk) * self.chunk
         provider = {}
-        ends = [self.chunk * (k + 1) + R for k in range(len(sched))]
+        ends = [self.chunk * (k + 1) + R for k in range(n_chunks)]
         begin0 = -L
-        for k in range(len(sched)):
+        for k in range(n_chunks):
             lo = begin0 if k == 0 else ends[k - 1]
             for t in range(lo, ends[k]):
                 provider.setdefault((t // self.chunk) * self.chunk, k)
-        maxk = len(sched) - 1
-        idx = np.array([min(provider.get(int(sl), maxk if sl > 0 else 0), maxk) for sl in slot])
-        return nn_in, ivs, self.nnet.forward(nn_in, ivs[idx], self.acoustic_scale)
+        maxk = n_chunks - 1
+        return np.array([min(provider.get(int(sl), maxk if sl > 0 else 0), maxk) for sl in slot])
 
     def transcribe_stream(self, pcm: np.ndarray, nbest: int = 1, lattice_acoustic_scale: float = 1.0) -> Transcript:
         pcm = np.asarray(pcm)

@@ -1662,101 +1662,91 @@ void Model::CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const Batc
     timings[7] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_l0).count();
   }}
 
-// One group of utterances, start to finish, on one stream with one arena.  DecodeBatchDevice runs two groups
-// concurrently (two host threads, two streams) so that the latency-bound stages of one group (search, iVector)
-// overlap the MFMA-bound stage (TDNN) of the other.
-void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const int64_t *sample_offsets, int n_utts, int nbest, float lat_scale,
-                        hipStream_t s, bool streaming, UttResult *out_utts, float *timings) {
-  DeviceArena &arena_ = cx.arena[gi];
-  HostArena &harena = cx.host_arena[gi];
-  RS_HIP(hipSetDevice(opts_.device_id));
-  auto wall0 = std::chrono::steady_clock::now();
-  if (n_utts == 0) return;
-  SampleGemmMode(exact_gemm_.load() || cx.force_exact, cx.gemm_ovf_dev);
-  const Nnet &nn = am_.nnet;
-  const int C = fc_.mfcc.nceps, P = nn.output_dim;
-  // ---- geometry
-  std::vector<int> T(n_utts), row_base(n_utts + 1, 0), frame_base(n_utts + 1, 0);
-  int maxT = 0;
-  for (int u = 0; u < n_utts; u++) {
-    long ns = (long)(sample_offsets[u + 1] - sample_offsets[u]);
-    if (ns < 0) Fail("sample offsets must be non-decreasing");
-    T[u] = NumFrames(ns, fc_.mfcc.opts);
-    maxT = std::max(maxT, T[u]);
-    row_base[u + 1] = row_base[u] + T[u] + L_ + R_;
-    frame_base[u + 1] = frame_base[u] + T[u];
-  }
+// One utterance group of a batch call: its host geometry, and what each stage of DecodeGroup leaves for the next
+struct BatchCall {
+  DeviceArena *arena = nullptr;
+  HostArena *harena = nullptr;
+  hipStream_t s = nullptr;
+  int n_utts = 0, share = 1;
+  bool streaming = false;
+  // frames: per utterance T feature frames in rows [row_base + L, ..) of T + L + R, T_dec decoder frames
   // --frame-subsampling-factor f: the decoder's frames are the output rows t = 0, f, 2 f, ... (decodable-online-looped.cc:56-84:
   // (T + f - 1) / f of them once the input is finished); num_frames is what the reference's binaries log as decoded frames
-  const int fsf = opts_.frame_subsampling_factor;
-  std::vector<int> T_dec(n_utts), dec_base(n_utts + 1, 0);
-  int maxT_dec = 0;
-  for (int u = 0; u < n_utts; u++) {
-    T_dec[u] = (T[u] + fsf - 1) / fsf;
-    maxT_dec = std::max(maxT_dec, T_dec[u]);
-    dec_base[u + 1] = dec_base[u] + T_dec[u];
-    out_utts[u].num_frames = T_dec[u];
+  std::vector<long> ns;
+  std::vector<int> T, row_base, frame_base, T_dec, dec_base;
+  int maxT = 0, maxT_dec = 0, rows = 0, guard = 0;
+  // iVector rows: one per utterance offline, one per nnet chunk streamed (sched; row_ivec: page-locked, per nnet row)
+  BatchSchedule sched;
+  int *row_ivec = nullptr, n_ivrows = 0;
+  std::vector<int> buf_ld;
+  int n_slabs = 1, slab_len = 1;
+  RowListPlan lists;
+  // on the device
+  BatchGeom g;
+  RowMaps row_maps;
+  int *d_row_ivec = nullptr, *d_frame_rows = nullptr;
+  std::vector<float *> bufp;
+  std::vector<ActImage> imgs;
+  float *raw = nullptr, *d_ivec = nullptr;
+  int raw_ld = 0;
+  float *Rows(int ld) { return arena->AllocT<float>(((size_t)rows + 2 * guard) * ld) + (size_t)guard * ld; }
+};
+
+static void LdsPoison(hipStream_t s) {
+#ifdef RS_TUNING
+  static const int lds_poison = [] { const char *e = TuneEnv("RS_LDS_POISON"); return e ? std::atoi(e) : 0; }();
+  if (!lds_poison) return;
+  static unsigned *sink = [] { unsigned *p = nullptr; (void)hipMalloc((void **)&p, 64); return p; }();
+  LaunchLdsPoison(sink, s);      // (profiles/micro/poison_kernels.hip)
+#else
+  (void)s;
+#endif
+}
+
+// ---- geometry, and the iVector schedule.  Offline (--online=false): one estimate per utterance from all frames.  Streaming:
+// one estimate per nnet chunk, from the frames available at the 1024-sample tick on which
+// DecodableNnetLoopedOnlineBase::AdvanceChunk runs for that chunk (call_plan.h: ScheduleChunks).  The schedule only depends on
+// sample counts, so the streaming result is reproduced exactly without replaying wall-clock time.
+void Model::BatchFrames(const int64_t *sample_offsets, BatchCall *b) const {
+  const int n = b->n_utts, fsf = opts_.frame_subsampling_factor;
+  b->ns.resize(n); b->T.resize(n); b->T_dec.resize(n);
+  b->row_base.assign(n + 1, 0); b->frame_base.assign(n + 1, 0); b->dec_base.assign(n + 1, 0);
+  for (int u = 0; u < n; u++) {
+    b->ns[u] = (long)(sample_offsets[u + 1] - sample_offsets[u]);
+    if (b->ns[u] < 0) Fail("sample offsets must be non-decreasing");
+    b->T[u] = NumFrames(b->ns[u], fc_.mfcc.opts);
+    b->T_dec[u] = (b->T[u] + fsf - 1) / fsf;
+    b->maxT = std::max(b->maxT, b->T[u]);
+    b->maxT_dec = std::max(b->maxT_dec, b->T_dec[u]);
+    b->row_base[u + 1] = b->row_base[u] + b->T[u] + L_ + R_;
+    b->frame_base[u + 1] = b->frame_base[u] + b->T[u];
+    b->dec_base[u + 1] = b->dec_base[u] + b->T_dec[u];
   }
-  const int rows = row_base[n_utts];
-  const int guard = L_ + R_ + 8;
-  // ---- iVector schedule.  Offline (--online=false): one estimate per utterance from all frames.  Streaming:
-  // one estimate per nnet chunk, from the frames available at the 1024-sample tick on which
-  // DecodableNnetLoopedOnlineBase::AdvanceChunk runs for that chunk (decodable-online-looped.cc:56-84,186-194;
-  // online2-cli-nnet3-decode-faster.cc:143-161).  The schedule only depends on sample counts, so the streaming
-  // result is reproduced exactly without replaying wall-clock time.
+  b->rows = b->row_base[n];
+  b->guard = L_ + R_ + 8;
+  b->harena->Reset();
+  if (b->streaming && fc_.ie.present) {
+    b->row_ivec = b->harena->AllocT<int>(b->rows);
+    PlanBatchSchedule(PlanCfg(), b->ns.data(), b->T.data(), b->row_base.data(), n, b->row_ivec, &b->sched);
+  } else {
+    // (offline: every row of an utterance reads its single iVector row -- filled in on the device with the row geometry)
+    b->sched.ivrow_base.resize(n + 1);
+    for (int u = 0; u <= n; u++) b->sched.ivrow_base[u] = u;
+  }
+  b->n_ivrows = b->sched.ivrow_base[n];
+}
+
+// What the call takes from its arena (the search's share is planned here: *sp)
+size_t Model::BatchArenaBytes(BatchCall *b, int nbest, float lat_scale, SearchPlan *sp) const {
+  const Nnet &nn = am_.nnet;
   const bool has_iv = fc_.ie.present;
-  const int chunk = opts_.frames_per_chunk;
-  std::vector<int> ivrow_base(n_utts + 1, 0);               // first iVector row of each utterance
-  std::vector<std::vector<int>> chunk_last(n_utts);          // streaming: last stats frame of every chunk
-  int max_chunks = 1;
-  for (int u = 0; u < n_utts; u++) {
-    int nrows_u = 1;
-    if (streaming && has_iv) {
-      const long ns = (long)(sample_offsets[u + 1] - sample_offsets[u]);
-      const int nch = (T[u] + chunk - 1) / chunk;
-      const int Rm = nn.right_context, sr = fc_.ie.splice_right;
-      const long nt = (ns + 1023) / 1024;
-      int k = 0;
-      for (long j = 0; j < nt && k < nch; j++) {
-        const int fr = NumFrames(std::min<long>(1024 * (j + 1), ns), fc_.mfcc.opts);
-        const int ready = std::max(0, fr - Rm) / chunk;
-        while (k < ready && k < nch) { chunk_last[u].push_back(std::min(fr - 1, fr - sr - 1)); k++; }
-      }
-      while (k < nch) { chunk_last[u].push_back(T[u] - 1); k++; }
-      nrows_u = std::max(nch, 1);
-      max_chunks = std::max(max_chunks, nch);
-    }
-    ivrow_base[u + 1] = ivrow_base[u] + nrows_u;
-  }
-  const int n_ivrows = ivrow_base[n_utts];
-  // which iVector row every frame row reads: the chunk that supplied its Round(ivector, chunk) slot
-  // (nnet-compile-looped.cc:164-231: chunk 0 supplies the slots of t in [-L, chunk + R), chunk k the new ones of
-  //  [k*chunk + R, (k+1)*chunk + R))
-  // (offline: every row of an utterance reads its single iVector row -- filled in on the device with the row geometry)
-  harena.Reset();
-  const bool host_row_ivec = streaming && has_iv;
-  int *row_ivec = host_row_ivec ? harena.AllocT<int>(rows) : nullptr;
-  for (int u = 0; host_row_ivec && u < n_utts; u++) {
-    const int nch = (int)chunk_last[u].size();
-    for (int r = row_base[u]; r < row_base[u + 1]; r++) {
-      int k = 0;
-      if (streaming && has_iv && nch > 0) {
-        const int t = r - row_base[u] - L_;
-        const int slot = (t >= 0 ? t / chunk : -((-t + chunk - 1) / chunk)) * chunk;
-        // smallest k whose input range [.., (k+1)*chunk + R) contains a time with this slot: slot < (k+1)*chunk + R
-        k = 0;
-        while (k < nch - 1 && slot >= (k + 1) * chunk + nn.right_context) k++;
-      }
-      row_ivec[r] = ivrow_base[u] + k;
-    }
-  }
-  // ---- arena sizing
+  const int n_utts = b->n_utts, rows = b->rows, guard = b->guard, fsf = opts_.frame_subsampling_factor, C = fc_.mfcc.nceps, P = nn.output_dim;
   auto fbytes = [&](int ld) { return ((size_t)rows + 2 * guard) * ld * sizeof(float) + 512; };
   size_t need = 0;
   need += (sizeof(int64_t) + 4 * sizeof(int)) * (size_t)(n_utts + 2) + 3 * sizeof(int) * (size_t)rows + 4096;
-  need += sizeof(int) * ((size_t)frame_base[n_utts] + 8 * (size_t)n_utts + 64) + 1024;     // frame-row map
-  std::vector<int> buf_ld(nn.bufs.size());
-  for (size_t b = 0; b < nn.bufs.size(); b++) { buf_ld[b] = RoundUp(nn.bufs[b].dim, 4); need += fbytes(buf_ld[b]); }
+  need += sizeof(int) * ((size_t)b->frame_base[n_utts] + 8 * (size_t)n_utts + 64) + 1024;     // frame-row map
+  b->buf_ld.resize(nn.bufs.size());
+  for (size_t i = 0; i < nn.bufs.size(); i++) { b->buf_ld[i] = RoundUp(nn.bufs[i].dim, 4); need += fbytes(b->buf_ld[i]); }
   need += ImageBytes(rows);
   need += (size_t)nn.ops.size() * (sizeof(int) * ((size_t)rows + n_utts + 64) + 512);      // row lists per output extent
   const int Dl = has_iv ? fc_.ie.feat_dim() : 0, Di = has_iv ? fc_.ie.ivector_dim() : 0, G = has_iv ? fc_.ie.num_gauss() : 0;
@@ -1766,35 +1756,221 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   if (has_iv) {
     need += fbytes(ld_c) + 2 * fbytes(ld_l);
     need += (size_t)rows * nsel * 8 + 1024;
-    need += (size_t)n_utts * ((size_t)G * 8 + (size_t)G * Dl * 8 + (size_t)Di * 8 * 2 + (size_t)usz * 8 + 8) + (size_t)n_ivrows * ld_i * 4 + 8192 + 1024;
-    need += (size_t)max_chunks * n_utts * 16 + 4096;
+    need += (size_t)n_utts * ((size_t)G * 8 + (size_t)G * Dl * 8 + (size_t)Di * 8 * 2 + (size_t)usz * 8 + 8) + (size_t)b->n_ivrows * ld_i * 4 + 8192 + 1024;
+    need += (size_t)b->sched.max_chunks * n_utts * 16 + 4096;
     need += IvecStatsScratchDoubles(ivec_dev_, n_utts) * 8 + 1024;
-    if (streaming) need += IvecChunkChainBytes(ivec_dev_, n_utts, max_chunks);
+    if (b->streaming) need += IvecChunkChainBytes(ivec_dev_, n_utts, b->sched.max_chunks);
   }
+  need += PlanSearch(n_utts, b->maxT_dec, nbest, lat_scale, sp);
+  if (fsf > 1) need += ((size_t)b->dec_base[n_utts] + 8) * RoundUp(P, 4) * sizeof(float) + (size_t)(b->dec_base[n_utts] + 3 * n_utts + 16) * sizeof(int) + 4096;
+  return need + 64 * 256;   // alignment slack
+}
+
+// ---- geometry on the device: ONE page-locked staging block -> one async copy, ONE launch that derives every per-row array on the
+// device (the rows' utterance / frame / iVector row and the row lists of the layers that are evaluated on fewer rows than the full
+// halo: call_plan.h, PlanRowLists).  Round 4 issued a copy + a launch per list: 8 + 8 of the ~25 launch boundaries in front of a
+// call's first real kernel.
+void Model::BatchSetupUpload(const int64_t *sample_offsets, BatchCall *b) {
+  const Nnet &nn = am_.nnet;
+  const int n_utts = b->n_utts, rows = b->rows;
+  hipStream_t s = b->s;
+  static const int trim_env = [] { const char *e = TuneEnv("RS_TRIM_HALO"); return e ? std::atoi(e) : 1; }();
+  std::vector<BufExtent> op_out;
+  for (auto &op : nn.ops) op_out.push_back({nn.bufs[op.out_buf].lext, nn.bufs[op.out_buf].rext, nn.bufs[op.out_buf].stride});
+  switch (PlanRowLists(b->T.data(), b->row_base.data(), n_utts, b->maxT, L_, R_, op_out, b->n_slabs, b->slab_len, BatchSetup::kMaxLists, trim_env != 0, &b->lists)) {
+    case RowListStatus::kOk: break;
+    case RowListStatus::kStridedInSlabs: Fail("internal error: strided layers in a slab-pipelined call");
+    case RowListStatus::kTooManyStrided:
+      Fail("nnet3: more distinct (context, stride) row lists than a call carries (" + std::to_string(BatchSetup::kMaxLists) + ") with --frame-subsampling-factor");
+  }
+  const std::vector<int> &segs = b->lists.segs;
+  const size_t n1 = (size_t)n_utts + 1;
+  const size_t geo_bytes = n1 * sizeof(int64_t) + 4 * n1 * sizeof(int), bytes = geo_bytes + segs.size() * sizeof(int);
+  char *hp = static_cast<char *>(b->harena->Alloc(bytes));
+  char *dp = static_cast<char *>(b->arena->Alloc(bytes));
+  int64_t *h_so = reinterpret_cast<int64_t *>(hp);
+  int *h_T = reinterpret_cast<int *>(hp + n1 * sizeof(int64_t)), *h_rb = h_T + n1, *h_fb = h_rb + n1, *h_ib = h_fb + n1;
+  std::memcpy(h_so, sample_offsets, n1 * sizeof(int64_t));
+  std::memcpy(h_T, b->T.data(), sizeof(int) * n_utts);
+  h_T[n_utts] = 0;
+  std::memcpy(h_rb, b->row_base.data(), sizeof(int) * n1);
+  std::memcpy(h_fb, b->frame_base.data(), sizeof(int) * n1);
+  std::memcpy(h_ib, b->sched.ivrow_base.data(), sizeof(int) * n1);
+  if (!segs.empty()) std::memcpy(hp + geo_bytes, segs.data(), segs.size() * sizeof(int));
+  RS_HIP(hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, s));
+  int64_t *d_so = reinterpret_cast<int64_t *>(dp);
+  int *d_T = reinterpret_cast<int *>(dp + n1 * sizeof(int64_t)), *d_rb = d_T + n1, *d_fb = d_rb + n1, *d_ib = d_fb + n1;
+  const int *d_segs = reinterpret_cast<const int *>(dp + geo_bytes);
+  int *d_ru = b->arena->AllocT<int>(rows), *d_rt = b->arena->AllocT<int>(rows);
+  b->d_row_ivec = b->arena->AllocT<int>(rows);
+  if (b->row_ivec) RS_HIP(hipMemcpyAsync(b->d_row_ivec, b->row_ivec, sizeof(int) * rows, hipMemcpyHostToDevice, s));
+  BatchSetup bs;
+  std::memset(&bs, 0, sizeof(bs));
+  bs.n_utts = n_utts; bs.rows = rows; bs.L = L_; bs.row_base = d_rb; bs.ivrow_base = d_ib; bs.row_utt = d_ru; bs.row_t = d_rt;
+  bs.row_ivec = b->row_ivec ? nullptr : b->d_row_ivec;
+  for (auto &l : b->lists.lists) {
+    int *out = b->arena->AllocT<int>(l.total);
+    bs.lists[bs.n_lists++] = {l.n_segs, l.total, l.L_eff, l.slab_len, d_segs + l.seg_at, out, l.stride, l.first};
+    b->row_maps.maps.push_back({l.lext, l.rext, out, l.total, l.span128, l.stride, l.span160});
+    if (l.lext == 0 && l.rext == 0 && l.stride == 1) b->d_frame_rows = out;
+  }
+  LaunchBatchSetup(bs, s);
+  BatchGeom &g = b->g;
+  g.n_utts = n_utts; g.L = L_; g.R = R_; g.total_rows = rows; g.total_frames = b->frame_base[n_utts]; g.max_frames = b->maxT; g.guard = b->guard;
+  g.d_sample_off = d_so; g.d_num_frames = d_T; g.d_row_base = d_rb; g.d_frame_base = d_fb; g.d_row_utt = d_ru; g.d_row_t = d_rt;
+}
+
+// ---- features: the network's buffers out of the arena, MFCC (and the nnet input's CMVN) into the input buffer
+void Model::BatchFeatures(const int16_t *d_pcm, BatchCall *b) {
+  const Nnet &nn = am_.nnet;
+  hipStream_t s = b->s;
+  const int ld_c = RoundUp(fc_.mfcc.nceps, 4), in_ld = b->buf_ld[nn.input_buf];
+  b->bufp.assign(nn.bufs.size(), nullptr);
+  for (size_t i = 0; i < nn.bufs.size(); i++) b->bufp[i] = b->Rows(b->buf_ld[i]);
+  b->imgs = AllocImages(*b->arena, b->rows);
+  b->raw = b->bufp[nn.input_buf];
+  if (fc_.use_cmvn) {
+    b->raw = b->Rows(ld_c);
+    LdsPoison(s);
+    LaunchMfcc(MfccWithDither(b->maxT), b->g, d_pcm, b->raw, ld_c, s, OthersInFlight());
+    LdsPoison(s);
+    LaunchOnlineCmvn(cmvn_nnet_dev_, b->g, b->raw, b->bufp[nn.input_buf], in_ld, s);
+  } else {
+    LdsPoison(s);
+    LaunchMfcc(MfccWithDither(b->maxT), b->g, d_pcm, b->raw, in_ld, s, OthersInFlight());
+  }
+  b->raw_ld = fc_.use_cmvn ? ld_c : in_ld;
+}
+
+// ---- iVectors: CMVN, splice + LDA, UBM posteriors, then one estimate per utterance (offline) or per chunk (streamed)
+void Model::BatchIvectors(BatchCall *b) {
+  const int C = fc_.mfcc.nceps, n_utts = b->n_utts, rows = b->rows, n_ivrows = b->n_ivrows, share = b->share;
+  const int Dl = fc_.ie.feat_dim(), Di = fc_.ie.ivector_dim(), G = fc_.ie.num_gauss(), nsel = fc_.ie.num_gselect, usz = Di * (Di + 1) / 2;
+  const int ld_c = RoundUp(C, 4), ld_l = RoundUp(std::max(Dl, 1), 4), ld_i = RoundUp(std::max(Di, 1), 4);
+  DeviceArena &arena_ = *b->arena;
+  hipStream_t s = b->s;
+  const BatchGeom &g = b->g;
+  float *cm = b->Rows(ld_c), *lda_raw = b->Rows(ld_l), *lda_norm = b->Rows(ld_l);
+  LdsPoison(s);
+  LaunchOnlineCmvn(cmvn_iv_dev_, g, b->raw, cm, ld_c, s);
+  LdsPoison(s);
+  LaunchGemm(MakeGemm(LdaPlan(b->raw_ld), {b->raw}, {b->raw_ld}, nullptr, 0, lda_raw, ld_l, share), rows, b->d_row_ivec, s);
+  LdsPoison(s);
+  LaunchGemm(MakeGemm(LdaPlan(ld_c), {cm}, {ld_c}, nullptr, 0, lda_norm, ld_l, share), rows, b->d_row_ivec, s);
+  int *post_idx = arena_.AllocT<int>((size_t)rows * nsel);
+  float *post_w = arena_.AllocT<float>((size_t)rows * nsel);
+  LdsPoison(s);
+  LaunchUbmPosteriors(ivec_dev_, g, lda_norm, ld_l, post_idx, post_w, s);
+  double *gamma = arena_.AllocT<double>((size_t)n_utts * G), *wfeats = arena_.AllocT<double>((size_t)n_utts * G * Dl);
+  double *linear = arena_.AllocT<double>((size_t)n_utts * Di), *quad = arena_.AllocT<double>((size_t)n_utts * usz);
+  double *numf = arena_.AllocT<double>(n_utts), *x = arena_.AllocT<double>((size_t)n_utts * Di);
+  float *d_ivec = b->d_ivec = arena_.AllocT<float>((size_t)n_ivrows * ld_i + 256);   // + slack: staging loads may read past a row's end
+  if (b->streaming) {          // (whole utterances: the accumulate kernel starts the sums itself)
+    RS_HIP(hipMemsetAsync(gamma, 0, sizeof(double) * (size_t)n_utts * G, s));
+    RS_HIP(hipMemsetAsync(wfeats, 0, sizeof(double) * (size_t)n_utts * G * Dl, s));
+  }
+  RS_HIP(hipMemsetAsync(d_ivec, 0, sizeof(float) * (size_t)n_ivrows * ld_i, s));
+  LaunchIvecInit(ivec_dev_, n_utts, linear, quad, x, numf, s);
+  double *iv_scratch = arena_.AllocT<double>(IvecStatsScratchDoubles(ivec_dev_, n_utts));
+  const float *stats_feats = fc_.ie.online_cmvn_iextractor ? lda_norm : lda_raw;
+  if (!b->streaming) {
+    LdsPoison(s);
+    LaunchIvecAccumulate(ivec_dev_, g, stats_feats, ld_l, post_idx, post_w, nullptr, nullptr, gamma, wfeats, true, s);
+    LdsPoison(s);
+    LaunchIvecStats(ivec_dev_, n_utts, gamma, wfeats, linear, quad, numf, iv_scratch, s);
+    LaunchIvecSolve(ivec_dev_, n_utts, linear, quad, numf, x, d_ivec, ld_i, nullptr, nullptr, s);
+    return;
+  }
+  // per-chunk schedule tables: [step][utt] frame_begin, frame_end, out_row, active
+  const StepTables &st = b->sched.steps;
+  const int max_chunks = b->sched.max_chunks;
+  const size_t nt = st.fb.size();
+  int *d_fb = arena_.AllocT<int>(nt), *d_fe = arena_.AllocT<int>(nt), *d_or = arena_.AllocT<int>(nt), *d_ac = arena_.AllocT<int>(nt);
+  RS_HIP(hipMemcpyAsync(d_fb, st.fb.data(), sizeof(int) * nt, hipMemcpyHostToDevice, s));
+  RS_HIP(hipMemcpyAsync(d_fe, st.fe.data(), sizeof(int) * nt, hipMemcpyHostToDevice, s));
+  RS_HIP(hipMemcpyAsync(d_or, st.orow.data(), sizeof(int) * nt, hipMemcpyHostToDevice, s));
+  RS_HIP(hipMemcpyAsync(d_ac, st.act.data(), sizeof(int) * nt, hipMemcpyHostToDevice, s));
+  RS_HIP(hipStreamSynchronize(s));
+  if (Di <= 128) {
+    IvecChunkChain(arena_, g, n_utts, max_chunks, stats_feats, ld_l, post_idx, post_w, d_fb, d_fe, d_or, d_ac, linear, quad, numf, x, nullptr, d_ivec, ld_i, s);
+  } else {
+    for (int k = 0; k < max_chunks; k++) {
+      const size_t o = (size_t)k * n_utts;
+      LaunchIvecAccumulate(ivec_dev_, g, stats_feats, ld_l, post_idx, post_w, d_fb + o, d_fe + o, gamma, wfeats, false, s);
+      LaunchIvecStats(ivec_dev_, n_utts, gamma, wfeats, linear, quad, numf, iv_scratch, s);
+      LaunchIvecSolve(ivec_dev_, n_utts, linear, quad, numf, x, d_ivec, ld_i, d_or + o, d_ac + o, s);
+      LaunchIvecClear(ivec_dev_, n_utts, gamma, wfeats, s);
+    }
+  }
+}
+
+// --frame-subsampling-factor: the rows the decoder reads, gathered into a dense [decoder frame][pdf] array with its own geometry (no halo)
+void Model::BatchDecoderRows(BatchCall *b, float **ll, int *ll_ld, BatchGeom *gdec) {
+  const int n_utts = b->n_utts, fsf = opts_.frame_subsampling_factor, P = am_.nnet.output_dim, nd = b->dec_base[n_utts];
+  int *h_idx = b->harena->AllocT<int>((size_t)nd + 2 * (size_t)n_utts + 2);
+  int *h_T = h_idx + nd, *h_base = h_T + n_utts;
+  for (int u = 0; u < n_utts; u++) {
+    for (int f = 0; f < b->T_dec[u]; f++) h_idx[b->dec_base[u] + f] = b->row_base[u] + L_ + f * fsf;
+    h_T[u] = b->T_dec[u];
+    h_base[u] = b->dec_base[u];
+  }
+  h_base[n_utts] = nd;
+  int *d_idx = b->arena->AllocT<int>((size_t)nd + 2 * (size_t)n_utts + 2);
+  RS_HIP(hipMemcpyAsync(d_idx, h_idx, sizeof(int) * ((size_t)nd + 2 * (size_t)n_utts + 2), hipMemcpyHostToDevice, b->s));
+  const int ld_dec = RoundUp(P, 4);
+  float *ll_dec = b->arena->AllocT<float>(((size_t)nd + 8) * ld_dec);
+  if (nd > 0) LaunchCopyRows(*ll, *ll_ld, d_idx, ll_dec, ld_dec, nullptr, nd, P, b->s);
+  *ll = ll_dec; *ll_ld = ld_dec;
+  gdec->L = 0; gdec->R = 0; gdec->total_rows = nd; gdec->total_frames = nd; gdec->max_frames = b->maxT_dec;
+  gdec->d_num_frames = d_idx + nd; gdec->d_row_base = d_idx + nd + n_utts; gdec->d_frame_base = d_idx + nd + n_utts;
+  gdec->d_row_utt = nullptr; gdec->d_row_t = nullptr; gdec->d_sample_off = nullptr;
+}
+
+// keep_intermediates: features, iVectors and log-likelihoods of every utterance to the host
+void Model::BatchIntermediates(const BatchCall &b, const float *ll, int ll_ld, UttResult *out_utts) const {
+  const Nnet &nn = am_.nnet;
+  const bool has_iv = fc_.ie.present;
+  const int C = fc_.mfcc.nceps, P = nn.output_dim, fsf = opts_.frame_subsampling_factor, Di = has_iv ? fc_.ie.ivector_dim() : 0, ld_i = RoundUp(std::max(Di, 1), 4);
+  const int in_ld = b.buf_ld[nn.input_buf];
+  const std::vector<int> &ivrow_base = b.sched.ivrow_base;
+  for (int u = 0; u < b.n_utts; u++) {
+    UttResult &ur = out_utts[u];
+    const int T = b.T[u], T_dec = b.T_dec[u];
+    ur.feat_dim = C; ur.num_pdfs = P; ur.ivec_dim = Di; ur.ivec_rows = has_iv ? ivrow_base[u + 1] - ivrow_base[u] : 0;
+    if (T == 0) continue;
+    ur.feats.resize((size_t)T * C);
+    ur.loglikes.resize((size_t)T_dec * P);
+    const float *fin = b.bufp[nn.input_buf] + ((size_t)b.row_base[u] + L_) * in_ld;
+    RS_HIP(hipMemcpy2D(ur.feats.data(), sizeof(float) * C, fin, sizeof(float) * in_ld, sizeof(float) * C, T, hipMemcpyDeviceToHost));
+    const float *lin = ll + (fsf > 1 ? (size_t)b.dec_base[u] : (size_t)b.row_base[u] + L_) * ll_ld;
+    RS_HIP(hipMemcpy2D(ur.loglikes.data(), sizeof(float) * P, lin, sizeof(float) * ll_ld, sizeof(float) * P, T_dec, hipMemcpyDeviceToHost));
+    if (has_iv) {
+      ur.ivector.resize((size_t)ur.ivec_rows * Di);
+      RS_HIP(hipMemcpy2D(ur.ivector.data(), sizeof(float) * Di, b.d_ivec + (size_t)ivrow_base[u] * ld_i, sizeof(float) * ld_i,
+                         sizeof(float) * Di, ur.ivec_rows, hipMemcpyDeviceToHost));
+    }
+  }
+}
+
+// One group of utterances, start to finish, on one stream with one arena.  DecodeBatchDevice runs two groups
+// concurrently (two host threads, two streams) so that the latency-bound stages of one group (search, iVector)
+// overlap the MFMA-bound stage (TDNN) of the other.
+void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const int64_t *sample_offsets, int n_utts, int nbest, float lat_scale,
+                        hipStream_t s, bool streaming, UttResult *out_utts, float *timings) {
+  RS_HIP(hipSetDevice(opts_.device_id));
+  auto wall0 = std::chrono::steady_clock::now();
+  if (n_utts == 0) return;
+  SampleGemmMode(exact_gemm_.load() || cx.force_exact, cx.gemm_ovf_dev);
+  const Nnet &nn = am_.nnet;
+  const int fsf = opts_.frame_subsampling_factor;
+  BatchCall b;
+  b.arena = &cx.arena[gi]; b.harena = &cx.host_arena[gi]; b.s = s; b.n_utts = n_utts; b.share = cx.active_groups; b.streaming = streaming;
+  BatchFrames(sample_offsets, &b);
+  for (int u = 0; u < n_utts; u++) out_utts[u].num_frames = b.T_dec[u];
   SearchPlan sp;
-  need += PlanSearch(n_utts, maxT_dec, nbest, lat_scale, &sp);
-  if (fsf > 1) need += ((size_t)dec_base[n_utts] + 8) * RoundUp(P, 4) * sizeof(float) + (size_t)(dec_base[n_utts] + 3 * n_utts + 16) * sizeof(int) + 4096;
-  const bool use_reg = sp.use_reg;
-  need += 64 * 256;   // alignment slack
-  arena_.Reserve(need + (1u << 20), s);
-  arena_.Reset();
-  // ---- geometry: ONE page-locked staging block -> one async copy, ONE launch that derives every per-row array on the device (the
-  // rows' utterance / frame / iVector row and the row lists of the layers that are evaluated on fewer rows than the full halo).
-  // Round 4 issued a copy + a launch per list: 8 + 8 of the ~25 launch boundaries in front of a call's first real kernel.
-  int *d_row_ivec = nullptr;
-  BatchGeom g;
-  g.n_utts = n_utts; g.L = L_; g.R = R_; g.total_rows = rows; g.total_frames = frame_base[n_utts]; g.max_frames = maxT; g.guard = guard;
-  const int total_frames = frame_base[n_utts];
-#ifdef RS_TUNING
-  static const int lds_poison = [] { const char *e = TuneEnv("RS_LDS_POISON"); return e ? std::atoi(e) : 0; }();
-  auto poison = [&]() {
-    if (!lds_poison) return;
-    static unsigned *sink = [] { unsigned *p = nullptr; (void)hipMalloc((void **)&p, 64); return p; }();
-    LaunchLdsPoison(sink, s);      // (profiles/micro/poison_kernels.hip)
-  };
-#else
-  auto poison = []() {};
-#endif
+  const size_t need = BatchArenaBytes(&b, nbest, lat_scale, &sp);
+  b.arena->Reserve(need + (1u << 20), s);
+  b.arena->Reset();
   // The last layer and the search can be pipelined over time slabs when the search is the register-resident kernel: the
   // output GEMM of slab k+1 (MFMA-bound) runs while slab k is searched (latency-bound) on a second, high-priority stream.
   // Measured on the bench batch: 5.07 -> 4.97 ms with 3 slabs -- the search runs at half speed while it shares the CUs
@@ -1802,136 +1978,10 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   const int overlap_env = [] { const char *e = std::getenv("RS_OVERLAP_SLABS"); return e ? std::atoi(e) : 1; }();
   const bool last_is_gemm = !nn.ops.empty() && nn.ops.back().kind == LayerOp::kGemm && nn.ops.back().out_buf == nn.output_buf &&
                             nn.bufs[nn.output_buf].lext == 0 && nn.bufs[nn.output_buf].rext == 0;
-  const bool pipelined = use_reg && !sp.reg_lattice && last_is_gemm && !d_log_priors_ && opts_.acoustic_scale == 1.0f && overlap_env > 1 && maxT >= 64 &&
+  const bool pipelined = sp.use_reg && !sp.reg_lattice && last_is_gemm && !d_log_priors_ && opts_.acoustic_scale == 1.0f && overlap_env > 1 && b.maxT >= 64 &&
                          s == cx.stream && fsf == 1;
-  const int n_slabs = pipelined ? std::min(overlap_env, 8) : 1, slab_len = std::max(1, (maxT + n_slabs - 1) / n_slabs);
-  std::vector<int> slab_off(n_slabs + 1, 0);
-  int *d_frame_rows = nullptr;
-  RowMaps row_maps;
-  {
-    // which row lists this batch needs: the real frames in slab-major order (slab k = frames [k * slab_len, (k + 1) * slab_len) of
-    // every utterance: layers nothing downstream reads with a time offset are evaluated on these rows only), and per hidden layer
-    // only as much halo as the layers after it reach (15 rows a side for the first, none for the last of the zamia-like net:
-    // 5 % fewer rows over the stack than evaluating the full halo everywhere)
-    struct ListPlan { int lext, rext, n_segs, total, L_eff, slab_len, span128; size_t seg_at; int stride = 1, first = 0, span160 = 0; };
-    std::vector<ListPlan> lists;
-    std::vector<int> segs;      // the lists' segment offsets, back to back
-    // The physical rows 128 consecutive entries of a stride-1 list reach over, exactly: the list is one run of consecutive rows per
-    // utterance with frames (t in [-lext, T + rext): T + lext + rext entries from row row_base + L - lext on); a window of 128 entries
-    // that holds the last entry of run a and the first of run b crosses every gap between them, and it can do so when the runs in
-    // between hold at most 126 entries.  An utterance without frames has no entries but still owns L + R rows (a too-short clip
-    // inside a batch), so the gap between two runs is not bounded by one halo: GemmKernelB3J's strip form trusts this number.
-    auto span_of_runs = [&](int lext, int rext, int window = 128) {
-      std::vector<std::pair<int, int>> runs;      // (first physical row, entries)
-      for (int u = 0; u < n_utts; u++) if (T[u] > 0) runs.emplace_back(row_base[u] + L_ - lext, T[u] + lext + rext);
-      int worst = 0;
-      size_t b = 0;
-      long inner = 0;                             // entries of the runs strictly between a and b
-      for (size_t a = 0; a + 1 < runs.size(); a++) {
-        if (b <= a) { b = a + 1; inner = 0; }
-        while (b + 1 < runs.size() && inner + runs[b].second <= window - 2) { inner += runs[b].second; b++; }
-        const long gaps = (long)runs[b].first - (runs[a].first + runs[a].second) - inner;
-        worst = std::max<long>(worst, gaps);
-        if (b > a + 1) inner -= runs[a + 1].second;
-      }
-      return window + worst;
-    };
-    if (total_frames > 0) {
-      ListPlan lp{0, 0, n_slabs * n_utts, total_frames, L_, slab_len, 0, segs.size()};
-      int acc_rows = 0;
-      for (int k = 0; k < n_slabs; k++) {
-        slab_off[k] = acc_rows;
-        for (int u = 0; u < n_utts; u++) { segs.push_back(acc_rows); acc_rows += std::min(std::max(T[u] - k * slab_len, 0), slab_len); }
-      }
-      segs.push_back(acc_rows);
-      slab_off[n_slabs] = acc_rows;
-      // (one slab: the list runs through the utterances in order, so a GEMM tile of 128 rows reaches over its rows + the halos it skips)
-      lp.span128 = n_slabs == 1 ? span_of_runs(0, 0) : 0;
-      lp.span160 = n_slabs == 1 ? span_of_runs(0, 0, 160) : 0;
-      lists.push_back(lp);
-      static const int trim_env = [] { const char *e = TuneEnv("RS_TRIM_HALO"); return e ? std::atoi(e) : 1; }();
-      // Trimmed halos are all or nothing: an op evaluated through its list leaves the other rows of its buffer as the arena held them, so
-      // everything that reads the buffer must go through a list as narrow or narrower.  Count the distinct lists first; a network with
-      // more of them than a call carries evaluates every layer on all rows (of the full halo: always valid) instead.
-      int trim = trim_env;
-      {
-        std::vector<std::array<int, 3>> distinct;
-        for (auto &op : nn.ops) {
-          const BufferInfo &ob = nn.bufs[op.out_buf];
-          if (ob.stride == 1 && ((ob.lext == 0 && ob.rext == 0) || (ob.lext >= L_ && ob.rext >= R_) || !trim_env)) continue;
-          const std::array<int, 3> key{ob.lext, ob.rext, ob.stride};
-          if (std::find(distinct.begin(), distinct.end(), key) == distinct.end()) distinct.push_back(key);
-        }
-        if ((int)distinct.size() + 1 > BatchSetup::kMaxLists) trim = 0;
-      }
-      // (two passes: the lists of the strided buffers first -- a buffer evaluated on every f-th row MUST have its list, its consumers
-      // read nothing else and its own sources may hold nothing else -- then, while there is room, the trimmed halos, which only save work)
-      for (size_t pi = 0; pi < 2 * nn.ops.size(); pi++) {
-        const size_t i = pi % nn.ops.size();
-        const bool strided_pass = pi < nn.ops.size();
-        const BufferInfo &ob = nn.bufs[nn.ops[i].out_buf];
-        const int st = ob.stride;
-        if ((st > 1) != strided_pass || (st == 1 && !trim)) continue;
-        if (ob.lext > L_ || ob.rext > R_) continue;
-        if (st == 1 && ((ob.lext == 0 && ob.rext == 0) || (ob.lext >= L_ && ob.rext >= R_))) continue;
-        if (st > 1 && n_slabs != 1) Fail("internal error: strided layers in a slab-pipelined call");
-        bool have = false;
-        for (auto &l : lists) have = have || (l.lext == ob.lext && l.rext == ob.rext && l.stride == st);
-        if (have) continue;
-        if ((int)lists.size() >= BatchSetup::kMaxLists) {
-          if (st > 1) Fail("nnet3: more distinct (context, stride) row lists than a call carries (" + std::to_string(BatchSetup::kMaxLists) + ") with --frame-subsampling-factor");
-          continue;
-        }
-        ListPlan l2{ob.lext, ob.rext, n_utts, 0, L_ - ob.lext, std::max(maxT + ob.lext + ob.rext, 1), 0, segs.size()};
-        l2.stride = st;
-        l2.first = ob.lext % st;             // t = -lext + first is the first row with t = 0 mod stride
-        int acc = 0;
-        // (rows t = 0 mod stride of [-lext, T + rext): (T + rext - 1) / stride + lext / stride + 1 of them)
-        for (int u = 0; u < n_utts; u++) { segs.push_back(acc); acc += T[u] > 0 ? (st == 1 ? T[u] + ob.lext + ob.rext : (T[u] + ob.rext - 1) / st + ob.lext / st + 1) : 0; }
-        segs.push_back(acc);
-        if (acc == 0) { segs.resize(l2.seg_at); continue; }
-        l2.total = acc;
-        // 128 consecutive rows of the list cross at most (126 / shortest run) + 1 utterance boundaries, each skipping the halo rows
-        // nobody reads: the physical rows a GEMM tile reaches over (a strided list: not bounded here, the strip form is not used)
-        l2.span128 = st == 1 ? span_of_runs(ob.lext, ob.rext) : 0;
-        l2.span160 = st == 1 ? span_of_runs(ob.lext, ob.rext, 160) : 0;
-        lists.push_back(l2);
-      }
-    }
-    const size_t n1 = (size_t)n_utts + 1;
-    const size_t geo_bytes = n1 * sizeof(int64_t) + 4 * n1 * sizeof(int), bytes = geo_bytes + segs.size() * sizeof(int);
-    char *hp = static_cast<char *>(harena.Alloc(bytes));
-    char *dp = static_cast<char *>(arena_.Alloc(bytes));
-    int64_t *h_so = reinterpret_cast<int64_t *>(hp);
-    int *h_T = reinterpret_cast<int *>(hp + n1 * sizeof(int64_t)), *h_rb = h_T + n1, *h_fb = h_rb + n1, *h_ib = h_fb + n1;
-    std::memcpy(h_so, sample_offsets, n1 * sizeof(int64_t));
-    std::memcpy(h_T, T.data(), sizeof(int) * n_utts);
-    h_T[n_utts] = 0;
-    std::memcpy(h_rb, row_base.data(), sizeof(int) * n1);
-    std::memcpy(h_fb, frame_base.data(), sizeof(int) * n1);
-    std::memcpy(h_ib, ivrow_base.data(), sizeof(int) * n1);
-    if (!segs.empty()) std::memcpy(hp + geo_bytes, segs.data(), segs.size() * sizeof(int));
-    RS_HIP(hipMemcpyAsync(dp, hp, bytes, hipMemcpyHostToDevice, s));
-    int64_t *d_so = reinterpret_cast<int64_t *>(dp);
-    int *d_T = reinterpret_cast<int *>(dp + n1 * sizeof(int64_t)), *d_rb = d_T + n1, *d_fb = d_rb + n1, *d_ib = d_fb + n1;
-    const int *d_segs = reinterpret_cast<const int *>(dp + geo_bytes);
-    int *d_ru = arena_.AllocT<int>(rows), *d_rt = arena_.AllocT<int>(rows);
-    d_row_ivec = arena_.AllocT<int>(rows);
-    if (host_row_ivec) RS_HIP(hipMemcpyAsync(d_row_ivec, row_ivec, sizeof(int) * rows, hipMemcpyHostToDevice, s));
-    BatchSetup bs;
-    std::memset(&bs, 0, sizeof(bs));
-    bs.n_utts = n_utts; bs.rows = rows; bs.L = L_; bs.row_base = d_rb; bs.ivrow_base = d_ib; bs.row_utt = d_ru; bs.row_t = d_rt;
-    bs.row_ivec = host_row_ivec ? nullptr : d_row_ivec;
-    for (auto &l : lists) {
-      int *out = arena_.AllocT<int>(l.total);
-      bs.lists[bs.n_lists++] = {l.n_segs, l.total, l.L_eff, l.slab_len, d_segs + l.seg_at, out, l.stride, l.first};
-      row_maps.maps.push_back({l.lext, l.rext, out, l.total, l.span128, l.stride, l.span160});
-      if (l.lext == 0 && l.rext == 0 && l.stride == 1) d_frame_rows = out;
-    }
-    LaunchBatchSetup(bs, s);
-    g.d_sample_off = d_so; g.d_num_frames = d_T; g.d_row_base = d_rb; g.d_frame_base = d_fb; g.d_row_utt = d_ru; g.d_row_t = d_rt;
-  }
-  auto falloc = [&](int ld) { return arena_.AllocT<float>(((size_t)rows + 2 * guard) * ld) + (size_t)guard * ld; };
+  const int n_slabs = b.n_slabs = pipelined ? std::min(overlap_env, 8) : 1, slab_len = b.slab_len = std::max(1, (b.maxT + n_slabs - 1) / n_slabs);
+  BatchSetupUpload(sample_offsets, &b);
   static const int chain = [] { const char *e = TuneEnv("RS_STAGE_CHAIN"); return e ? std::atoi(e) : 1; }();
   // (one chain per model: a single chain for all models of the process was no better on the two-model batch -- 10.75-10.96 ms
   // against 10.56-10.70 -- and its tail event would have to outlive the model that recorded it)
@@ -1953,165 +2003,48 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
     stage_lock.unlock();
   };
   stage_begin(0);
-  // ---- features
-  std::vector<float *> bufp(nn.bufs.size(), nullptr);
-  for (size_t b = 0; b < nn.bufs.size(); b++) bufp[b] = falloc(buf_ld[b]);
-  const std::vector<ActImage> imgs = AllocImages(arena_, rows);
-  float *raw = bufp[nn.input_buf];
-  if (fc_.use_cmvn) {
-    raw = falloc(ld_c);
-    poison();
-    LaunchMfcc(MfccWithDither(maxT), g, d_pcm, raw, ld_c, s, OthersInFlight());
-    poison();
-    LaunchOnlineCmvn(cmvn_nnet_dev_, g, raw, bufp[nn.input_buf], buf_ld[nn.input_buf], s);
-  } else {
-    poison();
-    LaunchMfcc(MfccWithDither(maxT), g, d_pcm, raw, buf_ld[nn.input_buf], s, OthersInFlight());
-  }
-  const int raw_ld = fc_.use_cmvn ? ld_c : buf_ld[nn.input_buf];
+  BatchFeatures(d_pcm, &b);
   tm.Mark();
-  // ---- iVector
-  float *d_ivec = nullptr;
-  if (has_iv) {
-    float *cm = falloc(ld_c), *lda_raw = falloc(ld_l), *lda_norm = falloc(ld_l);
-    poison();
-    LaunchOnlineCmvn(cmvn_iv_dev_, g, raw, cm, ld_c, s);
-    poison();
-    LaunchGemm(MakeGemm(LdaPlan(raw_ld), {raw}, {raw_ld}, nullptr, 0, lda_raw, ld_l, cx.active_groups), rows, d_row_ivec, s);
-    poison();
-    LaunchGemm(MakeGemm(LdaPlan(ld_c), {cm}, {ld_c}, nullptr, 0, lda_norm, ld_l, cx.active_groups), rows, d_row_ivec, s);
-    int *post_idx = arena_.AllocT<int>((size_t)rows * nsel);
-    float *post_w = arena_.AllocT<float>((size_t)rows * nsel);
-    poison();
-    LaunchUbmPosteriors(ivec_dev_, g, lda_norm, ld_l, post_idx, post_w, s);
-    double *gamma = arena_.AllocT<double>((size_t)n_utts * G), *wfeats = arena_.AllocT<double>((size_t)n_utts * G * Dl);
-    double *linear = arena_.AllocT<double>((size_t)n_utts * Di), *quad = arena_.AllocT<double>((size_t)n_utts * usz);
-    double *numf = arena_.AllocT<double>(n_utts), *x = arena_.AllocT<double>((size_t)n_utts * Di);
-    d_ivec = arena_.AllocT<float>((size_t)n_ivrows * ld_i + 256);   // + slack: staging loads may read past a row's end
-    if (streaming) {          // (whole utterances: the accumulate kernel starts the sums itself)
-      RS_HIP(hipMemsetAsync(gamma, 0, sizeof(double) * (size_t)n_utts * G, s));
-      RS_HIP(hipMemsetAsync(wfeats, 0, sizeof(double) * (size_t)n_utts * G * Dl, s));
-    }
-    RS_HIP(hipMemsetAsync(d_ivec, 0, sizeof(float) * (size_t)n_ivrows * ld_i, s));
-    LaunchIvecInit(ivec_dev_, n_utts, linear, quad, x, numf, s);
-    double *iv_scratch = arena_.AllocT<double>(IvecStatsScratchDoubles(ivec_dev_, n_utts));
-    const float *stats_feats = fc_.ie.online_cmvn_iextractor ? lda_norm : lda_raw;
-    if (!streaming) {
-      poison();
-      LaunchIvecAccumulate(ivec_dev_, g, stats_feats, ld_l, post_idx, post_w, nullptr, nullptr, gamma, wfeats, true, s);
-      poison();
-      LaunchIvecStats(ivec_dev_, n_utts, gamma, wfeats, linear, quad, numf, iv_scratch, s);
-      LaunchIvecSolve(ivec_dev_, n_utts, linear, quad, numf, x, d_ivec, ld_i, nullptr, nullptr, s);
-    } else {
-      // per-chunk schedule tables: [step][utt] frame_begin, frame_end, out_row, active
-      std::vector<int> fb((size_t)max_chunks * n_utts, 0), fe((size_t)max_chunks * n_utts, 0), orow((size_t)max_chunks * n_utts, -1),
-          act((size_t)max_chunks * n_utts, 0);
-      for (int u = 0; u < n_utts; u++) {
-        int done = 0;
-        for (size_t k = 0; k < chunk_last[u].size(); k++) {
-          const size_t i = k * n_utts + u;
-          const int last = chunk_last[u][k];
-          orow[i] = ivrow_base[u] + (int)k;
-          if (last + 1 > done) { fb[i] = done; fe[i] = last + 1; act[i] = 1; done = last + 1; }
-        }
-      }
-      int *d_fb = arena_.AllocT<int>(fb.size()), *d_fe = arena_.AllocT<int>(fb.size()), *d_or = arena_.AllocT<int>(fb.size()),
-          *d_ac = arena_.AllocT<int>(fb.size());
-      RS_HIP(hipMemcpyAsync(d_fb, fb.data(), sizeof(int) * fb.size(), hipMemcpyHostToDevice, s));
-      RS_HIP(hipMemcpyAsync(d_fe, fe.data(), sizeof(int) * fb.size(), hipMemcpyHostToDevice, s));
-      RS_HIP(hipMemcpyAsync(d_or, orow.data(), sizeof(int) * fb.size(), hipMemcpyHostToDevice, s));
-      RS_HIP(hipMemcpyAsync(d_ac, act.data(), sizeof(int) * fb.size(), hipMemcpyHostToDevice, s));
-      RS_HIP(hipStreamSynchronize(s));
-      if (Di <= 128) {
-        IvecChunkChain(arena_, g, n_utts, max_chunks, stats_feats, ld_l, post_idx, post_w, d_fb, d_fe, d_or, d_ac, linear, quad, numf, x, nullptr, d_ivec, ld_i, s);
-      } else {
-        for (int k = 0; k < max_chunks; k++) {
-          const size_t o = (size_t)k * n_utts;
-          LaunchIvecAccumulate(ivec_dev_, g, stats_feats, ld_l, post_idx, post_w, d_fb + o, d_fe + o, gamma, wfeats, false, s);
-          LaunchIvecStats(ivec_dev_, n_utts, gamma, wfeats, linear, quad, numf, iv_scratch, s);
-          LaunchIvecSolve(ivec_dev_, n_utts, linear, quad, numf, x, d_ivec, ld_i, d_or + o, d_ac + o, s);
-          LaunchIvecClear(ivec_dev_, n_utts, gamma, wfeats, s);
-        }
-      }
-    }
-  }
+  if (fc_.ie.present) BatchIvectors(&b);
   stage_end(0);
   // ---- search work buffers (before the acoustic model: the last layer can be pipelined with the search)
-  AllocSearch(&sp, arena_, s);
-  const DecodeOptsDev &dopts = sp.dopts;
-  DenseWork &dw = sp.dw;
+  AllocSearch(&sp, *b.arena, s);
+  const int ld_i = RoundUp(std::max(fc_.ie.present ? fc_.ie.ivector_dim() : 0, 1), 4);
   tm.Mark();
   // ---- acoustic model
   stage_begin(1);
   if (pipelined) {
-    RunNnet(bufp, buf_ld, d_ivec, ld_i, d_row_ivec, rows, row_maps, cx.active_groups, 0, nn.ops.size() - 1, s, &imgs);
+    RunNnet(b.bufp, b.buf_ld, b.d_ivec, ld_i, b.d_row_ivec, b.rows, b.row_maps, cx.active_groups, 0, nn.ops.size() - 1, s, &b.imgs);
     // slab k: output layer on the main stream, then the search of that slab on the decode stream
     const size_t i = nn.ops.size() - 1;
-    GemmDev gd = MakeGemm(gemm_plans_[i], bufp, buf_ld, d_ivec, ld_i, bufp[nn.ops[i].out_buf], buf_ld[nn.ops[i].out_buf], cx.active_groups, &imgs,
+    GemmDev gd = MakeGemm(gemm_plans_[i], b.bufp, b.buf_ld, b.d_ivec, ld_i, b.bufp[nn.ops[i].out_buf], b.buf_ld[nn.ops[i].out_buf], cx.active_groups, &b.imgs,
                           (int)nn.ops[i].out_buf);
     for (int k = 0; k < n_slabs; k++) {
-      gd.row_map = d_frame_rows + slab_off[k];
-      LaunchGemm(gd, slab_off[k + 1] - slab_off[k], d_row_ivec, s);
+      gd.row_map = b.d_frame_rows + b.lists.slab_off[k];
+      LaunchGemm(gd, b.lists.slab_off[k + 1] - b.lists.slab_off[k], b.d_row_ivec, s);
       RS_HIP(hipEventRecord(cx.slab_ev[k], s));
       RS_HIP(hipStreamWaitEvent(cx.stream_dec, cx.slab_ev[k], 0));
-      LaunchDecodeReg(hclg_dev_, reg_dev_, dopts, g, bufp[nn.output_buf], buf_ld[nn.output_buf], dw, k == 0 ? -1 : k * slab_len,
-                      k + 1 == n_slabs ? maxT + 1 : (k + 1) * slab_len, cx.stream_dec);
+      LaunchDecodeReg(hclg_dev_, reg_dev_, sp.dopts, b.g, b.bufp[nn.output_buf], b.buf_ld[nn.output_buf], sp.dw, k == 0 ? -1 : k * slab_len,
+                      k + 1 == n_slabs ? b.maxT + 1 : (k + 1) * slab_len, cx.stream_dec);
     }
     RS_HIP(hipEventRecord(cx.slab_ev[8], cx.stream_dec));
   } else {
-    poison();
-    RunNnet(bufp, buf_ld, d_ivec, ld_i, d_row_ivec, rows, row_maps, cx.active_groups, 0, nn.ops.size(), s, &imgs);
+    LdsPoison(s);
+    RunNnet(b.bufp, b.buf_ld, b.d_ivec, ld_i, b.d_row_ivec, b.rows, b.row_maps, cx.active_groups, 0, nn.ops.size(), s, &b.imgs);
   }
   stage_end(1);
-  float *ll = bufp[nn.output_buf];
-  int ll_ld = buf_ld[nn.output_buf];
-  BatchGeom gdec = g;                     // what the search sees: the utterances' decoder frames
-  if (fsf > 1) {
-    // the rows the decoder reads, gathered into a dense [decoder frame][pdf] array with its own geometry (no halo)
-    const int nd = dec_base[n_utts];
-    int *h_idx = harena.AllocT<int>((size_t)nd + 2 * (size_t)n_utts + 2);
-    int *h_T = h_idx + nd, *h_base = h_T + n_utts;
-    for (int u = 0; u < n_utts; u++) {
-      for (int f = 0; f < T_dec[u]; f++) h_idx[dec_base[u] + f] = row_base[u] + L_ + f * fsf;
-      h_T[u] = T_dec[u];
-      h_base[u] = dec_base[u];
-    }
-    h_base[n_utts] = nd;
-    int *d_idx = arena_.AllocT<int>((size_t)nd + 2 * (size_t)n_utts + 2);
-    RS_HIP(hipMemcpyAsync(d_idx, h_idx, sizeof(int) * ((size_t)nd + 2 * (size_t)n_utts + 2), hipMemcpyHostToDevice, s));
-    const int ld_dec = RoundUp(P, 4);
-    float *ll_dec = arena_.AllocT<float>(((size_t)nd + 8) * ld_dec);
-    if (nd > 0) LaunchCopyRows(ll, ll_ld, d_idx, ll_dec, ld_dec, nullptr, nd, P, s);
-    ll = ll_dec; ll_ld = ld_dec;
-    gdec.L = 0; gdec.R = 0; gdec.total_rows = nd; gdec.total_frames = nd; gdec.max_frames = maxT_dec;
-    gdec.d_num_frames = d_idx + nd; gdec.d_row_base = d_idx + nd + n_utts; gdec.d_frame_base = d_idx + nd + n_utts;
-    gdec.d_row_utt = nullptr; gdec.d_row_t = nullptr; gdec.d_sample_off = nullptr;
-  }
+  float *ll = b.bufp[nn.output_buf];
+  int ll_ld = b.buf_ld[nn.output_buf];
+  BatchGeom gdec = b.g;                     // what the search sees: the utterances' decoder frames
+  if (fsf > 1) BatchDecoderRows(&b, &ll, &ll_ld, &gdec);
   tm.Mark();
   // ---- decode
   if (pipelined) RS_HIP(hipStreamWaitEvent(s, cx.slab_ev[8], 0));       // the search of the last slab
-  else { poison(); LaunchSearch(&sp, arena_, gdec, ll, ll_ld, s); }
+  else { LdsPoison(s); LaunchSearch(&sp, *b.arena, gdec, ll, ll_ld, s); }
   tm.Mark();
-  CollectResults(sp, cx, gi, gdec, T_dec.data(), ll, ll_ld, nbest, lat_scale, s, out_utts, timings);
+  CollectResults(sp, cx, gi, gdec, b.T_dec.data(), ll, ll_ld, nbest, lat_scale, s, out_utts, timings);
   tm.Mark();
-  if (opts_.keep_intermediates) {
-    for (int u = 0; u < n_utts; u++) {
-      UttResult &ur = out_utts[u];
-      ur.feat_dim = C; ur.num_pdfs = P; ur.ivec_dim = Di; ur.ivec_rows = has_iv ? ivrow_base[u + 1] - ivrow_base[u] : 0;
-      if (T[u] == 0) continue;
-      ur.feats.resize((size_t)T[u] * C);
-      ur.loglikes.resize((size_t)T_dec[u] * P);
-      const float *fin = bufp[nn.input_buf] + ((size_t)row_base[u] + L_) * buf_ld[nn.input_buf];
-      RS_HIP(hipMemcpy2D(ur.feats.data(), sizeof(float) * C, fin, sizeof(float) * buf_ld[nn.input_buf], sizeof(float) * C, T[u], hipMemcpyDeviceToHost));
-      const float *lin = ll + (fsf > 1 ? (size_t)dec_base[u] : (size_t)row_base[u] + L_) * ll_ld;
-      RS_HIP(hipMemcpy2D(ur.loglikes.data(), sizeof(float) * P, lin, sizeof(float) * ll_ld, sizeof(float) * P, T_dec[u], hipMemcpyDeviceToHost));
-      if (has_iv) {
-        ur.ivector.resize((size_t)ur.ivec_rows * Di);
-        RS_HIP(hipMemcpy2D(ur.ivector.data(), sizeof(float) * Di, d_ivec + (size_t)ivrow_base[u] * ld_i, sizeof(float) * ld_i,
-                           sizeof(float) * Di, ur.ivec_rows, hipMemcpyDeviceToHost));
-      }
-    }
-  }
+  if (opts_.keep_intermediates) BatchIntermediates(b, ll, ll_ld, out_utts);
   // kernel launches are not checked one by one; a failed launch of this thread surfaces here instead of as silent garbage
   { const hipError_t le = hipGetLastError(); if (le != hipSuccess) Fail(std::string("a kernel launch failed: ") + hipGetErrorString(le)); }
   timings[1] = tm.Ms(0, 1);

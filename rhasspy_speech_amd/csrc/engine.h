@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <condition_variable>
 #include <atomic>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/rhasspy_speech_hip.h"
+#include "call_plan.h"
 #include "kernels.h"
 #include "lattice.h"
 #include "model.h"
@@ -98,6 +100,9 @@ struct Timer {
 };
 
 struct StreamPool;                                                 // stream.cc
+struct AdvanceSet;
+struct BatchCall;                                                  // engine.cc
+struct StagesBC;
 void SampleGemmMode(bool exact, int *ovf_dev);                   // engine.cc: which layer GEMMs this thread's launches use, and whose range flag they raise
 struct StreamPoolDeleter { void operator()(StreamPool *p) const; };
 
@@ -183,6 +188,14 @@ class Model {
   struct DecodeContext;
   void DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const int64_t *sample_offsets, int n_utts, int nbest, float lat_scale,
                    hipStream_t s, bool streaming, UttResult *out_utts, float *timings);
+  // DecodeGroup's stages (engine.cc)
+  void BatchFrames(const int64_t *sample_offsets, BatchCall *b) const;
+  size_t BatchArenaBytes(BatchCall *b, int nbest, float lat_scale, SearchPlan *sp) const;
+  void BatchSetupUpload(const int64_t *sample_offsets, BatchCall *b);
+  void BatchFeatures(const int16_t *d_pcm, BatchCall *b);
+  void BatchIvectors(BatchCall *b);
+  void BatchDecoderRows(BatchCall *b, float **ll, int *ll_ld, BatchGeom *gdec);
+  void BatchIntermediates(const BatchCall &b, const float *ll, int ll_ld, UttResult *out_utts) const;
   template <typename T> T *Upload(const std::vector<T> &v);
   void *UploadBytes(const void *p, size_t bytes);
   void BuildGemmPlan(const LayerOp &op, GemmPlan *plan);
@@ -259,6 +272,18 @@ class Model {
   void StreamsDrain(StreamPool *p, float *extra);
   void IssuerSync(StreamPool *p);     // everything handed to the pool's issuing thread has been queued; ITS failure poisons the open streams, then rethrows
   void StreamGrow(rs_stream *st, int need_frames);
+  // One advance, stage by stage (stream.cc: StreamsAdvanceLocked is their outline)
+  PlanConfig PlanCfg() const;         // the integers call_plan.h plans with
+  int AdvanceTakeSet(StreamPool *p, bool final);
+  void AdvancePlanStreams(StreamPool *p, rs_stream *const *streams, int n, bool flush, bool final, AdvancePlan *plan);
+  void AdvanceUpload(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, size_t search_bytes, bool final, AdvanceSet *set);
+  void AdvanceStageA(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set);
+  void AdvanceIvectors(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set);
+  void AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set, bool final, bool reg_windows, SearchPlan *sp);
+  void IssueStagesBC(const StagesBC &j);      // on the caller's thread (a finishing call) or the pool's issuing thread
+  void AdvanceBookkeeping(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, int par, bool searched);
+  void AdvanceFinish(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, const AdvanceSet &set, SearchPlan &sp, bool flush, int nbest,
+                     float lat_scale, std::chrono::steady_clock::time_point wall0, Result *res);
   void StreamsPartialLocked(rs_stream *const *streams, int n, Result *res);      // pool_mu_ held
   void StreamsEndpointLocked(rs_stream *const *streams, int n, const std::vector<int32_t> &sil_phones, rs_endpoint_status *out, std::string *search_error);      // pool_mu_ held
   // "the arc's transition-id belongs to a silence phone", one bit per HCLG arc, on the device; rebuilt when the phone list changes
@@ -328,8 +353,7 @@ struct rs_stream {
   long pcm_start = 0, n_samples = 0;
   int slot = -1, row0 = 0, cap = 0;   // the stream's slot and frame-row range in the model's pool
   int frames_mfcc = 0;             // MFCC (and CMVN) frames produced
-  long ticks_done = 0;             // 1024-sample ticks the chunk schedule has seen
-  int chunks_sched = 0;            // nnet chunks computed
+  rs::ChunkCursor sched;           // the chunk schedule so far: ticks seen, nnet chunks computed (call_plan.h)
   int stats_done = 0;              // frames accumulated into the iVector statistics
   int ll_done = 0;                 // frames with log-likelihoods in the pool
   int frames_decoded = 0;          // frames the incremental search has consumed

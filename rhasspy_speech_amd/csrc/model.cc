@@ -1,4 +1,5 @@
 #include "model.h"
+#include "call_plan.h"
 #include "nnet3_setup.h"
 #include "env.h"
 
@@ -61,9 +62,7 @@ void ReadMfccOptions(const std::string &conf_path, MfccOptions *o) {
 }
 
 int NumFrames(long num_samples, const MfccOptions &o) {
-  long shift = o.WindowShift(), len = o.WindowSize();
-  if (num_samples < len) return 0;
-  return (int)(1 + (num_samples - len) / shift);
+  return FramesOf(num_samples, o.WindowSize(), o.WindowShift());
 }
 
 // mel-computations.h:81-87

@@ -27,6 +27,7 @@
 // rs_streams_finish = one last advance with end-of-input semantics, then traceback / lattice / result records: its device
 // work is one chunk's worth when the streams were advanced as the audio came in.
 #include <algorithm>
+#include <chrono>
 #include <condition_variable>
 #include <cstring>
 #include <deque>
@@ -168,6 +169,8 @@ struct StreamPool {
   std::map<int, int> free_rows;  // start -> length
   std::vector<void *> owned;
   float host_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // host time of the sections of an advance (RS_STREAMS_TRACE)
+  AdvancePlan plans[kDepth];      // the plan of the advance on each arena set: reused, so that its vectors keep their capacity (call_plan.h)
+  std::vector<StreamView> views;  // ... and what it reads of the call's streams
   float stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // device time of the stages, summed over the advances since the last finish
 
   int AllocRows(int n) {
@@ -218,23 +221,6 @@ namespace {
 int RoundUp(int x, int m) { return (x + m - 1) / m * m; }
 int EnvInt(const char *name, int dflt) { const char *e = std::getenv(name); return e ? std::atoi(e) : dflt; }
 
-// index arrays of one advance: collected on the host, uploaded with one copy
-struct IntStage {
-  std::vector<int> h;
-  size_t Add(const std::vector<int> &v) {
-    const size_t o = h.size();
-    h.insert(h.end(), v.begin(), v.end());
-    while (h.size() & 3) h.push_back(0);
-    return o;
-  }
-  size_t Add64(const std::vector<int64_t> &v) {
-    const size_t o = h.size();
-    h.resize(o + 2 * v.size());
-    if (!v.empty()) std::memcpy(&h[o], v.data(), 8 * v.size());
-    while (h.size() & 3) h.push_back(0);
-    return o;
-  }
-};
 }  // namespace
 
 StreamPool *Model::Pool() {
@@ -501,7 +487,7 @@ void Model::StreamEnd(rs_stream *st, bool flushed) {
   if (!pool_) return;
   // the frames GetState covers: all of them after a finish; after a finalize those of the complete ticks (what lies beyond the last
   // complete tick is ignored, as by the results)
-  st->adapt_frames = flushed ? st->frames_mfcc : std::min(st->frames_mfcc, NumFrames(1024L * st->ticks_done, fc_.mfcc.opts));
+  st->adapt_frames = flushed ? st->frames_mfcc : std::min(st->frames_mfcc, NumFrames(kTickSamples * st->sched.ticks_done, fc_.mfcc.opts));
   st->open = false;
   st->ended = true;
   auto &os = pool_->open_streams;
@@ -580,424 +566,355 @@ void Model::StreamsAdvance(rs_stream *const *streams, int n, bool final, int nbe
   }
 }
 
-void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res, bool every_tick, bool no_flush) {
-  // no_flush (rs_streams_finalize): the end of the streams as the reference reaches it after an endpoint -- FinalizeDecoding() without
-  // InputFinished() (online2-wav-nnet3-latgen-faster.cc:270-278): the ticks completed are scheduled like by any advance, nothing is
-  // flushed, and the final stage runs over the decoder frames those ticks give
-  const bool flush = final && !no_flush;
-  StreamPool *p = Pool();
-  RS_HIP(hipSetDevice(opts_.device_id));
-  // queues: qa = features + iVectors (stage A), q = acoustic model + search (stage B, behind stage A's event); consecutive
-  // advances rotate over kDepth arena / staging sets, so the host plans and issues the next advances while earlier ones still run
-  // Coalescing: nothing but the end of a stream reads what an advance computes, and an advance is chains of small dependent launches
-  // (the iVector estimator's per-chunk chain is the longest queue of a step: ~300 us per advance whatever the number of chunks) -- so
-  // a call that brings less than min_ticks ticks of new audio on every stream leaves it to the next one.  The chunk / iVector
-  // schedule is a function of the sample counts, not of the calls (the tick loop below): same rows, same results as with one
-  // advance per tick or one at the end (the three delivery patterns of the stream tests).  RS_STREAM_MIN_TICKS=1: every call works.
-  if (!final && !every_tick && p->min_ticks > 1) {
-    long most = 0;
-    for (int i = 0; i < n; i++) most = std::max(most, (long)(streams[i]->n_samples / 1024) - streams[i]->ticks_done);
-    if (most < p->min_ticks) return;
+// ---------------------------------------------------------------------------------------------------------- one advance, stage by stage
+namespace {
+// The host's time per section of an advance, into StreamPool::host_ms (RS_STREAMS_TRACE: plan | arena + uploads | issue of stage A | B | C)
+struct HostClock {
+  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+  void Mark(float *ms) {
+    const auto now = std::chrono::steady_clock::now();
+    *ms += std::chrono::duration<float, std::milli>(now - last).count();
+    last = now;
   }
-  hipStream_t qa = p->qa, q = p->q, qc = p->qc, qi = p->qi;
-  DecodeContext &cx = *static_cast<DecodeContext *>(p->cx);
+};
+float MsSince(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+void MarkIf(bool timed, Timer *t) { if (timed) t->Mark(); }
+float *AllocGuarded(DeviceArena &arena, int rows, int ld, int guard) { return arena.AllocT<float>(((size_t)rows + 2 * guard) * ld) + (size_t)guard * ld; }
+}  // namespace
+
+// The arena / staging set an advance runs on and what its upload left there
+struct AdvanceSet {
+  int par = 0;
+  DeviceArena *arena = nullptr;
+  HostArena *harena = nullptr;
+  int *d_is = nullptr;           // AdvancePlan::stage on the device
+  int16_t *d_pcm = nullptr;      // the new samples of the streams with new frames, back to back
+  bool timed = false;            // this advance carries the stage timers' events (StreamPool::kTimedEvery)
+  int guard = 0;
+  std::vector<int> buf_ld;       // row pitch of the network's buffers
+};
+
+// Stages B and C of an advance -- the acoustic model and the scatter into the pool on q, the search windows on qc -- as the values
+// they need: everything queues on q / qc and needs nothing the caller's thread computes later.  A finishing call runs it itself
+// (Model::IssueStagesBC); everyone else hands it to the pool's issuing thread.  Its buffers came out of the arena in the caller's thread.
+struct StagesBC {
+  StreamPool *p = nullptr;
+  DeviceArena *arena = nullptr;
+  int par = 0;
+  bool final = false, timed = false, reg_windows = false, exact = false;
+  int *ovf_dev = nullptr;
+  int nI = 0, nN = 0, rowsN = 0, framesN = 0, maxTn = 1, n = 0, n_sub = 0;
+  bool have_sub = false;
+  const int *d_nsrc = nullptr, *d_nfb = nullptr, *d_nrb = nullptr, *d_nriv = nullptr, *d_nll = nullptr, *d_nlls = nullptr, *d_slots = nullptr;
+  std::vector<float *> bufp;
+  std::vector<int> buf_ld;
+  std::vector<ActImage> imgs;
+  int *frame_rows = nullptr;
+  BatchGeom gd;
+  DenseWork dw;
+  DecodeOptsDev dopts;
+  SearchPlan *sp = nullptr;      // (a finishing call only)
+};
+
+// Coalescing: nothing but the end of a stream reads what an advance computes, and an advance is chains of small dependent launches
+// (the iVector estimator's per-chunk chain is the longest queue of a step: ~300 us per advance whatever the number of chunks) -- so
+// a call that brings less than min_ticks ticks of new audio on every stream leaves it to the next one.  The chunk / iVector
+// schedule is a function of the sample counts, not of the calls (ScheduleChunks): same rows, same results as with one
+// advance per tick or one at the end (the three delivery patterns of the stream tests).  RS_STREAM_MIN_TICKS=1: every call works.
+static bool LeftToTheNextCall(const StreamPool *p, rs_stream *const *streams, int n) {
+  if (p->min_ticks <= 1) return false;
+  long most = 0;
+  for (int i = 0; i < n; i++) most = std::max(most, (long)(streams[i]->n_samples / kTickSamples) - streams[i]->sched.ticks_done);
+  return most < p->min_ticks;
+}
+
+PlanConfig Model::PlanCfg() const {
+  PlanConfig c;
+  c.window = fc_.mfcc.win; c.shift = fc_.mfcc.shift;
+  c.chunk = opts_.frames_per_chunk;
+  c.L = L_; c.R = R_; c.Rm = am_.nnet.right_context;
+  c.has_iv = fc_.ie.present;
+  c.sl = c.has_iv ? fc_.ie.splice_left : 0; c.sr = c.has_iv ? fc_.ie.splice_right : 0;
+  c.fsf = opts_.frame_subsampling_factor;
+  return c;
+}
+
+// Consecutive advances rotate over kDepth arena / staging sets, so the host plans and issues the next advances while earlier ones
+// still run: the advance kDepth calls ago used this set and has to be over (it normally is)
+int Model::AdvanceTakeSet(StreamPool *p, bool final) {
   const int par = (int)(p->n_adv % StreamPool::kDepth);
-  DeviceArena &arena = cx.arena[par];
-  HostArena &harena = cx.host_arena[par];
   if (final) IssuerSync(p);      // a finishing call issues everything itself, behind what the issuing thread still holds
-  if (p->pending[par]) {       // the advance kDepth calls ago used this set: it has to be over (it normally is)
+  if (p->pending[par]) {
     const auto w0 = std::chrono::steady_clock::now();
     IssuerSync(p);         // (its done event has been recorded)
     RS_HIP(hipEventSynchronize(p->ev_done[par]));
-    p->stage_ms[7] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - w0).count();
+    p->stage_ms[7] += MsSince(w0);
     p->pending[par] = false;
     p->Account(par, nullptr);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) Fail(std::string("a kernel launch failed: ") + hipGetErrorString(le));
     StreamsCheckRange();
   }
-  SampleGemmMode(exact_gemm_.load(), cx.gemm_ovf_dev);
+  return par;
+}
+
+// The plan of the advance (call_plan.h), in its two steps around the move of the streams that outgrew their rows
+void Model::AdvancePlanStreams(StreamPool *p, rs_stream *const *streams, int n, bool flush, bool final, AdvancePlan *plan) {
+  const PlanConfig cfg = PlanCfg();
+  std::vector<StreamView> &views = p->views;
+  views.resize(n);
+  for (int i = 0; i < n; i++) {
+    const rs_stream &st = *streams[i];
+    StreamView &v = views[i];
+    v.n_samples = st.n_samples; v.sched = st.sched;
+    v.frames_mfcc = st.frames_mfcc; v.stats_done = st.stats_done; v.ll_done = st.ll_done; v.frames_decoded = st.frames_decoded; v.dec_started = st.dec_started;
+    v.slot = st.slot; v.spk_iv = st.spk_iv; v.spk_nn = st.spk_nn;
+  }
+  PlanAdvanceSchedule(cfg, views.data(), n, flush, plan);
+  for (int i = 0; i < n; i++) {
+    if (plan->pl[i].avail + 2 > streams[i]->cap) StreamGrow(streams[i], plan->pl[i].avail + 2);
+    views[i].row0 = streams[i]->row0;
+  }
+  PlanAdvanceRows(cfg, views.data(), n, flush, final, plan);
+}
+
+// Arena of the set sized for every stage, then the uploads on qa: the index arrays in one copy, the new samples in another
+void Model::AdvanceUpload(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, size_t search_bytes, bool final, AdvanceSet *set) {
   const Nnet &nn = am_.nnet;
   const bool has_iv = fc_.ie.present;
-  const int C = fc_.mfcc.nceps, P = nn.output_dim, chunk = p->chunk, Rm = nn.right_context, fsf = opts_.frame_subsampling_factor;
-  const int shift = fc_.mfcc.shift;
-  const int sl = has_iv ? fc_.ie.splice_left : 0, sr = has_iv ? fc_.ie.splice_right : 0;
   const int Dl = has_iv ? fc_.ie.feat_dim() : 0, Di = has_iv ? fc_.ie.ivector_dim() : 0, G = has_iv ? fc_.ie.num_gauss() : 0;
-  const int ld_c = p->ld_c, ld_l = RoundUp(std::max(Dl, 1), 4), ld_i = p->ld_i, usz = Di * (Di + 1) / 2, nsel = has_iv ? fc_.ie.num_gselect : 0;
-  auto wall0 = std::chrono::steady_clock::now();
-  // (RS_STREAMS_TRACE: the host's time per section -- plan | arena + uploads | issue of stage A | B | C)
-  auto host_last = wall0;
-#define HOST_MARK(i) do { const auto n_ = std::chrono::steady_clock::now(); p->host_ms[i] += std::chrono::duration<float, std::milli>(n_ - host_last).count(); host_last = n_; } while (0)
-
-  // ---------------------------------------------------------------- plan (host)
-  struct Plan {
-    int avail = 0;                 // frames computable from the samples accepted so far
-    int mf0 = 0;                   // first new MFCC frame
-    std::vector<std::pair<int, int>> chunks;      // new nnet chunks: (index, last frame its iVector has seen)
-    int sa = 0, sb = 0;            // frames to splice / LDA / score for the iVector statistics: [sa, sb)
-    int t0 = 0, t1 = 0;            // frames that get log-likelihoods in this advance: [t0, t1)
-  };
-  std::vector<Plan> pl(n);
-  int max_new_chunks = 0;
-  for (int i = 0; i < n; i++) {
-    rs_stream &st = *streams[i];
-    Plan &a = pl[i];
-    const long ns = st.n_samples;
-    a.avail = NumFrames(ns, fc_.mfcc.opts);
-    if (a.avail + 2 > st.cap) StreamGrow(&st, a.avail + 2);
-    a.mf0 = st.frames_mfcc;
-    // the tick schedule (DecodeGroup's, resumed): ticks completed by the samples so far; the partial last read counts at EOF
-    const long ticks = flush ? (ns + 1023) / 1024 : ns / 1024;
-    const int nch_final = (a.avail + chunk - 1) / chunk;
-    for (long j = st.ticks_done; j < ticks; j++) {
-      const int fr = NumFrames(std::min<long>(1024 * (j + 1), ns), fc_.mfcc.opts);
-      const int ready = std::max(0, fr - Rm) / chunk;
-      while (st.chunks_sched < ready && (!flush || st.chunks_sched < nch_final)) {
-        a.chunks.push_back({st.chunks_sched, std::min(fr - 1, fr - sr - 1)});
-        st.chunks_sched++;
-      }
-    }
-    st.ticks_done = ticks;
-    if (flush) while (st.chunks_sched < nch_final) { a.chunks.push_back({st.chunks_sched, a.avail - 1}); st.chunks_sched++; }
-    max_new_chunks = std::max(max_new_chunks, (int)a.chunks.size());
-    a.sa = a.sb = st.stats_done;
-    for (auto &c : a.chunks) a.sb = std::max(a.sb, c.second + 1);
-    a.t0 = st.ll_done;
-    a.t1 = flush ? a.avail : std::min(chunk * st.chunks_sched, a.avail);
-  }
-  // ---------------------------------------------------------------- transient geometry of the stages, index arrays
-  IntStage is;
-  std::vector<int> slots(n), row0s(n), avails(n);
-  for (int i = 0; i < n; i++) { slots[i] = streams[i]->slot; row0s[i] = streams[i]->row0; avails[i] = ((flush ? pl[i].avail : pl[i].t1) + fsf - 1) / fsf; }      // (the frames a final stage covers)
-  // stage 1: MFCC over the new frames (dense rows, no halo), rows -> pool
-  std::vector<int> m_T, m_rb{0}, m_out, m_f0;
-  std::vector<int64_t> m_so{0};
-  size_t pcm_total = 0;
-  for (int i = 0; i < n; i++) {
-    const int tn = pl[i].avail - pl[i].mf0;
-    if (tn <= 0) continue;
-    rs_stream &st = *streams[i];
-    const long first = (long)pl[i].mf0 * shift, cnt = st.n_samples - first;
-    m_T.push_back(tn);
-    m_f0.push_back(pl[i].mf0);
-    m_rb.push_back(m_rb.back() + tn);
-    m_so.push_back(m_so.back() + cnt);
-    { const size_t b0 = m_out.size(); m_out.resize(b0 + tn); int *po = m_out.data() + b0; const int r0 = st.row0 + pl[i].mf0; for (int t = 0; t < tn; t++) po[t] = r0 + t; }
-    pcm_total += (size_t)cnt;
-  }
-  const int nM = (int)m_T.size(), rowsM = m_rb.back();
-  m_T.push_back(0);
-  m_f0.push_back(0);
-  // stage 2: CMVN resumed (same streams)
-  std::vector<int> c_T, c_rb, c_tb, c_slot, c_spk_iv, c_spk_nn;
-  bool any_spk_iv = false, any_spk_nn = false;      // a stream of the call carries speaker statistics: the CMVN kernel with that term
-  for (int i = 0; i < n; i++)
-    if (pl[i].avail > pl[i].mf0) {
-      const rs_stream &st = *streams[i];
-      c_T.push_back(pl[i].avail); c_rb.push_back(st.row0); c_tb.push_back(pl[i].mf0); c_slot.push_back(st.slot);
-      c_spk_iv.push_back(st.spk_iv ? st.slot : -1); c_spk_nn.push_back(st.spk_nn ? st.slot : -1);
-      any_spk_iv = any_spk_iv || st.spk_iv; any_spk_nn = any_spk_nn || st.spk_nn;
-    }
-  c_rb.push_back(0);
-  // stage 3: iVector segments
-  std::vector<int> I_idx;
-  for (int i = 0; i < n; i++) if (has_iv && !pl[i].chunks.empty()) I_idx.push_back(i);
-  const int nI = (int)I_idx.size();
-  std::vector<int> i_T(nI + 1, 0), i_rb(nI + 1, 0), i_src, i_slot(nI);
-  for (int u = 0; u < nI; u++) {
-    const Plan &a = pl[I_idx[u]];
-    const rs_stream &st = *streams[I_idx[u]];
-    i_T[u] = a.sb - a.sa;
-    i_rb[u + 1] = i_rb[u] + i_T[u] + sl + sr;
-    i_slot[u] = st.slot;
-    {
-      const int nr = i_T[u] + sl + sr, hi = std::max(a.avail - 1, 0), t_first = a.sa - sl;
-      const size_t b0 = i_src.size();
-      i_src.resize(b0 + nr);
-      int *ps = i_src.data() + b0;
-      for (int r = 0; r < nr; r++) { const int t = t_first + r; ps[r] = st.row0 + (t < 0 ? 0 : (t > hi ? hi : t)); }
-    }
-  }
-  const int rowsI = i_rb[nI];
-  std::vector<int> s_fb((size_t)max_new_chunks * std::max(nI, 1), 0), s_fe(s_fb.size(), 0), s_or(s_fb.size(), -1), s_ac(s_fb.size(), 0);
-  for (int u = 0; u < nI; u++) {
-    const Plan &a = pl[I_idx[u]];
-    const rs_stream &st = *streams[I_idx[u]];
-    int done = a.sa;
-    for (size_t k = 0; k < a.chunks.size(); k++) {
-      const size_t o = k * nI + u;
-      s_or[o] = st.row0 / chunk + a.chunks[k].first;
-      if (a.chunks[k].second + 1 > done) { s_fb[o] = done - a.sa; s_fe[o] = a.chunks[k].second + 1 - a.sa; s_ac[o] = 1; done = a.chunks[k].second + 1; }
-    }
-  }
-  // stage 4: nnet segments
-  std::vector<int> N_idx;
-  for (int i = 0; i < n; i++) if (pl[i].t1 > pl[i].t0) N_idx.push_back(i);
-  const int nN = (int)N_idx.size();
-  std::vector<int> n_T(nN + 1, 0), n_rb(nN + 1, 0), n_fb(nN + 1, 0), n_src, n_riv, n_lldst, n_llsrc;
-  {
-    size_t rows_est = 0;
-    for (int u = 0; u < nN; u++) rows_est += (size_t)(pl[N_idx[u]].t1 - pl[N_idx[u]].t0) + L_ + R_;
-    n_src.reserve(rows_est); n_riv.reserve(rows_est); n_lldst.reserve(rows_est);
-  }
-  int maxTn = 0;
-  for (int u = 0; u < nN; u++) {
-    const Plan &a = pl[N_idx[u]];
-    const rs_stream &st = *streams[N_idx[u]];
-    n_T[u] = a.t1 - a.t0;
-    maxTn = std::max(maxTn, n_T[u]);
-    n_rb[u + 1] = n_rb[u] + n_T[u] + L_ + R_;
-    n_fb[u + 1] = n_fb[u] + n_T[u];
-    {
-      // per row: the pool row it is gathered from (context rows clamped to the stream's frames) and the chunk whose iVector its
-      // Round(ivector, chunk) slot was supplied by (DecodeGroup: row_ivec) = the number of chunks j >= 1 with j * chunk + Rm <= slot_t,
-      // at most the last scheduled one.  slot_t / chunk is carried along instead of divided out per row (the plan was 3.7 ms of a
-      // 24 ms step on the host).
-      const int nr = n_T[u] + L_ + R_, hi = std::max(a.avail - 1, 0), t_first = a.t0 - L_, kmax = std::max(st.chunks_sched - 1, 0), ivrow0 = st.row0 / chunk;
-      const size_t b0 = n_src.size();
-      n_src.resize(b0 + nr);
-      n_riv.resize(b0 + nr);
-      int *ps = n_src.data() + b0, *pr = n_riv.data() + b0;
-      int q = t_first >= 0 ? t_first / chunk : -((-t_first + chunk - 1) / chunk), rem = t_first - q * chunk;      // t = q * chunk + rem, 0 <= rem < chunk
-      auto k_of = [&](int qq) { const int d = qq * chunk - Rm; const int k = d >= 0 ? d / chunk : 0; return ivrow0 + (k > kmax ? kmax : k); };
-      int kv = k_of(q);
-      for (int r = 0; r < nr; r++) {
-        const int t = t_first + r;
-        ps[r] = st.row0 + (t < 0 ? 0 : (t > hi ? hi : t));
-        pr[r] = kv;
-        if (++rem == chunk) { rem = 0; kv = k_of(++q); }
-      }
-      if (fsf == 1) {
-        const size_t l0 = n_lldst.size();
-        n_lldst.resize(l0 + n_T[u]);
-        int *pd = n_lldst.data() + l0;
-        for (int t = 0; t < n_T[u]; t++) pd[t] = st.row0 + a.t0 + t;
-      } else {
-        // --frame-subsampling-factor: the decoder's frame t / fsf is the output row of t = 0, fsf, 2 fsf, ...; only those go to the pool
-        for (int t = (a.t0 + fsf - 1) / fsf * fsf; t < a.t1; t += fsf) { n_llsrc.push_back(n_rb[u] + L_ + (t - a.t0)); n_lldst.push_back(st.row0 + t / fsf); }
-      }
-    }
-  }
-  const int rowsN = n_rb[nN], framesN = n_fb[nN];
-  // stage 5: search windows (every stream of the call: a stream that ends without new rows still needs its traceback)
-  SearchPlan sp;
-  int maxT = 0;
-  auto dec_frames = [&](int t) { return (t + fsf - 1) / fsf; };       // decoder frames of the first t feature frames (decodable-online-looped.cc:56-84)
-  int max_feat_frames = 0;                                               // (the dither table is indexed by FEATURE frames)
-  for (int i = 0; i < n; i++) { maxT = std::max(maxT, dec_frames(pl[i].avail)); max_feat_frames = std::max(max_feat_frames, pl[i].avail); }
-  size_t search_bytes = 0;
-  if (final) search_bytes = PlanSearch(n, maxT, nbest, lat_scale, &sp);
-  const bool reg_windows = p->reg && !(final && sp.want_lattice);
-  std::vector<int> d_T(n + 1, 0), d_rb(n + 1, 0), w_b(n), w_e(n), w_f(n, final ? 1 : 0);
-  for (int i = 0; i < n; i++) {
-    d_T[i] = dec_frames(pl[i].t1); d_rb[i] = streams[i]->row0;
-    w_b[i] = streams[i]->dec_started ? streams[i]->frames_decoded : -1;
-    w_e[i] = dec_frames(pl[i].t1);
-  }
-  const size_t o_mT = is.Add(m_T), o_mrb = is.Add(m_rb), o_mout = is.Add(m_out), o_mf0 = is.Add(m_f0), o_mso = is.Add64(m_so);
-  const size_t o_cT = is.Add(c_T), o_crb = is.Add(c_rb), o_ctb = is.Add(c_tb), o_cslot = is.Add(c_slot);
-  const size_t o_cspki = any_spk_iv ? is.Add(c_spk_iv) : 0, o_cspkn = any_spk_nn ? is.Add(c_spk_nn) : 0;
-  const size_t o_iT = is.Add(i_T), o_irb = is.Add(i_rb), o_isrc = is.Add(i_src), o_islot = is.Add(i_slot);
-  const size_t o_sfb = is.Add(s_fb), o_sfe = is.Add(s_fe), o_sor = is.Add(s_or), o_sac = is.Add(s_ac);
-  is.Add(n_T);
-  const size_t o_nrb = is.Add(n_rb), o_nfb = is.Add(n_fb), o_nsrc = is.Add(n_src), o_nriv = is.Add(n_riv), o_nll = is.Add(n_lldst), o_nlls = is.Add(n_llsrc);
-  const size_t o_dT = is.Add(d_T), o_drb = is.Add(d_rb), o_wb = is.Add(w_b), o_we = is.Add(w_e), o_wf = is.Add(w_f), o_slots = is.Add(slots), o_row0 = is.Add(row0s);
-  // ---------------------------------------------------------------- arena
-  HOST_MARK(0);
-  const int guard = L_ + R_ + 8;
+  const int ld_c = p->ld_c, ld_l = RoundUp(std::max(Dl, 1), 4), usz = Di * (Di + 1) / 2, nsel = has_iv ? fc_.ie.num_gselect : 0;
+  const int n = plan.n, nI = plan.nI, rowsM = plan.rowsM, rowsI = plan.rowsI, rowsN = plan.rowsN, guard = set->guard = L_ + R_ + 8;
+  DeviceArena &arena = *set->arena;
+  HostArena &harena = *set->harena;
+  hipStream_t qa = p->qa;
   auto fbytes = [&](int rows, int ld) { return ((size_t)rows + 2 * guard) * ld * sizeof(float) + 512; };
-  std::vector<int> buf_ld(nn.bufs.size());
-  size_t need = is.h.size() * 4 + pcm_total * 2 + 4096 + 3 * sizeof(int) * (size_t)(rowsM + rowsI + rowsN + 64) + sizeof(int) * (size_t)(framesN + 64);
-  for (size_t b = 0; b < nn.bufs.size(); b++) { buf_ld[b] = RoundUp(nn.bufs[b].dim, 4); need += fbytes(rowsN, buf_ld[b]); }
+  set->buf_ld.resize(nn.bufs.size());
+  size_t need = plan.stage.size() * 4 + plan.pcm_total * 2 + 4096 + 3 * sizeof(int) * (size_t)(rowsM + rowsI + rowsN + 64) + sizeof(int) * (size_t)(plan.framesN + 64);
+  for (size_t b = 0; b < nn.bufs.size(); b++) { set->buf_ld[b] = RoundUp(nn.bufs[b].dim, 4); need += fbytes(rowsN, set->buf_ld[b]); }
   need += ImageBytes(rowsN);
   if (has_iv) {
     need += 2 * fbytes(rowsI, ld_c) + 2 * fbytes(rowsI, ld_l) + (size_t)rowsI * nsel * 8 + 4096;
     need += (size_t)std::max(nI, 1) * ((size_t)G * 8 + (size_t)G * Dl * 8 + (size_t)Di * 16 + (size_t)usz * 8 + 64) + 8192;
     need += IvecStatsScratchDoubles(ivec_dev_, std::max(nI, 1)) * 8 + 1024;
-    need += IvecChunkChainBytes(ivec_dev_, std::max(nI, 1), std::max(max_new_chunks, 1));
+    need += IvecChunkChainBytes(ivec_dev_, std::max(nI, 1), std::max(plan.max_new_chunks, 1));
   }
   need += search_bytes + (size_t)n * 64 * 8 + 64 * 256 + (1u << 20);
   arena.Reserve(need, qa);
   arena.Reset();
   harena.Reset();
-  // ---------------------------------------------------------------- uploads: index arrays, new samples
-  int *d_is = arena.AllocT<int>(is.h.size() + 16);
+  const size_t n_is = plan.stage.size(), pcm_total = plan.pcm_total;
+  set->d_is = arena.AllocT<int>(n_is + 16);
   {
-    int *hp = harena.AllocT<int>(is.h.size() + 16);
-    std::memcpy(hp, is.h.data(), is.h.size() * 4);
-    RS_HIP(hipMemcpyAsync(d_is, hp, is.h.size() * 4, hipMemcpyHostToDevice, qa));
+    int *hp = harena.AllocT<int>(n_is + 16);
+    std::memcpy(hp, plan.stage.data(), n_is * 4);
+    RS_HIP(hipMemcpyAsync(set->d_is, hp, n_is * 4, hipMemcpyHostToDevice, qa));
   }
-  auto D = [&](size_t off) { return d_is + off; };
-  int16_t *d_pcm = arena.AllocT<int16_t>(pcm_total + 512);
+  set->d_pcm = arena.AllocT<int16_t>(pcm_total + 512);
   if (pcm_total) {
     int16_t *hp = harena.AllocT<int16_t>(pcm_total + 512);
+    const int shift = fc_.mfcc.shift;
     size_t o = 0;
     for (int i = 0; i < n; i++) {
-      rs_stream &st = *streams[i];
-      if (pl[i].avail <= pl[i].mf0) continue;
-      const long first = (long)pl[i].mf0 * shift, cnt = st.n_samples - first;
+      const rs_stream &st = *streams[i];
+      if (plan.pl[i].avail <= plan.pl[i].mf0) continue;
+      const long first = (long)plan.pl[i].mf0 * shift, cnt = st.n_samples - first;
       std::memcpy(hp + o, st.pcm.data() + (first - st.pcm_start), sizeof(int16_t) * (size_t)cnt);
       o += (size_t)cnt;
     }
-    RS_HIP(hipMemcpyAsync(d_pcm, hp, sizeof(int16_t) * pcm_total, hipMemcpyHostToDevice, qa));
+    RS_HIP(hipMemcpyAsync(set->d_pcm, hp, sizeof(int16_t) * pcm_total, hipMemcpyHostToDevice, qa));
   }
-  Timer &tma = *p->tm_a[par], &tmb = *p->tm_b[par], &tmc = *p->tm_c[par], &tmi = *p->tm_i[par];
-  tma.Reset(); tmb.Reset(); tmc.Reset(); tmi.Reset();
-  const bool timed = final || p->n_adv % StreamPool::kTimedEvery == 0;
-  p->time_weight[par] = final ? 1.f : (timed ? (float)StreamPool::kTimedEvery : 0.f);
-#define TM_MARK(t) do { if (timed) (t).Mark(); } while (0)
-  TM_MARK(tma);
-  // ---------------------------------------------------------------- 1. MFCC
-  HOST_MARK(1);
+  const int par = set->par;
+  p->tm_a[par]->Reset(); p->tm_b[par]->Reset(); p->tm_c[par]->Reset(); p->tm_i[par]->Reset();
+  set->timed = final || p->n_adv % StreamPool::kTimedEvery == 0;
+  p->time_weight[par] = final ? 1.f : (set->timed ? (float)StreamPool::kTimedEvery : 0.f);
+  MarkIf(set->timed, p->tm_a[par].get());
+}
+
+// Stage A on qa: 1. MFCC of the new frames, straight into the pool; 2. CMVN resumed from the parked sums; 3. for the streams with
+// new chunks splice + LDA + UBM posteriors over the not-yet-accumulated frames -- and on qi, behind them, the estimator's steps
+void Model::AdvanceStageA(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set) {
+  const AdvancePlan::Offsets &o = plan.o;
+  const int par = set.par, ld_c = p->ld_c, nM = plan.nM, rowsM = plan.rowsM;
+  const bool timed = set.timed;
+  DeviceArena &arena = *set.arena;
+  hipStream_t qa = p->qa;
+  Timer *tma = p->tm_a[par].get();
+  auto D = [&](size_t off) { return set.d_is + off; };
   if (nM > 0) {
     BatchGeom g;
     g.n_utts = nM; g.total_rows = rowsM; g.total_frames = rowsM;
-    g.d_sample_off = reinterpret_cast<const int64_t *>(D(o_mso)); g.d_num_frames = D(o_mT); g.d_row_base = D(o_mrb);
-    g.d_frame0 = D(o_mf0);
+    g.d_sample_off = reinterpret_cast<const int64_t *>(D(o.mso)); g.d_num_frames = D(o.mT); g.d_row_base = D(o.mrb);
+    g.d_frame0 = D(o.mf0);
     int *ru = arena.AllocT<int>(rowsM), *rt = arena.AllocT<int>(rowsM);
-    LaunchRowGeometry(nM, rowsM, 0, D(o_mrb), nullptr, ru, rt, nullptr, qa);
+    LaunchRowGeometry(nM, rowsM, 0, D(o.mrb), nullptr, ru, rt, nullptr, qa);
     g.d_row_utt = ru; g.d_row_t = rt;
-    LaunchMfcc(MfccWithDither(max_feat_frames), g, d_pcm, p->raw, ld_c, qa, false, D(o_mout));
-    // ---------------------------------------------------------------- 2. CMVN, resumed
+    LaunchMfcc(MfccWithDither(plan.max_feat_frames), g, set.d_pcm, p->raw, ld_c, qa, false, D(o.mout));
     BatchGeom gc;
-    gc.n_utts = nM; gc.d_num_frames = D(o_cT); gc.d_row_base = D(o_crb);
-    if (has_iv) LaunchOnlineCmvn(cmvn_iv_dev_, gc, p->raw, p->cm, ld_c, qa, D(o_ctb), p->cmvn_iv, D(o_cslot), any_spk_iv ? p->spk_iv : nullptr, any_spk_iv ? D(o_cspki) : nullptr);
+    gc.n_utts = nM; gc.d_num_frames = D(o.cT); gc.d_row_base = D(o.crb);
+    const bool spk_iv = plan.any_spk_iv, spk_nn = plan.any_spk_nn;
+    if (fc_.ie.present) LaunchOnlineCmvn(cmvn_iv_dev_, gc, p->raw, p->cm, ld_c, qa, D(o.ctb), p->cmvn_iv, D(o.cslot), spk_iv ? p->spk_iv : nullptr, spk_iv ? D(o.cspki) : nullptr);
     if (fc_.use_cmvn)
-      LaunchOnlineCmvn(cmvn_nnet_dev_, gc, p->raw, p->nn_in, ld_c, qa, D(o_ctb), p->cmvn_nn, D(o_cslot), any_spk_nn ? p->spk_nn : nullptr, any_spk_nn ? D(o_cspkn) : nullptr);
+      LaunchOnlineCmvn(cmvn_nnet_dev_, gc, p->raw, p->nn_in, ld_c, qa, D(o.ctb), p->cmvn_nn, D(o.cslot), spk_nn ? p->spk_nn : nullptr, spk_nn ? D(o.cspkn) : nullptr);
   }
-  TM_MARK(tma);
-  // ---------------------------------------------------------------- 3. iVectors of the new chunks
-  auto falloc = [&](int rows, int ld) { return arena.AllocT<float>(((size_t)rows + 2 * guard) * ld) + (size_t)guard * ld; };
-  if (nI > 0) {
-    float *seg_raw = falloc(rowsI, ld_c), *seg_cm = falloc(rowsI, ld_c), *lda_raw = falloc(rowsI, ld_l), *lda_norm = falloc(rowsI, ld_l);
-    LaunchCopyRows(p->raw, ld_c, D(o_isrc), seg_raw, ld_c, nullptr, rowsI, C, qa);
-    LaunchCopyRows(p->cm, ld_c, D(o_isrc), seg_cm, ld_c, nullptr, rowsI, C, qa);
-    BatchGeom g;
-    g.n_utts = nI; g.L = sl; g.R = sr; g.total_rows = rowsI; g.guard = guard;
-    g.d_num_frames = D(o_iT); g.d_row_base = D(o_irb);
-    int *ru = arena.AllocT<int>(rowsI + 8), *rt = arena.AllocT<int>(rowsI + 8);
-    LaunchRowGeometry(nI, rowsI, sl, D(o_irb), nullptr, ru, rt, nullptr, qa);
-    g.d_row_utt = ru; g.d_row_t = rt;
-    LaunchGemm(MakeGemm(LdaPlan(ld_c), {seg_raw}, {ld_c}, nullptr, 0, lda_raw, ld_l, 1), rowsI, ru, qa);
-    LaunchGemm(MakeGemm(LdaPlan(ld_c), {seg_cm}, {ld_c}, nullptr, 0, lda_norm, ld_l, 1), rowsI, ru, qa);
-    int *post_idx = arena.AllocT<int>((size_t)rowsI * nsel + 64);
-    float *post_w = arena.AllocT<float>((size_t)rowsI * nsel + 64);
-    LaunchUbmPosteriors(ivec_dev_, g, lda_norm, ld_l, post_idx, post_w, qa);
-    // the estimator's steps on their own queue, behind the posteriors
-    RS_HIP(hipEventRecord(p->ev_f[par], qa));
-    RS_HIP(hipStreamWaitEvent(qi, p->ev_f[par], 0));
-    TM_MARK(tmi);
-    const float *stats_feats = fc_.ie.online_cmvn_iextractor ? lda_norm : lda_raw;
-    if (Di <= 128) {
-      // the new chunks of all streams: statistics side by side, then one launch that walks every stream's chunks in order on its
-      // estimator state in place (round 4: state rows gathered, a five-launch chain per chunk, state rows scattered)
-      IvecChunkChain(arena, g, nI, max_new_chunks, stats_feats, ld_l, post_idx, post_w, D(o_sfb), D(o_sfe), D(o_sor), D(o_sac), p->lin, p->quad, p->numf,
-                     p->x, D(o_islot), p->ivec, ld_i, qi);
-    } else {
-      double *gamma = arena.AllocT<double>((size_t)nI * G), *wfeats = arena.AllocT<double>((size_t)nI * G * Dl);
-      double *linear = arena.AllocT<double>((size_t)nI * Di), *quad = arena.AllocT<double>((size_t)nI * usz);
-      double *numf = arena.AllocT<double>(nI), *x = arena.AllocT<double>((size_t)nI * Di);
-      double *scratch = arena.AllocT<double>(IvecStatsScratchDoubles(ivec_dev_, nI));
-      // estimator state: slots -> dense, the steps, dense -> slots (one launch each way for the four arrays)
-      CopyRowsSet in_set{{{p->lin, linear, 2L * Di, 2 * Di}, {p->quad, quad, 2L * usz, 2 * usz}, {p->numf, numf, 2, 2}, {p->x, x, 2L * Di, 2 * Di}}, 4};
-      LaunchCopyRowsMulti(in_set, D(o_islot), nullptr, nI, qi);
-      for (int k = 0; k < max_new_chunks; k++) {
-        const size_t o = (size_t)k * nI;
-        LaunchIvecAccumulate(ivec_dev_, g, stats_feats, ld_l, post_idx, post_w, D(o_sfb) + o, D(o_sfe) + o, gamma, wfeats, true, qi);
-        LaunchIvecStats(ivec_dev_, nI, gamma, wfeats, linear, quad, numf, scratch, qi);
-        LaunchIvecSolve(ivec_dev_, nI, linear, quad, numf, x, p->ivec, ld_i, D(o_sor) + o, D(o_sac) + o, qi);
-      }
-      CopyRowsSet out_set{{{linear, p->lin, 2L * Di, 2 * Di}, {quad, p->quad, 2L * usz, 2 * usz}, {numf, p->numf, 2, 2}, {x, p->x, 2L * Di, 2 * Di}}, 4};
-      LaunchCopyRowsMulti(out_set, nullptr, D(o_islot), nI, qi);
-    }
-    TM_MARK(tmi);
-  }
-  TM_MARK(tma);
+  MarkIf(timed, tma);
+  if (plan.nI > 0) AdvanceIvectors(p, plan, set);
+  MarkIf(timed, tma);
   // the acoustic model waits for both: the features (qa) and, where there is an extractor, the iVectors (qi, itself behind qa)
   RS_HIP(hipEventRecord(p->ev_a[par], qa));
-  if (nI > 0) RS_HIP(hipEventRecord(p->ev_i[par], qi));
-  // ---------------------------------------------------------------- 4. acoustic model over the new chunks (+ context), 5. search
-  // Everything below queues on q / qc and needs nothing this thread computes later: a closure over values, run here by a finishing
-  // call and handed to the pool's issuing thread otherwise (StreamIssuer).  Buffers come out of the arena here, in this thread.
-  HOST_MARK(2);
-  std::vector<float *> bufp(nn.bufs.size(), nullptr);
-  std::vector<ActImage> imgs;
-  int *frame_rows = nullptr;
-  if (nN > 0) {
-    for (size_t b = 0; b < nn.bufs.size(); b++) bufp[b] = falloc(rowsN, buf_ld[b]);
-    imgs = AllocImages(arena, rowsN);
-    frame_rows = arena.AllocT<int>(framesN + 8);
+  if (plan.nI > 0) RS_HIP(hipEventRecord(p->ev_i[par], p->qi));
+}
+
+// 3. iVectors of the new chunks
+void Model::AdvanceIvectors(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set) {
+  const AdvancePlan::Offsets &o = plan.o;
+  const int C = fc_.mfcc.nceps, sl = fc_.ie.splice_left, sr = fc_.ie.splice_right;
+  const int Dl = fc_.ie.feat_dim(), Di = fc_.ie.ivector_dim(), G = fc_.ie.num_gauss(), nsel = fc_.ie.num_gselect, usz = Di * (Di + 1) / 2;
+  const int ld_c = p->ld_c, ld_l = RoundUp(std::max(Dl, 1), 4), ld_i = p->ld_i;
+  const int par = set.par, guard = set.guard, nI = plan.nI, rowsI = plan.rowsI, max_new_chunks = plan.max_new_chunks;
+  DeviceArena &arena = *set.arena;
+  hipStream_t qa = p->qa, qi = p->qi;
+  Timer *tmi = p->tm_i[par].get();
+  auto D = [&](size_t off) { return set.d_is + off; };
+  float *seg_raw = AllocGuarded(arena, rowsI, ld_c, guard), *seg_cm = AllocGuarded(arena, rowsI, ld_c, guard);
+  float *lda_raw = AllocGuarded(arena, rowsI, ld_l, guard), *lda_norm = AllocGuarded(arena, rowsI, ld_l, guard);
+  LaunchCopyRows(p->raw, ld_c, D(o.isrc), seg_raw, ld_c, nullptr, rowsI, C, qa);
+  LaunchCopyRows(p->cm, ld_c, D(o.isrc), seg_cm, ld_c, nullptr, rowsI, C, qa);
+  BatchGeom g;
+  g.n_utts = nI; g.L = sl; g.R = sr; g.total_rows = rowsI; g.guard = guard;
+  g.d_num_frames = D(o.iT); g.d_row_base = D(o.irb);
+  int *ru = arena.AllocT<int>(rowsI + 8), *rt = arena.AllocT<int>(rowsI + 8);
+  LaunchRowGeometry(nI, rowsI, sl, D(o.irb), nullptr, ru, rt, nullptr, qa);
+  g.d_row_utt = ru; g.d_row_t = rt;
+  LaunchGemm(MakeGemm(LdaPlan(ld_c), {seg_raw}, {ld_c}, nullptr, 0, lda_raw, ld_l, 1), rowsI, ru, qa);
+  LaunchGemm(MakeGemm(LdaPlan(ld_c), {seg_cm}, {ld_c}, nullptr, 0, lda_norm, ld_l, 1), rowsI, ru, qa);
+  int *post_idx = arena.AllocT<int>((size_t)rowsI * nsel + 64);
+  float *post_w = arena.AllocT<float>((size_t)rowsI * nsel + 64);
+  LaunchUbmPosteriors(ivec_dev_, g, lda_norm, ld_l, post_idx, post_w, qa);
+  // the estimator's steps on their own queue, behind the posteriors
+  RS_HIP(hipEventRecord(p->ev_f[par], qa));
+  RS_HIP(hipStreamWaitEvent(qi, p->ev_f[par], 0));
+  MarkIf(set.timed, tmi);
+  const float *stats_feats = fc_.ie.online_cmvn_iextractor ? lda_norm : lda_raw;
+  if (Di <= 128) {
+    // the new chunks of all streams: statistics side by side, then one launch that walks every stream's chunks in order on its
+    // estimator state in place (round 4: state rows gathered, a five-launch chain per chunk, state rows scattered)
+    IvecChunkChain(arena, g, nI, max_new_chunks, stats_feats, ld_l, post_idx, post_w, D(o.sfb), D(o.sfe), D(o.sor), D(o.sac), p->lin, p->quad, p->numf,
+                   p->x, D(o.islot), p->ivec, ld_i, qi);
+  } else {
+    double *gamma = arena.AllocT<double>((size_t)nI * G), *wfeats = arena.AllocT<double>((size_t)nI * G * Dl);
+    double *linear = arena.AllocT<double>((size_t)nI * Di), *quad = arena.AllocT<double>((size_t)nI * usz);
+    double *numf = arena.AllocT<double>(nI), *x = arena.AllocT<double>((size_t)nI * Di);
+    double *scratch = arena.AllocT<double>(IvecStatsScratchDoubles(ivec_dev_, nI));
+    // estimator state: slots -> dense, the steps, dense -> slots (one launch each way for the four arrays)
+    CopyRowsSet in_set{{{p->lin, linear, 2L * Di, 2 * Di}, {p->quad, quad, 2L * usz, 2 * usz}, {p->numf, numf, 2, 2}, {p->x, x, 2L * Di, 2 * Di}}, 4};
+    LaunchCopyRowsMulti(in_set, D(o.islot), nullptr, nI, qi);
+    for (int k = 0; k < max_new_chunks; k++) {
+      const size_t at = (size_t)k * nI;
+      LaunchIvecAccumulate(ivec_dev_, g, stats_feats, ld_l, post_idx, post_w, D(o.sfb) + at, D(o.sfe) + at, gamma, wfeats, true, qi);
+      LaunchIvecStats(ivec_dev_, nI, gamma, wfeats, linear, quad, numf, scratch, qi);
+      LaunchIvecSolve(ivec_dev_, nI, linear, quad, numf, x, p->ivec, ld_i, D(o.sor) + at, D(o.sac) + at, qi);
+    }
+    CopyRowsSet out_set{{{linear, p->lin, 2L * Di, 2 * Di}, {quad, p->quad, 2L * usz, 2 * usz}, {numf, p->numf, 2, 2}, {x, p->x, 2L * Di, 2 * Di}}, 4};
+    LaunchCopyRowsMulti(out_set, nullptr, D(o.islot), nI, qi);
   }
+  MarkIf(set.timed, tmi);
+}
+
+// What the search of an advance (and the collection of a finish) sees: every stream of the call, its decoder frames in the pool
+static BatchGeom SearchGeom(const AdvancePlan &plan, const int *d_is) {
   BatchGeom gd;
-  gd.n_utts = n; gd.max_frames = maxT; gd.d_num_frames = D(o_dT); gd.d_row_base = D(o_drb);
-  DenseWork dw;
+  gd.n_utts = plan.n; gd.max_frames = plan.maxT; gd.d_num_frames = d_is + plan.o.dT; gd.d_row_base = d_is + plan.o.drb;
+  return gd;
+}
+
+// 4. the acoustic model over the new chunks (+ context), 5. the search: buffers out of the arena here, the launches as a StagesBC
+void Model::AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set, bool final, bool reg_windows, SearchPlan *sp) {
+  const Nnet &nn = am_.nnet;
+  const AdvancePlan::Offsets &o = plan.o;
+  DeviceArena &arena = *set.arena;
+  auto D = [&](size_t off) { return set.d_is + off; };
+  StagesBC job;
+  job.p = p; job.arena = &arena; job.par = set.par;
+  job.final = final; job.timed = set.timed; job.reg_windows = reg_windows; job.exact = exact_gemm_.load();
+  job.ovf_dev = static_cast<DecodeContext *>(p->cx)->gemm_ovf_dev;
+  job.nI = plan.nI; job.nN = plan.nN; job.rowsN = plan.rowsN; job.framesN = plan.framesN; job.maxTn = std::max(plan.maxTn, 1); job.n = plan.n;
+  job.n_sub = (int)plan.n_lldst.size(); job.have_sub = !plan.n_llsrc.empty();
+  job.d_nsrc = D(o.nsrc); job.d_nfb = D(o.nfb); job.d_nrb = D(o.nrb); job.d_nriv = D(o.nriv); job.d_nll = D(o.nll); job.d_nlls = D(o.nlls); job.d_slots = D(o.slots);
+  job.bufp.assign(nn.bufs.size(), nullptr);
+  job.buf_ld = set.buf_ld;
+  if (plan.nN > 0) {
+    for (size_t b = 0; b < nn.bufs.size(); b++) job.bufp[b] = AllocGuarded(arena, plan.rowsN, set.buf_ld[b], set.guard);
+    job.imgs = AllocImages(arena, plan.rowsN);
+    job.frame_rows = arena.AllocT<int>(plan.framesN + 8);
+  }
+  job.gd = SearchGeom(plan, set.d_is);
+  DenseWork &dw = job.dw;
   std::memset(&dw, 0, sizeof(dw));
   dw.bp = p->bp; dw.frame_info = p->finfo; dw.state_cost = p->dec_state; dw.counters = p->dec_ctr;
-  dw.win_begin = D(o_wb); dw.win_end = D(o_we); dw.win_final = D(o_wf); dw.pool_row = D(o_row0); dw.slot = D(o_slots);
-  DecodeOptsDev dopts;
+  dw.win_begin = D(o.wb); dw.win_end = D(o.we); dw.win_final = D(o.wf); dw.pool_row = D(o.row0); dw.slot = D(o.slots);
+  DecodeOptsDev &dopts = job.dopts;
   dopts.beam = opts_.beam; dopts.lattice_beam = opts_.lattice_beam; dopts.beam_delta = opts_.beam_delta;
   dopts.max_active = opts_.max_active; dopts.min_active = opts_.min_active;
   dopts.exact_order = ExactOrder() ? 1 : 0;
-  {
+  job.sp = sp;
+  if (final || !p->use_issuer) IssueStagesBC(job);
+  else p->issuer.Submit([this, job = std::move(job)] { IssueStagesBC(job); });
+}
+
+void Model::IssueStagesBC(const StagesBC &j) {
+  StreamPool *p = j.p;
+  const Nnet &nn = am_.nnet;
+  const int C = fc_.mfcc.nceps, P = nn.output_dim, fsf = opts_.frame_subsampling_factor, par = j.par;
+  hipStream_t q = p->q, qc = p->qc;
+  Timer *tb = p->tm_b[par].get(), *tc = p->tm_c[par].get();
+  SampleGemmMode(j.exact, j.ovf_dev);      // (thread-local: the issuing thread's launches run in the mode this advance was planned in)
+  RS_HIP(hipStreamWaitEvent(q, p->ev_a[par], 0));
+  if (j.nI > 0) RS_HIP(hipStreamWaitEvent(q, p->ev_i[par], 0));
+  MarkIf(j.timed, tb);
+  if (j.nN > 0) {
     const float *nn_src = fc_.use_cmvn ? p->nn_in : p->raw;
-    const int *d_nsrc = D(o_nsrc), *d_nfb = D(o_nfb), *d_nrb = D(o_nrb), *d_nriv = D(o_nriv), *d_nll = D(o_nll), *d_nlls = D(o_nlls), *d_slots = D(o_slots);
-    const int n_sub = (int)n_lldst.size();
-    const bool have_sub = !n_llsrc.empty(), exact_now = exact_gemm_.load();
-    int *const ovf_dev = cx.gemm_ovf_dev;
-    Timer *const tb = &tmb, *const tc = &tmc;
-    SearchPlan *const spp = &sp;            // (a finishing call only; it runs the closure itself)
-    DeviceArena *const arp = &arena;
-    hipEvent_t ev_a = p->ev_a[par], ev_i = p->ev_i[par], ev_b = p->ev_b[par], ev_done = p->ev_done[par];
-    const int maxTn_c = std::max(maxTn, 1);
-    const Nnet *const nnp = &nn;             // (a pointer: [=] on the reference would copy the network)
-    auto issue_bc = [=]() {
-      SampleGemmMode(exact_now, ovf_dev);      // (thread-local: the issuing thread's launches run in the mode this advance was planned in)
-      RS_HIP(hipStreamWaitEvent(q, ev_a, 0));
-      if (nI > 0) RS_HIP(hipStreamWaitEvent(q, ev_i, 0));
-      if (timed) tb->Mark();
-      if (nN > 0) {
-        LaunchCopyRows(nn_src, ld_c, d_nsrc, bufp[nnp->input_buf], buf_ld[nnp->input_buf], nullptr, rowsN, C, q);
-        LaunchFrameRows(nN, nN, framesN, L_, maxTn_c, d_nfb, d_nrb, frame_rows, q);
-        RowMaps row_maps;
-        row_maps.maps.push_back({0, 0, frame_rows, framesN});
-        if (fsf > 1 && have_sub) row_maps.maps.push_back({0, 0, d_nlls, n_sub, 0, fsf});      // the layers only the decoder's frames read
-        RunNnet(bufp, buf_ld, p->ivec, ld_i, d_nriv, rowsN, row_maps, 1, 0, nnp->ops.size(), q, &imgs);
-        if (fsf == 1) LaunchCopyRows(bufp[nnp->output_buf], buf_ld[nnp->output_buf], frame_rows, p->ll, p->ld_ll, d_nll, framesN, P, q);
-        else if (n_sub > 0) LaunchCopyRows(bufp[nnp->output_buf], buf_ld[nnp->output_buf], d_nlls, p->ll, p->ld_ll, d_nll, n_sub, P, q);
-      }
-      if (timed) tb->Mark();
-      // the search on its own queue: the next advance's acoustic model does not wait for it
-      RS_HIP(hipEventRecord(ev_b, q));
-      RS_HIP(hipStreamWaitEvent(qc, ev_b, 0));
-      if (timed) tc->Mark();
-      if (final) AllocSearch(spp, *arp, qc, /*pooled_frames=*/reg_windows);
-      if (reg_windows && (final || nN > 0)) {      // (an advance without new log-likelihood rows has nothing to search)
-        DenseWork dw2 = dw;
-        if (final) { dw2 = spp->dw; dw2.bp = dw.bp; dw2.frame_info = dw.frame_info; dw2.state_cost = dw.state_cost; dw2.counters = dw.counters;
-                     dw2.win_begin = dw.win_begin; dw2.win_end = dw.win_end; dw2.win_final = dw.win_final; dw2.pool_row = dw.pool_row; dw2.slot = dw.slot; }
-        LaunchDecodeReg(hclg_dev_, reg_dev_, dopts, gd, p->ll, p->ld_ll, dw2, 0, 0, qc, final);
-        if (final) LaunchCopyRows(p->dec_ctr, 16, d_slots, spp->w.counters, 16, nullptr, n, 16, qc);
-      } else if (final) {
-        LaunchSearch(spp, *arp, gd, p->ll, p->ld_ll, qc);
-      }
-      if (timed) tc->Mark();
-      RS_HIP(hipEventRecord(ev_done, qc));
-      const hipError_t le = hipGetLastError();      // (per thread: a failed launch of this closure is seen here)
-      if (le != hipSuccess) Fail(std::string("a kernel launch failed: ") + hipGetErrorString(le));
-    };
-    if (final || !p->use_issuer) issue_bc();
-    else p->issuer.Submit(issue_bc);
+    LaunchCopyRows(nn_src, p->ld_c, j.d_nsrc, j.bufp[nn.input_buf], j.buf_ld[nn.input_buf], nullptr, j.rowsN, C, q);
+    LaunchFrameRows(j.nN, j.nN, j.framesN, L_, j.maxTn, j.d_nfb, j.d_nrb, j.frame_rows, q);
+    RowMaps row_maps;
+    row_maps.maps.push_back({0, 0, j.frame_rows, j.framesN});
+    if (fsf > 1 && j.have_sub) row_maps.maps.push_back({0, 0, j.d_nlls, j.n_sub, 0, fsf});      // the layers only the decoder's frames read
+    RunNnet(j.bufp, j.buf_ld, p->ivec, p->ld_i, j.d_nriv, j.rowsN, row_maps, 1, 0, nn.ops.size(), q, &j.imgs);
+    if (fsf == 1) LaunchCopyRows(j.bufp[nn.output_buf], j.buf_ld[nn.output_buf], j.frame_rows, p->ll, p->ld_ll, j.d_nll, j.framesN, P, q);
+    else if (j.n_sub > 0) LaunchCopyRows(j.bufp[nn.output_buf], j.buf_ld[nn.output_buf], j.d_nlls, p->ll, p->ld_ll, j.d_nll, j.n_sub, P, q);
   }
-  HOST_MARK(3);
-  // ---------------------------------------------------------------- host bookkeeping
-  HOST_MARK(4);
-  for (int i = 0; i < n; i++) {
+  MarkIf(j.timed, tb);
+  // the search on its own queue: the next advance's acoustic model does not wait for it
+  RS_HIP(hipEventRecord(p->ev_b[par], q));
+  RS_HIP(hipStreamWaitEvent(qc, p->ev_b[par], 0));
+  MarkIf(j.timed, tc);
+  if (j.final) AllocSearch(j.sp, *j.arena, qc, /*pooled_frames=*/j.reg_windows);
+  if (j.reg_windows && (j.final || j.nN > 0)) {      // (an advance without new log-likelihood rows has nothing to search)
+    DenseWork dw2 = j.dw;
+    if (j.final) { dw2 = j.sp->dw; dw2.bp = j.dw.bp; dw2.frame_info = j.dw.frame_info; dw2.state_cost = j.dw.state_cost; dw2.counters = j.dw.counters;
+                   dw2.win_begin = j.dw.win_begin; dw2.win_end = j.dw.win_end; dw2.win_final = j.dw.win_final; dw2.pool_row = j.dw.pool_row; dw2.slot = j.dw.slot; }
+    LaunchDecodeReg(hclg_dev_, reg_dev_, j.dopts, j.gd, p->ll, p->ld_ll, dw2, 0, 0, qc, j.final);
+    if (j.final) LaunchCopyRows(p->dec_ctr, 16, j.d_slots, j.sp->w.counters, 16, nullptr, j.n, 16, qc);
+  } else if (j.final) {
+    LaunchSearch(j.sp, *j.arena, j.gd, p->ll, p->ld_ll, qc);
+  }
+  MarkIf(j.timed, tc);
+  RS_HIP(hipEventRecord(p->ev_done[par], qc));
+  const hipError_t le = hipGetLastError();      // (per thread: a failed launch of this job is seen here)
+  if (le != hipSuccess) Fail(std::string("a kernel launch failed: ") + hipGetErrorString(le));
+}
+
+// What the advance did, into the streams: the schedule's cursor, the frames done per stage; samples no longer needed go
+void Model::AdvanceBookkeeping(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, int par, bool searched) {
+  const int shift = fc_.mfcc.shift, fsf = opts_.frame_subsampling_factor;
+  for (int i = 0; i < plan.n; i++) {
     rs_stream &st = *streams[i];
-    const Plan &a = pl[i];
+    const StreamAdvance &a = plan.pl[i];
+    st.sched = a.sched;
     st.frames_mfcc = a.avail;
     st.stats_done = a.sb;
     st.ll_done = a.t1;
-    if (reg_windows && (final || nN > 0)) { st.frames_decoded = dec_frames(a.t1); st.dec_started = true; }      // (the search was launched)
+    if (searched) { st.frames_decoded = (a.t1 + fsf - 1) / fsf; st.dec_started = true; }
     // samples before the first frame that is not complete yet are not needed again (online-feature.cc:186-203)
     const long keep_from = (long)a.avail * shift;
     if (!st.keep_pcm && keep_from > st.pcm_start) {
@@ -1005,50 +922,47 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
       st.pcm_start = keep_from;
     }
   }
-  p->pending[par] = true;         // (its done event is recorded by the closure above)
+  p->pending[par] = true;         // (its done event is recorded by the StagesBC)
   p->n_adv++;
-  if (!final) {
-    // No wait here: the next advance is planned and issued while this one runs.  What it did on the device is accounted for --
-    // and a device error of it reported -- by whichever later call of this model waits for it.
-    if (p->sync_each) StreamsDrain(p, nullptr);
-    p->stage_ms[6] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    return;
-  }
+}
+
+// The end of a finishing call: every advance in flight waited for, results, intermediates, timings
+void Model::AdvanceFinish(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, const AdvanceSet &set, SearchPlan &sp, bool flush, int nbest,
+                          float lat_scale, std::chrono::steady_clock::time_point wall0, Result *res) {
+  const Nnet &nn = am_.nnet;
+  const bool has_iv = fc_.ie.present;
+  const int C = fc_.mfcc.nceps, P = nn.output_dim, chunk = p->chunk, fsf = opts_.frame_subsampling_factor, Di = has_iv ? fc_.ie.ivector_dim() : 0;
+  const int n = plan.n, par = set.par, ld_c = p->ld_c, ld_i = p->ld_i;
+  hipStream_t qc = p->qc;
   float own[4] = {0.f, 0.f, 0.f, 0.f};
-  {
-    // every earlier advance first (their time is the stream's, not this call's), then this one
-    for (int k = 1; k < StreamPool::kDepth; k++) {
-      const int other = (par + k) % StreamPool::kDepth;       // oldest first
-      if (!p->pending[other]) continue;
-      RS_HIP(hipEventSynchronize(p->ev_done[other]));
-      p->pending[other] = false;
-      p->Account(other, nullptr);
-    }
-    RS_HIP(hipEventSynchronize(p->ev_done[par]));
-    p->pending[par] = false;
-    p->Account(par, own);
-    StreamsCheckRange();
+  // every earlier advance first (their time is the stream's, not this call's), then this one
+  for (int k = 1; k <= StreamPool::kDepth; k++) {
+    const int other = (par + k) % StreamPool::kDepth;       // oldest first; k = kDepth: this call's own
+    if (!p->pending[other]) continue;
+    RS_HIP(hipEventSynchronize(p->ev_done[other]));
+    p->pending[other] = false;
+    p->Account(other, other == par ? own : nullptr);
   }
-  // ---------------------------------------------------------------- results
+  StreamsCheckRange();
   res->utts.resize(n);
-  for (int i = 0; i < n; i++) res->utts[i].num_frames = avails[i];
+  for (int i = 0; i < n; i++) res->utts[i].num_frames = plan.avails[i];
   Timer tmr(qc);
   tmr.Mark();
-  CollectResults(sp, cx, par, gd, avails.data(), p->ll, p->ld_ll, nbest, lat_scale, qc, res->utts.data(), res->timings);
+  CollectResults(sp, *static_cast<DecodeContext *>(p->cx), par, SearchGeom(plan, set.d_is), plan.avails.data(), p->ll, p->ld_ll, nbest, lat_scale, qc, res->utts.data(),
+                 res->timings);
   tmr.Mark();
   if (opts_.keep_intermediates) {
     const float *fin = fc_.use_cmvn ? p->nn_in : p->raw;
     for (int i = 0; i < n; i++) {
       UttResult &ur = res->utts[i];
       const rs_stream &st = *streams[i];
-      const int T = flush ? pl[i].avail : pl[i].t1, nch = std::max((T + chunk - 1) / chunk, 1);
+      const int T = flush ? plan.pl[i].avail : plan.pl[i].t1, nch = std::max((T + chunk - 1) / chunk, 1), T_dec = (T + fsf - 1) / fsf;
       ur.feat_dim = C; ur.num_pdfs = P; ur.ivec_dim = Di; ur.ivec_rows = has_iv ? nch : 0;
       if (T == 0) continue;
       ur.feats.resize((size_t)T * C);
-      ur.loglikes.resize((size_t)dec_frames(T) * P);
+      ur.loglikes.resize((size_t)T_dec * P);
       RS_HIP(hipMemcpy2D(ur.feats.data(), sizeof(float) * C, fin + (size_t)st.row0 * ld_c, sizeof(float) * ld_c, sizeof(float) * C, T, hipMemcpyDeviceToHost));
-      RS_HIP(hipMemcpy2D(ur.loglikes.data(), sizeof(float) * P, p->ll + (size_t)st.row0 * p->ld_ll, sizeof(float) * p->ld_ll, sizeof(float) * P, dec_frames(T),
-                         hipMemcpyDeviceToHost));
+      RS_HIP(hipMemcpy2D(ur.loglikes.data(), sizeof(float) * P, p->ll + (size_t)st.row0 * p->ld_ll, sizeof(float) * p->ld_ll, sizeof(float) * P, T_dec, hipMemcpyDeviceToHost));
       if (has_iv) {
         ur.ivector.resize((size_t)nch * Di);
         RS_HIP(hipMemcpy2D(ur.ivector.data(), sizeof(float) * Di, p->ivec + (size_t)(st.row0 / chunk) * ld_i, sizeof(float) * ld_i, sizeof(float) * Di, nch,
@@ -1058,7 +972,7 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
   }
   { const hipError_t le = hipGetLastError(); if (le != hipSuccess) Fail(std::string("a kernel launch failed: ") + hipGetErrorString(le)); }
   // stage times of the whole stream(s): this call plus the advances since the previous finish on this model; [7] = this call alone
-  res->timings[7] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  res->timings[7] = MsSince(wall0);
   for (int k = 0; k < 4; k++) res->timings[k + 1] = p->stage_ms[k + 1];
   res->timings[5] = tmr.Ms(0, 1);
   res->timings[6] = p->stage_ms[6] + res->timings[7];
@@ -1071,6 +985,47 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
     for (float &v : p->host_ms) v = 0.f;
   }
   for (float &v : p->stage_ms) v = 0.f;
+}
+
+// queues: qa = features + UBM posteriors, qi = the iVector steps (stage A); q = acoustic model, qc = search (stages B and C, behind
+// stage A's events).  no_flush (rs_streams_finalize): the end of the streams as the reference reaches it after an endpoint --
+// FinalizeDecoding() without InputFinished() (online2-wav-nnet3-latgen-faster.cc:270-278): the ticks completed are scheduled like by
+// any advance, nothing is flushed, and the final stage runs over the decoder frames those ticks give
+void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, int nbest, float lat_scale, Result *res, bool every_tick, bool no_flush) {
+  const bool flush = final && !no_flush;
+  StreamPool *p = Pool();
+  RS_HIP(hipSetDevice(opts_.device_id));
+  if (!final && !every_tick && LeftToTheNextCall(p, streams, n)) return;
+  DecodeContext &cx = *static_cast<DecodeContext *>(p->cx);
+  AdvanceSet set;
+  set.par = AdvanceTakeSet(p, final);
+  set.arena = &cx.arena[set.par];
+  set.harena = &cx.host_arena[set.par];
+  SampleGemmMode(exact_gemm_.load(), cx.gemm_ovf_dev);
+  HostClock clock;
+  const auto wall0 = clock.last;
+  AdvancePlan &plan = p->plans[set.par];
+  AdvancePlanStreams(p, streams, n, flush, final, &plan);
+  SearchPlan sp;
+  const size_t search_bytes = final ? PlanSearch(n, plan.maxT, nbest, lat_scale, &sp) : 0;
+  const bool reg_windows = p->reg && !(final && sp.want_lattice);
+  clock.Mark(&p->host_ms[0]);
+  AdvanceUpload(p, streams, plan, search_bytes, final, &set);
+  clock.Mark(&p->host_ms[1]);
+  AdvanceStageA(p, plan, set);
+  clock.Mark(&p->host_ms[2]);
+  AdvanceStagesBC(p, plan, set, final, reg_windows, &sp);
+  clock.Mark(&p->host_ms[3]);
+  clock.Mark(&p->host_ms[4]);
+  AdvanceBookkeeping(p, streams, plan, set.par, /*searched=*/reg_windows && (final || plan.nN > 0));
+  if (!final) {
+    // No wait here: the next advance is planned and issued while this one runs.  What it did on the device is accounted for --
+    // and a device error of it reported -- by whichever later call of this model waits for it.
+    if (p->sync_each) StreamsDrain(p, nullptr);
+    p->stage_ms[6] += MsSince(wall0);
+    return;
+  }
+  AdvanceFinish(p, streams, plan, set, sp, flush, nbest, lat_scale, wall0, res);
 }
 
 // ---------------------------------------------------------------------------------------------------------- partial results
@@ -1100,7 +1055,7 @@ void Model::StreamsPartialLocked(rs_stream *const *streams, int n, Result *res) 
   StreamPool *p = Pool();
   RS_HIP(hipSetDevice(opts_.device_id));
   bool more = false;
-  for (int i = 0; i < n; i++) more = more || streams[i]->n_samples / 1024 > streams[i]->ticks_done;
+  for (int i = 0; i < n; i++) more = more || streams[i]->n_samples / kTickSamples > streams[i]->sched.ticks_done;
   if (more) StreamsAdvanceLocked(streams, n, /*final=*/false, 1, 1.0f, nullptr, /*every_tick=*/true);
   StreamsDrain(p, nullptr);        // every advance has finished: the arena sets are free, the frontier and rows are in place
   const int fsf = opts_.frame_subsampling_factor, S = p->S;
@@ -1234,7 +1189,7 @@ void Model::StreamsEndpointLocked(rs_stream *const *streams, int n, const std::v
   StreamPool *p = Pool();
   RS_HIP(hipSetDevice(opts_.device_id));
   bool more = false;
-  for (int i = 0; i < n; i++) more = more || streams[i]->n_samples / 1024 > streams[i]->ticks_done;
+  for (int i = 0; i < n; i++) more = more || streams[i]->n_samples / kTickSamples > streams[i]->sched.ticks_done;
   if (more) StreamsAdvanceLocked(streams, n, /*final=*/false, 1, 1.0f, nullptr, /*every_tick=*/true);
   StreamsDrain(p, nullptr);        // every advance has finished: the arena sets are free, the frontier and rows are in place
   const int fsf = opts_.frame_subsampling_factor;

@@ -280,7 +280,7 @@ def _short_run_batch(V):
 
 def test_many_short_runs_under_wide_tiles(variants, monkeypatch):
     """Row lists whose runs hold one to three entries on the model with 128/160-row GEMM tiles: a tile of 128 list entries then
-    crosses a hundred utterance boundaries (span_of_runs, engine.cc).  Every utterance with frames is held to its golden -- in the
+    crosses a hundred utterance boundaries (SpanOfRuns, call_plan.cc).  Every utterance with frames is held to its golden -- in the
     kernels such a call takes by itself and with the wide tiles forced on every launch (RS_GEMM_B3J=2, both tile heights), which a
     batch a few times larger takes by itself -- and the forced runs equal the first bit for bit.  512 copies of the one-frame clip."""
     V = variants("V8")
