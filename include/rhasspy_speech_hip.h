@@ -105,7 +105,10 @@ int rs_model_load(const char *model_dir, const char *graph_dir, const rs_decode_
 int rs_model_to_device(rs_model *model);
 void rs_model_free(rs_model *model);
 /* Writes a one-line-per-item description of the parsed model (dims, layer plan, graph size) into buf;
- * returns the number of bytes needed (like snprintf). */
+ * returns the number of bytes needed (like snprintf).  Two lines are state, not structure: `layer_gemm:` and
+ *   arenas: device blocks=B bytes=N allocations=A; host blocks=B bytes=N allocations=A
+ * summed over the model's decode contexts: the blocks and bytes their per-call arenas hold now, and the hipMalloc / hipHostMalloc
+ * calls they have made since the model was loaded.  `allocations` stands still once every context has seen its largest call twice. */
 int rs_model_describe(const rs_model *model, char *buf, size_t len);
 /* The check the reference makes when a waveform arrives (OnlineGenericBaseFeature::MaybeCreateResampler, feat/online-feature.cc:
  * 86-101; online2-wav-nnet3-latgen-faster.cc:233 hands it WaveData::SampFreq()): RS_OK when `sample_rate` is the model's

@@ -26,49 +26,23 @@ void HipCheck(hipError_t e, const char *what, const char *file, int line) {
   }
 }
 
-DeviceArena::~DeviceArena() { if (base_) (void)hipFree(base_); }
-
-void DeviceArena::Reserve(size_t bytes, hipStream_t s) {
-  if (bytes <= cap_) return;
-  if (base_) {
-    RS_HIP(hipStreamSynchronize(s));
-    RS_HIP(hipFree(base_));
-    base_ = nullptr;
-    cap_ = 0;
-  }
-  size_t want = bytes + bytes / 8 + (1u << 20);
-  RS_HIP(hipMalloc((void **)&base_, want));
-  RS_HIP(hipMemsetAsync(base_, 0, want, s));
-  cap_ = want;
-  used_ = 0;
+void *DeviceBlocks::Allocate(size_t bytes, hipStream_t s) {
+  void *p = nullptr;
+  RS_HIP(hipMalloc(&p, bytes));
+  hipError_t e = hipMemsetAsync(p, 0, bytes, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) (void)hipFree(p);
+  RS_HIP(e);
+  return p;
 }
+void DeviceBlocks::Synchronize(hipStream_t s) { RS_HIP(hipStreamSynchronize(s)); }
 
-HostArena::~HostArena() { for (auto &b : blocks_) (void)hipHostFree(b.first); }
-
-void *HostArena::Alloc(size_t bytes) {
-  // blocks are never freed before destruction, so pointers handed out earlier in the same call stay valid when a new
-  // block is appended; Reset() restarts from the first block
-  for (;;) {
-    if (cur_ < blocks_.size()) {
-      const size_t a = (used_ + 63) & ~(size_t)63;
-      if (a + bytes <= blocks_[cur_].second) { used_ = a + bytes; return blocks_[cur_].first + a; }
-      cur_++;
-      used_ = 0;
-      continue;
-    }
-    const size_t want = std::max(bytes + bytes / 4, (size_t)1 << 20);
-    char *p = nullptr;
-    RS_HIP(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-    blocks_.push_back({p, want});
-  }
+void *PinnedBlocks::Allocate(size_t bytes, hipStream_t) {
+  void *p = nullptr;
+  RS_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+  return p;
 }
-
-void *DeviceArena::Alloc(size_t bytes) {
-  size_t a = (used_ + 255) & ~(size_t)255;
-  if (a + bytes > cap_) Fail("internal error: device arena too small");
-  used_ = a + bytes;
-  return base_ + a;
-}
+void PinnedBlocks::Synchronize(hipStream_t s) { RS_HIP(hipStreamSynchronize(s)); }
 
 static int RoundUp(int x, int m) { return (x + m - 1) / m * m; }
 
@@ -933,6 +907,16 @@ std::string Model::Describe() const {
      << " (split-fp16 carries an operand row to 2^-22 of its largest element while that element lies in [2^-3, 65520): a row with |x| >= 65520, infinity"
         " or NaN, or a non-zero row whose largest |x| is below 2^-3, raises a flag and the call is repeated on the exact-FP32 kernels; the third such call"
         " makes them permanent)\n";
+  // (what the decode contexts' arenas hold; `allocations` stands still once the model has seen its largest call twice)
+  size_t dev[3] = {0, 0, 0}, host[3] = {0, 0, 0};
+  auto add = [&](const DecodeContext &c) {
+    for (const DeviceArena &a : c.arena) { dev[0] += a.blocks(); dev[1] += a.bytes(); dev[2] += a.allocations(); }
+    for (const HostArena &a : c.host_arena) { host[0] += a.blocks(); host[1] += a.bytes(); host[2] += a.allocations(); }
+  };
+  for (auto &c : ctx_) add(*c);
+  { std::lock_guard<std::mutex> lk(pool_mu_); if (stream_ctx_) add(*stream_ctx_); }
+  os << "arenas: device blocks=" << dev[0] << " bytes=" << dev[1] << " allocations=" << dev[2] << "; host blocks=" << host[0] << " bytes=" << host[1]
+     << " allocations=" << host[2] << "\n";
   return os.str();
 }
 
@@ -1151,14 +1135,6 @@ std::unique_ptr<Result> Model::DecodeInContext(DecodeContext &cx, const int16_t 
   return res;
 }
 
-size_t Model::ImageBytes(int rows) const {
-  size_t b = 0;
-  const int guard = RoundUp(L_ + R_ + 8, 32);
-  for (size_t i = 0; i < buf_image_.size(); i++)
-    if (buf_image_[i]) b += kActImageParts * ActImagePartBytes(rows, guard, am_.nnet.bufs[i].dim) + 1024;
-  return b;
-}
-
 std::vector<ActImage> Model::AllocImages(DeviceArena &arena, int rows) const {
   std::vector<ActImage> imgs(buf_image_.size(), ActImage{nullptr, 0, 0, 0});
   const int guard = RoundUp(L_ + R_ + 8, 32);
@@ -1316,10 +1292,6 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
 
 // ------------------------------------------------------------------------------------------------ online iVector estimator, chunk chain
 static int IvecChainGroup(int n, int K) { return std::max(1, std::min(K, 512 / std::max(n, 1))); }      // chunks whose statistics are computed side by side
-size_t Model::IvecChunkChainBytes(const IvecDev &iv, int n, int K) {
-  const size_t P = (size_t)IvecChainGroup(n, K) * n, Di = iv.ivec_dim, usz = Di * (Di + 1) / 2;
-  return P * ((size_t)iv.num_gauss * 8 + (size_t)iv.num_gauss * iv.feat_dim * 8 + (Di + usz + 1) * 8) + IvecStatsScratchDoubles(iv, (int)P) * 8 + 4096;
-}
 void Model::IvecChunkChain(DeviceArena &arena, const BatchGeom &g, int n, int K, const float *stats_feats, int ld_l, const int *post_idx, const float *post_w,
                            const int *d_fb, const int *d_fe, const int *d_or, const int *d_ac, double *lin, double *quad, double *numf, double *x,
                            const int *slot, float *ivec_out, int ld_i, hipStream_t s) const {
@@ -1348,9 +1320,9 @@ void Model::IvecChunkChain(DeviceArena &arena, const BatchGeom &g, int n, int K,
 }
 
 // ------------------------------------------------------------------------------------------------ search
-// Which search kernel a call runs and the work buffers it needs (all from the call's arena).  Shared by the batch path
-// (DecodeGroup) and the end of a stream (stream.cc), whose log-likelihoods live in the stream pool.
-size_t Model::PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only, bool token_lists) const {
+// Which search kernel a call runs, its token capacity and options; AllocSearch / LaunchSearch take the work buffers from the call's
+// arena.  Shared by the batch path (DecodeGroup) and the end of a stream (stream.cc), whose log-likelihoods live in the stream pool.
+void Model::PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only, bool token_lists) const {
   const int S = hclg_.num_states();
   sp->S = S; sp->n_utts = n_utts; sp->maxT = maxT; sp->max_words = 1024;
   // The reference un-scales the lattice's acoustic costs before lattice-to-nbest ranks its paths (online2-wav-nnet3-latgen-
@@ -1381,19 +1353,7 @@ size_t Model::PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, Searc
   sp->dopts.beam = opts_.beam; sp->dopts.lattice_beam = opts_.lattice_beam; sp->dopts.beam_delta = opts_.beam_delta;
   sp->dopts.max_active = opts_.max_active; sp->dopts.min_active = opts_.min_active;
   sp->dopts.exact_order = ExactOrder() ? 1 : 0;
-  size_t need = (size_t)n_utts * ((size_t)(maxT + 1) * 16 + (size_t)sp->max_words * 4 + 4 + 16 + 64) + 65536;      // results, counters, frame info
-  if (sp->use_dense)      // dense / register-resident search: back-pointer rows, path scratch, parked token costs
-    need += (size_t)n_utts * ((size_t)(maxT + 1) * S * 4 + (size_t)(maxT + 2) * 32 + (2 * (size_t)S + 4) * 4) + 4096;
-  if (sp->reg_lattice)    // ... the cost rows, the token lists made of them, LatticeKernel's two maps
-    need += (size_t)n_utts * ((size_t)(maxT + 1) * S * 4 + (size_t)sp->tok_cap * 16 + (size_t)(maxT + 2) * 4 + (size_t)S * 8) + 8192;
-  if (!sp->use_dense) {                  // token-list search: per-state tables, queues, the token arrays of every frame
-    need += (size_t)n_utts * ((size_t)S * (8 + 4 * 5) + (size_t)sp->tok_cap * 16 + (size_t)(maxT + 2) * 4) + 8192;
-    sp->use_hash = decoder_choice_ != 3 && DecodeLiveUsable(hclg_dev_);
-    if (sp->use_hash) need += (size_t)n_utts * ((size_t)DecodeLiveTableSize() * (8 + 4) + (size_t)DecodeLiveGlobalTable() * 4 + (size_t)DecodeLiveSlotCap() * 16 +
-                                                (size_t)kHashCandCap * 8 + (size_t)kLiveQueueCap * 2 * 20 + 4) + 16384;
-  }
-  if (sp->want_lattice) need += sizeof(float) * (size_t)n_utts * sp->tok_cap + 4096;                                // LatticeKernel's extra_cost
-  return need;
+  sp->use_hash = !sp->use_dense && decoder_choice_ != 3 && DecodeLiveUsable(hclg_dev_);      // token-list search: the live-state tables
 }
 
 void Model::AllocSearch(SearchPlan *sp, DeviceArena &arena_, hipStream_t s, bool pooled_frames) const {
@@ -1724,7 +1684,7 @@ void Model::BatchFrames(const int64_t *sample_offsets, BatchCall *b) const {
   }
   b->rows = b->row_base[n];
   b->guard = L_ + R_ + 8;
-  b->harena->Reset();
+  b->harena->Reset(b->s);
   if (b->streaming && fc_.ie.present) {
     b->row_ivec = b->harena->AllocT<int>(b->rows);
     PlanBatchSchedule(PlanCfg(), b->ns.data(), b->T.data(), b->row_base.data(), n, b->row_ivec, &b->sched);
@@ -1734,36 +1694,6 @@ void Model::BatchFrames(const int64_t *sample_offsets, BatchCall *b) const {
     for (int u = 0; u <= n; u++) b->sched.ivrow_base[u] = u;
   }
   b->n_ivrows = b->sched.ivrow_base[n];
-}
-
-// What the call takes from its arena (the search's share is planned here: *sp)
-size_t Model::BatchArenaBytes(BatchCall *b, int nbest, float lat_scale, SearchPlan *sp) const {
-  const Nnet &nn = am_.nnet;
-  const bool has_iv = fc_.ie.present;
-  const int n_utts = b->n_utts, rows = b->rows, guard = b->guard, fsf = opts_.frame_subsampling_factor, C = fc_.mfcc.nceps, P = nn.output_dim;
-  auto fbytes = [&](int ld) { return ((size_t)rows + 2 * guard) * ld * sizeof(float) + 512; };
-  size_t need = 0;
-  need += (sizeof(int64_t) + 4 * sizeof(int)) * (size_t)(n_utts + 2) + 3 * sizeof(int) * (size_t)rows + 4096;
-  need += sizeof(int) * ((size_t)b->frame_base[n_utts] + 8 * (size_t)n_utts + 64) + 1024;     // frame-row map
-  b->buf_ld.resize(nn.bufs.size());
-  for (size_t i = 0; i < nn.bufs.size(); i++) { b->buf_ld[i] = RoundUp(nn.bufs[i].dim, 4); need += fbytes(b->buf_ld[i]); }
-  need += ImageBytes(rows);
-  need += (size_t)nn.ops.size() * (sizeof(int) * ((size_t)rows + n_utts + 64) + 512);      // row lists per output extent
-  const int Dl = has_iv ? fc_.ie.feat_dim() : 0, Di = has_iv ? fc_.ie.ivector_dim() : 0, G = has_iv ? fc_.ie.num_gauss() : 0;
-  const int ld_c = RoundUp(C, 4), ld_l = RoundUp(std::max(Dl, 1), 4), ld_i = RoundUp(std::max(Di, 1), 4);
-  const int usz = Di * (Di + 1) / 2, nsel = has_iv ? fc_.ie.num_gselect : 0;
-  if (fc_.use_cmvn) need += fbytes(ld_c);
-  if (has_iv) {
-    need += fbytes(ld_c) + 2 * fbytes(ld_l);
-    need += (size_t)rows * nsel * 8 + 1024;
-    need += (size_t)n_utts * ((size_t)G * 8 + (size_t)G * Dl * 8 + (size_t)Di * 8 * 2 + (size_t)usz * 8 + 8) + (size_t)b->n_ivrows * ld_i * 4 + 8192 + 1024;
-    need += (size_t)b->sched.max_chunks * n_utts * 16 + 4096;
-    need += IvecStatsScratchDoubles(ivec_dev_, n_utts) * 8 + 1024;
-    if (b->streaming) need += IvecChunkChainBytes(ivec_dev_, n_utts, b->sched.max_chunks);
-  }
-  need += PlanSearch(n_utts, b->maxT_dec, nbest, lat_scale, sp);
-  if (fsf > 1) need += ((size_t)b->dec_base[n_utts] + 8) * RoundUp(P, 4) * sizeof(float) + (size_t)(b->dec_base[n_utts] + 3 * n_utts + 16) * sizeof(int) + 4096;
-  return need + 64 * 256;   // alignment slack
 }
 
 // ---- geometry on the device: ONE page-locked staging block -> one async copy, ONE launch that derives every per-row array on the
@@ -1824,9 +1754,10 @@ void Model::BatchSetupUpload(const int64_t *sample_offsets, BatchCall *b) {
 void Model::BatchFeatures(const int16_t *d_pcm, BatchCall *b) {
   const Nnet &nn = am_.nnet;
   hipStream_t s = b->s;
-  const int ld_c = RoundUp(fc_.mfcc.nceps, 4), in_ld = b->buf_ld[nn.input_buf];
+  b->buf_ld.resize(nn.bufs.size());
   b->bufp.assign(nn.bufs.size(), nullptr);
-  for (size_t i = 0; i < nn.bufs.size(); i++) b->bufp[i] = b->Rows(b->buf_ld[i]);
+  for (size_t i = 0; i < nn.bufs.size(); i++) { b->buf_ld[i] = RoundUp(nn.bufs[i].dim, 4); b->bufp[i] = b->Rows(b->buf_ld[i]); }
+  const int ld_c = RoundUp(fc_.mfcc.nceps, 4), in_ld = b->buf_ld[nn.input_buf];
   b->imgs = AllocImages(*b->arena, b->rows);
   b->raw = b->bufp[nn.input_buf];
   if (fc_.use_cmvn) {
@@ -1968,9 +1899,8 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   BatchFrames(sample_offsets, &b);
   for (int u = 0; u < n_utts; u++) out_utts[u].num_frames = b.T_dec[u];
   SearchPlan sp;
-  const size_t need = BatchArenaBytes(&b, nbest, lat_scale, &sp);
-  b.arena->Reserve(need + (1u << 20), s);
-  b.arena->Reset();
+  PlanSearch(n_utts, b.maxT_dec, nbest, lat_scale, &sp);
+  b.arena->Reset(s);
   // The last layer and the search can be pipelined over time slabs when the search is the register-resident kernel: the
   // output GEMM of slab k+1 (MFMA-bound) runs while slab k is searched (latency-bound) on a second, high-priority stream.
   // Measured on the bench batch: 5.07 -> 4.97 ms with 3 slabs -- the search runs at half speed while it shares the CUs

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/rhasspy_speech_hip.h"
+#include "arena.h"
 #include "call_plan.h"
 #include "kernels.h"
 #include "lattice.h"
@@ -25,32 +26,27 @@ struct DeviceError : Error {
 void HipCheck(hipError_t e, const char *what, const char *file, int line);
 #define RS_HIP(x) ::rs::HipCheck((x), #x, __FILE__, __LINE__)
 
-// Grow-only device arena; reset at the start of every batch (no hipMalloc inside the timed region once warm).
-class DeviceArena {
- public:
-  ~DeviceArena();
-  void Reset() { used_ = 0; }
-  void Reserve(size_t bytes, hipStream_t s);   // make sure capacity >= bytes (frees + reallocates if needed)
-  void *Alloc(size_t bytes);                   // 256-byte aligned; throws if Reserve() was too small
-  size_t capacity() const { return cap_; }
-  template <typename T> T *AllocT(size_t n) { return static_cast<T *>(Alloc(n * sizeof(T))); }
- private:
-  char *base_ = nullptr;
-  size_t cap_ = 0, used_ = 0;
+// The two arenas of a decode call (arena.h: blocks appended on demand, coalesced into one by the Reset that follows, so that a warm
+// call allocates nothing).  Device memory: every block zero-filled when it is allocated, and its last 1 MiB never handed out -- some
+// kernels read a little past the end of their last buffer (the + 256 / + 8 / + 64 at the allocation sites), which has to stay in
+// mapped memory.  Page-locked host staging: the small H2D / D2H transfers of a call are truly asynchronous from it and never wait on
+// a pageable-memory bounce buffer.
+struct DeviceBlocks {
+  static constexpr size_t kAlign = 256, kTail = (size_t)1 << 20;
+  using Stream = hipStream_t;
+  void *Allocate(size_t bytes, hipStream_t s);      // filled before it returns: the block may be used on any stream
+  void Free(void *p) { (void)hipFree(p); }
+  void Synchronize(hipStream_t s);
 };
-
-// Grow-only page-locked host staging: small H2D / D2H transfers of a decode call are truly asynchronous from it and never
-// wait on a pageable-memory bounce buffer.  Contents stay valid until the next Reset().
-class HostArena {
- public:
-  ~HostArena();
-  void Reset() { used_ = 0; cur_ = 0; }
-  void *Alloc(size_t bytes);                   // 64-byte aligned; grows (a new block) when needed
-  template <typename T> T *AllocT(size_t n) { return static_cast<T *>(Alloc(n * sizeof(T))); }
- private:
-  std::vector<std::pair<char *, size_t>> blocks_;
-  size_t cur_ = 0, used_ = 0;
+struct PinnedBlocks {
+  static constexpr size_t kAlign = 64, kTail = 0;
+  using Stream = hipStream_t;
+  void *Allocate(size_t bytes, hipStream_t s);
+  void Free(void *p) { (void)hipHostFree(p); }
+  void Synchronize(hipStream_t s);
 };
+using DeviceArena = Arena<DeviceBlocks>;
+using HostArena = Arena<PinnedBlocks>;
 
 struct Hypothesis {
   std::vector<int32_t> words;
@@ -140,7 +136,6 @@ class Model {
   void ToDevice();
   // The online iVector estimator over K chunks of n streams / utterances in four launches (ivector_kernels.hip: IvecChainKernel);
   // d_fb / d_fe / d_or / d_ac: [K][n] frame ranges, iVector rows, "has new frames"; state rows slot[u] (null: u) of lin / quad / numf / x
-  static size_t IvecChunkChainBytes(const IvecDev &iv, int n, int K);
   void IvecChunkChain(DeviceArena &arena, const BatchGeom &g, int n, int K, const float *stats_feats, int ld_l, const int *post_idx, const float *post_w,
                       const int *d_fb, const int *d_fe, const int *d_or, const int *d_ac, double *lin, double *quad, double *numf, double *x, const int *slot,
                       float *ivec_out, int ld_i, hipStream_t s) const;
@@ -190,7 +185,6 @@ class Model {
                    hipStream_t s, bool streaming, UttResult *out_utts, float *timings);
   // DecodeGroup's stages (engine.cc)
   void BatchFrames(const int64_t *sample_offsets, BatchCall *b) const;
-  size_t BatchArenaBytes(BatchCall *b, int nbest, float lat_scale, SearchPlan *sp) const;
   void BatchSetupUpload(const int64_t *sample_offsets, BatchCall *b);
   void BatchFeatures(const int16_t *d_pcm, BatchCall *b);
   void BatchIvectors(BatchCall *b);
@@ -203,11 +197,10 @@ class Model {
   // buffer `out` belongs to (-1: none of them)
   GemmDev MakeGemm(const GemmPlan &pl, const std::vector<float *> &src, const std::vector<int> &src_ld, float *ivec, int ivec_ld, float *out, int ldo,
                    int share, const std::vector<ActImage> *imgs = nullptr, int out_buf = -1) const;
-  // operand images for the buffers the split-bf16 GEMM reads as images: bytes needed / allocation from a call's arena
-  size_t ImageBytes(int rows) const;
+  // operand images for the buffers the split-bf16 GEMM reads as images, from a call's arena
   std::vector<ActImage> AllocImages(DeviceArena &arena, int rows) const;
   std::vector<char> buf_image_, buf_f32_;      // per nnet buffer: has an operand image / is (also) read as plain floats
-  size_t PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only = false, bool token_lists = false) const;
+  void PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only = false, bool token_lists = false) const;
   void AllocSearch(SearchPlan *sp, DeviceArena &arena, hipStream_t s, bool pooled_frames = false) const;
   void LaunchSearch(SearchPlan *sp, DeviceArena &arena, const BatchGeom &g, const float *ll, int ll_ld, hipStream_t s) const;
   void CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const BatchGeom &g, const int *T, const float *ll, int ll_ld, int nbest,
@@ -267,7 +260,7 @@ class Model {
   friend struct StreamPool;
   std::unique_ptr<StreamPool, StreamPoolDeleter> pool_;
   std::unique_ptr<DecodeContext> stream_ctx_;
-  std::mutex pool_mu_;             // pool bookkeeping and advances of this model, one at a time
+  mutable std::mutex pool_mu_;     // pool bookkeeping and advances of this model, one at a time
   StreamPool *Pool();
   void StreamsDrain(StreamPool *p, float *extra);
   void IssuerSync(StreamPool *p);     // everything handed to the pool's issuing thread has been queued; ITS failure poisons the open streams, then rethrows
@@ -276,7 +269,7 @@ class Model {
   PlanConfig PlanCfg() const;         // the integers call_plan.h plans with
   int AdvanceTakeSet(StreamPool *p, bool final);
   void AdvancePlanStreams(StreamPool *p, rs_stream *const *streams, int n, bool flush, bool final, AdvancePlan *plan);
-  void AdvanceUpload(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, size_t search_bytes, bool final, AdvanceSet *set);
+  void AdvanceUpload(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, bool final, AdvanceSet *set);
   void AdvanceStageA(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set);
   void AdvanceIvectors(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set);
   void AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set, bool final, bool reg_windows, SearchPlan *sp);

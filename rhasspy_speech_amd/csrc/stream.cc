@@ -591,7 +591,6 @@ struct AdvanceSet {
   int16_t *d_pcm = nullptr;      // the new samples of the streams with new frames, back to back
   bool timed = false;            // this advance carries the stage timers' events (StreamPool::kTimedEvery)
   int guard = 0;
-  std::vector<int> buf_ld;       // row pitch of the network's buffers
 };
 
 // Stages B and C of an advance -- the acoustic model and the scatter into the pool on q, the search windows on qc -- as the values
@@ -678,31 +677,15 @@ void Model::AdvancePlanStreams(StreamPool *p, rs_stream *const *streams, int n, 
   PlanAdvanceRows(cfg, views.data(), n, flush, final, plan);
 }
 
-// Arena of the set sized for every stage, then the uploads on qa: the index arrays in one copy, the new samples in another
-void Model::AdvanceUpload(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, size_t search_bytes, bool final, AdvanceSet *set) {
-  const Nnet &nn = am_.nnet;
-  const bool has_iv = fc_.ie.present;
-  const int Dl = has_iv ? fc_.ie.feat_dim() : 0, Di = has_iv ? fc_.ie.ivector_dim() : 0, G = has_iv ? fc_.ie.num_gauss() : 0;
-  const int ld_c = p->ld_c, ld_l = RoundUp(std::max(Dl, 1), 4), usz = Di * (Di + 1) / 2, nsel = has_iv ? fc_.ie.num_gselect : 0;
-  const int n = plan.n, nI = plan.nI, rowsM = plan.rowsM, rowsI = plan.rowsI, rowsN = plan.rowsN, guard = set->guard = L_ + R_ + 8;
+// The set's arenas handed back, then the uploads on qa: the index arrays in one copy, the new samples in another
+void Model::AdvanceUpload(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, bool final, AdvanceSet *set) {
+  const int n = plan.n;
   DeviceArena &arena = *set->arena;
   HostArena &harena = *set->harena;
   hipStream_t qa = p->qa;
-  auto fbytes = [&](int rows, int ld) { return ((size_t)rows + 2 * guard) * ld * sizeof(float) + 512; };
-  set->buf_ld.resize(nn.bufs.size());
-  size_t need = plan.stage.size() * 4 + plan.pcm_total * 2 + 4096 + 3 * sizeof(int) * (size_t)(rowsM + rowsI + rowsN + 64) + sizeof(int) * (size_t)(plan.framesN + 64);
-  for (size_t b = 0; b < nn.bufs.size(); b++) { set->buf_ld[b] = RoundUp(nn.bufs[b].dim, 4); need += fbytes(rowsN, set->buf_ld[b]); }
-  need += ImageBytes(rowsN);
-  if (has_iv) {
-    need += 2 * fbytes(rowsI, ld_c) + 2 * fbytes(rowsI, ld_l) + (size_t)rowsI * nsel * 8 + 4096;
-    need += (size_t)std::max(nI, 1) * ((size_t)G * 8 + (size_t)G * Dl * 8 + (size_t)Di * 16 + (size_t)usz * 8 + 64) + 8192;
-    need += IvecStatsScratchDoubles(ivec_dev_, std::max(nI, 1)) * 8 + 1024;
-    need += IvecChunkChainBytes(ivec_dev_, std::max(nI, 1), std::max(plan.max_new_chunks, 1));
-  }
-  need += search_bytes + (size_t)n * 64 * 8 + 64 * 256 + (1u << 20);
-  arena.Reserve(need, qa);
-  arena.Reset();
-  harena.Reset();
+  set->guard = L_ + R_ + 8;
+  arena.Reset(qa);
+  harena.Reset(qa);
   const size_t n_is = plan.stage.size(), pcm_total = plan.pcm_total;
   set->d_is = arena.AllocT<int>(n_is + 16);
   {
@@ -842,9 +825,10 @@ void Model::AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const Advanc
   job.n_sub = (int)plan.n_lldst.size(); job.have_sub = !plan.n_llsrc.empty();
   job.d_nsrc = D(o.nsrc); job.d_nfb = D(o.nfb); job.d_nrb = D(o.nrb); job.d_nriv = D(o.nriv); job.d_nll = D(o.nll); job.d_nlls = D(o.nlls); job.d_slots = D(o.slots);
   job.bufp.assign(nn.bufs.size(), nullptr);
-  job.buf_ld = set.buf_ld;
+  job.buf_ld.resize(nn.bufs.size());
+  for (size_t b = 0; b < nn.bufs.size(); b++) job.buf_ld[b] = RoundUp(nn.bufs[b].dim, 4);
   if (plan.nN > 0) {
-    for (size_t b = 0; b < nn.bufs.size(); b++) job.bufp[b] = AllocGuarded(arena, plan.rowsN, set.buf_ld[b], set.guard);
+    for (size_t b = 0; b < nn.bufs.size(); b++) job.bufp[b] = AllocGuarded(arena, plan.rowsN, job.buf_ld[b], set.guard);
     job.imgs = AllocImages(arena, plan.rowsN);
     job.frame_rows = arena.AllocT<int>(plan.framesN + 8);
   }
@@ -1007,10 +991,10 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
   AdvancePlan &plan = p->plans[set.par];
   AdvancePlanStreams(p, streams, n, flush, final, &plan);
   SearchPlan sp;
-  const size_t search_bytes = final ? PlanSearch(n, plan.maxT, nbest, lat_scale, &sp) : 0;
+  if (final) PlanSearch(n, plan.maxT, nbest, lat_scale, &sp);
   const bool reg_windows = p->reg && !(final && sp.want_lattice);
   clock.Mark(&p->host_ms[0]);
-  AdvanceUpload(p, streams, plan, search_bytes, final, &set);
+  AdvanceUpload(p, streams, plan, final, &set);
   clock.Mark(&p->host_ms[1]);
   AdvanceStageA(p, plan, set);
   clock.Mark(&p->host_ms[2]);
@@ -1074,17 +1058,14 @@ void Model::StreamsPartialLocked(rs_stream *const *streams, int n, Result *res) 
   HostArena &harena = cx.host_arena[par];
   hipStream_t qc = p->qc;
   SearchPlan sp;
-  size_t need = (size_t)n * 3 * 16 + 4096;
   if (p->reg) {
     sp.n_utts = n; sp.S = S; sp.maxT = maxT; sp.max_words = StreamPool::kPartialWords;
-    need += (size_t)n * ((size_t)sp.max_words * 4 + 4 + 16 + 64 + (size_t)4 * (maxT + 2) * 8) + 65536;
   } else {
-    need += PlanSearch(n, maxT, 1, 1.0f, &sp, /*best_path_only=*/true);
+    PlanSearch(n, maxT, 1, 1.0f, &sp, /*best_path_only=*/true);
     sp.dopts.no_final = 1;
   }
-  arena.Reserve(need, qc);
-  arena.Reset();
-  harena.Reset();
+  arena.Reset(qc);
+  harena.Reset(qc);
   int *d_idx = arena.AllocT<int>((size_t)3 * n + 16);
   {
     int *h = harena.AllocT<int>((size_t)3 * n + 16);
@@ -1206,11 +1187,9 @@ void Model::StreamsEndpointLocked(rs_stream *const *streams, int n, const std::v
   HostArena &harena = cx.host_arena[par];
   hipStream_t qc = p->qc;
   SearchPlan sp;
-  size_t need = (size_t)n * (3 * 16 + 16) + 8192;
-  if (!p->reg) need += PlanSearch(n, maxT, 1, 1.0f, &sp, /*best_path_only=*/true, /*token_lists=*/true);
-  arena.Reserve(need, qc);
-  arena.Reset();
-  harena.Reset();
+  if (!p->reg) PlanSearch(n, maxT, 1, 1.0f, &sp, /*best_path_only=*/true, /*token_lists=*/true);
+  arena.Reset(qc);
+  harena.Reset(qc);
   EndpointWork ew;
   std::memset(&ew, 0, sizeof(ew));
   ew.sil_arc = SilenceArcBitmap(sil_phones, qc);
@@ -1297,9 +1276,8 @@ void Model::StreamsAdaptation(rs_stream *const *streams, int n, rs_adaptation **
     DeviceArena &arena = cx.arena[par];
     HostArena &harena = cx.host_arena[par];
     hipStream_t qc = p->qc;
-    arena.Reserve((size_t)n * (3 * 4 + (4 * (size_t)C1 + stride) * 8) + 8192, qc);
-    arena.Reset();
-    harena.Reset();
+    arena.Reset(qc);
+    harena.Reset(qc);
     int *d_idx = arena.AllocT<int>((size_t)3 * n + 16);
     double *d_car = arena.AllocT<double>((size_t)n * 4 * C1 + 8), *d_out = arena.AllocT<double>((size_t)n * stride + 8);
     {
