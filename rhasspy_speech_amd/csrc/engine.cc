@@ -506,8 +506,8 @@ void Model::BuildGemmPlan(const LayerOp &op, GemmPlan *plan) {
     }
     // (2) GemmKernelB3I (sources stored as operand images): segments padded to the 16-wide k-step only; needs every source
     // to be a frame buffer whose first column sits on a k-step boundary
-    // ... and the layer to be one the split-bf16 kernels take at all (GemmB3IUsable's padding rule: at most a quarter of the
-    // 256-column tiles may be padding) -- decided HERE, because the producers of its sources stop storing plain floats
+    // ... and the layer to be one the split-fp16 kernels take at all (the padding rule of gemm_launch.h: GemmB3PaddingOk) --
+    // decided HERE, because the producers of its sources stop storing plain floats
     bool imageable = finite && GemmB3PaddingOk(op.out_dim, plan->n3);
     for (auto &sg : op.segs) imageable = imageable && sg.src_buf >= 0 && sg.src_col % 16 == 0;
     if (imageable) {
@@ -1236,17 +1236,18 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
     int conv_rows = rows;
     if (op.kind == LayerOp::kGemm) {
       GemmDev gd = MakeGemm(gemm_plans_[i], bufp, buf_ld, d_ivec, ld_i, bufp[op.out_buf], buf_ld[op.out_buf], share, imgs, (int)op.out_buf);
-      if (img_out && !GemmWritesImage(gd)) gd.write_f32 = 1;      // a kernel without the image epilogue: converted below
+      const GemmSwitches sw = ReadGemmSwitches();
+      if (img_out && !GemmWritesImage(gd, sw)) gd.write_f32 = 1;      // the exact-FP32 kernels have no image epilogue: converted below
       else img_done = img_out;
       const BufferInfo &ob = nn.bufs[op.out_buf];
       if (const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride)) {     // only the rows somebody reads
         gd.row_map = rm->rows;
         gd.row_map_span128 = rm->span128;
         gd.row_map_span160 = rm->span160;
-        LaunchGemm(gd, rm->count, d_row_ivec, s);
+        LaunchGemm(gd, rm->count, d_row_ivec, s, &sw);
         conv_map = rm->rows; conv_rows = rm->count;
       } else {
-        LaunchGemm(gd, rows, d_row_ivec, s);
+        LaunchGemm(gd, rows, d_row_ivec, s, &sw);
       }
     } else {
       EltwiseDev d;

@@ -16,7 +16,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int kB3BN = 256, kB3KS = 16;
+// (kB3BN = 256 columns per tile, kB3KS = 16 of K per step: gemm_dev.h, shared with the launch policy)
 constexpr int kB3Parts = 2;                           // fp16 parts per FP32 operand (nnet_gemm_b3.hip)
 constexpr int kB3FragBytes = 1024;                    // one 32 x 16 fp16 operand fragment
 // LDS of the epilogue (nnet_b3_epilogue.inc): one 32-row slab at a pitch of kB3BN + 4 floats + bias / scale / offset / weight scale of the tile's columns

@@ -1,4 +1,4 @@
-// Pieces shared by the GEMM kernels (nnet_kernels.hip: exact-FP32 MFMA; nnet_gemm_b3.hip: split-bf16 MFMA).
+// Pieces shared by the GEMM kernels (nnet_kernels.hip: exact-FP32 MFMA; nnet_gemm_b3*.hip: split-fp16 MFMA).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,19 +26,14 @@ inline int GemmEpiMode(const GemmDev &d, int rows) {
 }
 
 
-// nnet_gemm_b3.hip
-bool GemmB3Usable(const GemmDev &d);
-void LaunchGemmB3(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s);
+// One dispatch per kernel file: runs the instantiation the plan names (gemm_launch.h; p.family is the file's) on the grid the plan
+// carries.  A shape without an instantiation is a programming error: GemmNoInstantiation fails naming it, nothing is launched.
+void DispatchGemmB3(const GemmLaunch &p, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s);      // nnet_gemm_b3.hip
+void DispatchGemmB3I(const GemmLaunch &p, const GemmDev &d, int rows, hipStream_t s);                          // nnet_gemm_b3i.hip
+void DispatchGemmB3J(const GemmLaunch &p, const GemmDev &d, int rows, hipStream_t s);                          // nnet_gemm_b3j.hip
+[[noreturn]] void GemmNoInstantiation(const GemmLaunch &p);                                                    // nnet_kernels.hip
 // nnet_gemm_b3i.hip: a layer with a folded residual (GemmDev::res) on a kernel that does not add it in its own epilogue
 GemmDev GemmWithoutResidual(const GemmDev &d);
 void LaunchResidualAdd(const GemmDev &d, int rows, hipStream_t s);
-// nnet_gemm_b3i.hip (sources stored as operand images)
-bool GemmB3IUsable(const GemmDev &d);
-void LaunchGemmB3I(const GemmDev &d, int rows, hipStream_t s);
-// nnet_gemm_b3j.hip: the same GEMM with both operands through LDS-DMA, hand-placed waits and a 256 x 256 tile (large launches)
-bool GemmB3JUsable(const GemmDev &d, int rows);
-bool GemmB3JSmallUsable(const GemmDev &d);                 // launches of 32-row tiles on GemmKernelB3J (nnet_gemm_b3j.hip)
-void LaunchGemmB3JSmall(const GemmDev &d, int rows, hipStream_t s);
-void LaunchGemmB3J(const GemmDev &d, int rows, hipStream_t s);
 
 }  // namespace rs

@@ -29,10 +29,7 @@
 //            requested and the activations of step t + 1 are split into LDS.
 // (History of the three-bf16 form of this kernel: profiles/r01)
 #include <hip/hip_runtime.h>
-#include <algorithm>
 #include <cstdint>
-#include <cstdlib>
-#include "env.h"
 
 #include "nnet_b3_common.h"
 
@@ -253,8 +250,7 @@ __global__ __launch_bounds__(256 * WM, WM == 1 ? 2 : 1) void GemmKernelB3(GemmDe
 }
 
 template <int MR, bool MIXED, int WM>
-void LaunchB3(const GemmDev &d, int rows, int nbig, const int *row_ivec, hipStream_t s) {
-  constexpr int BM = 32 * MR * WM;
+void LaunchB3(const GemmLaunch &p, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
   constexpr size_t stage = 2 * (size_t)(MR * WM * kB3Parts * kB3FragBytes), ctile = kB3EpiBytes;
   // WM = 2 asks for all but 1 KiB of the CU's LDS: no other workgroup fits beside it
   constexpr size_t smem = WM == 1 ? (stage > ctile ? stage : ctile) : (size_t)159 * 1024;
@@ -263,78 +259,21 @@ void LaunchB3(const GemmDev &d, int rows, int nbig, const int *row_ivec, hipStre
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&GemmKernelB3<MR, MIXED, WM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
-  const int ncol = (d.n + kB3BN - 1) / kB3BN;
-  const int rest = std::max(rows - nbig * BM, 0), nsmall = MIXED ? (rest + BM / 2 - 1) / (BM / 2) : 0;
-  const int blocks = ((nbig + 7) / 8 * 8 + (nsmall + 7) / 8 * 8) * ncol;
-  hipLaunchKernelGGL((GemmKernelB3<MR, MIXED, WM>), dim3(blocks), dim3(256 * WM), smem, s, d, rows, nbig, row_ivec, GemmEpiMode(d, rows));
+  hipLaunchKernelGGL((GemmKernelB3<MR, MIXED, WM>), dim3(p.blocks), dim3(p.threads), smem, s, d, rows, p.nbig, row_ivec, GemmEpiMode(d, rows));
 }
 
 }  // namespace
 
-// Up to 45 % of the 256-column tiles may be padding: per padded column the split-fp16 kernels are about three times as fast as
-// the exact-FP32 kernel with its 128-column tiles (hidden layer 105 us for 33 GFLOP against 163 us for the 15 GFLOP of the pruned
-// output layer, profiles/r04), so e.g. the headline's 362 output columns (29 % padding in two tiles) belong here: 163 -> 85 us.
-bool GemmB3PaddingOk(int n, int n3) {
-  static const int pct = [] { const char *e = TuneEnv("RS_GEMM_B3_PAD"); return e ? std::atoi(e) : 45; }();
-  // One tile wide, at least 96 columns (round 6: a factorised TDNN's 128-wide bottlenecks, K = 2048): the exact-FP32 kernel ran such a
-  // layer at 109 TFLOP/s, 0.7 of ITS peak (403 us for 84 k rows), the split kernels take 62.5 % padding and are still 2.4 times as fast
-  // (profiles/r06/tdnnf_notes.txt); RS_GEMM_B3_NARROW=0 (read per model load) keeps the 45 % rule alone.
-  if (n3 == kB3BN && n >= 96) { const char *e = std::getenv("RS_GEMM_B3_NARROW"); if (!(e && std::atoi(e) == 0)) return true; }
-  return (long)(n3 - n) * 100 <= (long)n3 * pct;
-}
-
-bool GemmB3Usable(const GemmDev &d) {
-  const char *e = std::getenv("RS_GEMM_B3");          // read per call: the parity test flips it between two decodes
-  if ((e && std::atoi(e) == 0) || !d.W3 || d.n3 < kB3BN) return false;
-  if (!GemmB3PaddingOk(d.n, d.n3)) return false;
-  for (int i = 0; i < d.nsegs; i++)
-    if ((d.segs[i].ld & 3) || (d.segs[i].col0 & 3) || (reinterpret_cast<uintptr_t>(d.segs[i].src) & 15)) return false;
-  return true;
-}
-
-void LaunchGemmB3(const GemmDev &d0, int rows, const int *row_ivec, hipStream_t s) {
-  if (d0.res) {      // (a folded residual: this kernel's epilogue does not add it -- nnet_gemm_b3i.hip)
-    LaunchGemmB3(GemmWithoutResidual(d0), rows, row_ivec, s);
-    LaunchResidualAdd(d0, rows, s);
-    return;
+void DispatchGemmB3(const GemmLaunch &p, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
+  switch (p.mr * 100 + p.mixed * 10 + p.wm) {      // MR, MIXED, WM
+    case 302: return LaunchB3<3, false, 2>(p, d, rows, row_ivec, s);
+    case 202: return LaunchB3<2, false, 2>(p, d, rows, row_ivec, s);
+    case 201: return LaunchB3<2, false, 1>(p, d, rows, row_ivec, s);
+    case 301: return LaunchB3<3, false, 1>(p, d, rows, row_ivec, s);
+    case 401: return LaunchB3<4, false, 1>(p, d, rows, row_ivec, s);
+    case 411: return LaunchB3<4, true, 1>(p, d, rows, row_ivec, s);
+    default: GemmNoInstantiation(p);
   }
-  const GemmDev &d = d0;
-  static int num_cu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  static int force_mr = [] { const char *e = TuneEnv("RS_GEMM_B3_MR"); return e ? std::atoi(e) : 0; }();
-  static int mixed = [] { const char *e = TuneEnv("RS_GEMM_B3_MIXED"); return e ? std::atoi(e) : 1; }();
-  const int ncol = (d.n + kB3BN - 1) / kB3BN;
-  if (d.exclusive) {
-    // one 512-thread workgroup per CU; tile height 128 or 192 rows, whichever leaves the fuller last round
-    auto rounds1 = [&](int bm) { return (double)(((long)((rows + bm - 1) / bm) * ncol + num_cu - 1) / num_cu) * bm; };
-    if (rounds1(192) * 0.97 < rounds1(128)) LaunchB3<3, false, 2>(d, rows, (rows + 191) / 192, row_ivec, s);
-    else LaunchB3<2, false, 2>(d, rows, (rows + 127) / 128, row_ivec, s);
-    return;
-  }
-  const long slots = std::max(2L * num_cu / std::max(d.share, 1), 8L);      // two workgroups per CU; the device may be shared
-  // Tile height: rounds of `slots` tiles, each as long as the tile is tall, weighted by the measured per-row efficiency
-  // of the height (taller tiles stream the weights for more rows: 0.78 at 128 rows).
-  auto rounds = [&](long row_tiles) { return (double)((row_tiles * ncol + slots - 1) / slots); };
-  auto cost = [&](int bm, double eff) { return rounds((rows + bm - 1) / bm) * bm * eff; };
-  int mr = 2, nbig = (rows + 63) / 64;
-  double best = cost(64, 1.0);
-  if (cost(96, 0.97) < best) { best = cost(96, 0.97); mr = 3; nbig = (rows + 95) / 96; }
-  if (cost(128, 0.78) < best) { best = cost(128, 0.78); mr = 4; nbig = (rows + 127) / 128; }
-  if (mixed) {
-    // whole rounds of 128-row tiles, the remaining rows as 64-row tiles of the same launch
-    const long full = (long)(rows / 128) * ncol / slots * slots / ncol;        // 128-row tiles in whole rounds
-    const long rest = rows - full * 128;
-    const double c = rounds(full) * 128 * 0.78 + rounds((rest + 63) / 64) * 64 * 1.0;
-    if (full > 0 && c < best) { best = c; mr = 4; nbig = (int)full; }
-  }
-  if (force_mr >= 2 && force_mr <= 4) { mr = force_mr; nbig = (rows + 32 * mr - 1) / (32 * mr); }
-  if (mr == 2) LaunchB3<2, false, 1>(d, rows, nbig, row_ivec, s);
-  else if (mr == 3) LaunchB3<3, false, 1>(d, rows, nbig, row_ivec, s);
-  else if ((long)nbig * 128 >= rows) LaunchB3<4, false, 1>(d, rows, nbig, row_ivec, s);
-  else LaunchB3<4, true, 1>(d, rows, nbig, row_ivec, s);
 }
 
 }  // namespace rs

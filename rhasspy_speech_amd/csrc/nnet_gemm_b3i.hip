@@ -23,10 +23,7 @@
 // beside the asm loads spill.  The tile quantisation (656 row tiles of 128 on 512 slots) and the L2 stream of the weights
 // (24 KiB per k-step and workgroup) are what is left to attack.
 #include <hip/hip_runtime.h>
-#include <algorithm>
 #include <cstdint>
-#include <cstdlib>
-#include "env.h"
 
 #include "nnet_b3_common.h"
 
@@ -199,8 +196,7 @@ __global__ __launch_bounds__(256, 2) void GemmKernelB3I(GemmDev d, int rows, int
 }
 
 template <int MR, bool MIXED, int KPS = kKPS>
-void LaunchB3I(const GemmDev &d, int rows, int nbig, hipStream_t s) {
-  constexpr int BM = 32 * MR;
+void LaunchB3I(const GemmLaunch &p, const GemmDev &d, int rows, hipStream_t s) {
   constexpr size_t stage = 2 * (size_t)KPS * MR * kB3Parts * kB3FragBytes, ctile = kB3EpiBytes;
   constexpr size_t smem = stage > ctile ? stage : ctile;
   static bool attr_set = false;
@@ -208,10 +204,7 @@ void LaunchB3I(const GemmDev &d, int rows, int nbig, hipStream_t s) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&GemmKernelB3I<MR, MIXED, KPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
-  const int ncol = (d.n + kB3BN - 1) / kB3BN;
-  const int rest = std::max(rows - nbig * BM, 0), nsmall = MIXED ? (rest + BM / 2 - 1) / (BM / 2) : 0;
-  const int blocks = ((nbig + 7) / 8 * 8 + (nsmall + 7) / 8 * 8) * ncol;
-  hipLaunchKernelGGL((GemmKernelB3I<MR, MIXED, KPS>), dim3(blocks), dim3(256), smem, s, d, rows, nbig, GemmEpiMode(d, rows));
+  hipLaunchKernelGGL((GemmKernelB3I<MR, MIXED, KPS>), dim3(p.blocks), dim3(p.threads), smem, s, d, rows, p.nbig, GemmEpiMode(d, rows));
 }
 
 // f32 rows -> operand image: one wave per (row block, k-step) 1 KiB block, both parts
@@ -314,61 +307,16 @@ void LaunchResidualAdd(const GemmDev &d, int rows, hipStream_t s) {
   hipLaunchKernelGGL(ToImageKernel, dim3((rows + 31) / 32), dim3(256), 0, s, d.out, d.ldo, d.n, rows, d.out_img, d.ovf, d.row_map, rd);
 }
 
-bool GemmImagesEnabled() {
-  const char *e = std::getenv("RS_GEMM_B3I"), *e3 = std::getenv("RS_GEMM_B3");          // read per call (tests flip them)
-  return !(e && std::atoi(e) == 0) && !(e3 && std::atoi(e3) == 0);
-}
-
-bool GemmB3IUsable(const GemmDev &d) {
-  if (!GemmImagesEnabled() || !d.W3I || d.n3 < kB3BN) return false;
-  if (!GemmB3PaddingOk(d.n, d.n3)) return false;
-  for (int i = 0; i < d.nsegs; i++)
-    if (!d.segs[i].img.base || d.segs[i].per_utt || (d.segs[i].col0 % kB3KS) != 0) return false;
-  if (d.interleave)
-    for (int i = 1; i < d.nsegs; i++) if (d.segs[i].img.base != d.segs[0].img.base) return false;
-  return true;
-}
-
-void LaunchGemmB3I(const GemmDev &d0, int rows, hipStream_t s) {
-  const GemmDev d = d0.res ? GemmWithoutResidual(d0) : d0;
-  static int num_cu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  static int force_mr = [] { const char *e = TuneEnv("RS_GEMM_B3_MR"); return e ? std::atoi(e) : 0; }();
-  const int ncol = (d.n + kB3BN - 1) / kB3BN;
-  const long slots = std::max(2L * num_cu / std::max(d.share, 1), 8L);      // two workgroups per CU; the device may be shared
-  // Tile height: rounds of `slots` tiles, each as long as the tile is tall, weighted by the per-row cost of the height
-  // (a 64-row tile streams the weights for half as many rows as a 128-row one)
-  auto rounds = [&](long row_tiles) { return (double)((row_tiles * ncol + slots - 1) / slots); };
-  static const double eff64 = [] { const char *e = TuneEnv("RS_GEMM_B3I_EFF64"); return e ? std::atof(e) : 1.3; }();
-  // whole rounds of 128-row tiles, the remaining rows as 64-row tiles of the same launch
-  const long full = (long)(rows / 128) * ncol / slots * slots / ncol;
-  const long rest = rows - full * 128;
-  const double c_mixed = rounds(full) * 128 + rounds((rest + 63) / 64) * 64 * eff64;
-  const double c_128 = rounds((rows + 127) / 128) * 128, c_64 = rounds((rows + 63) / 64) * 64 * eff64;
-  // a launch of less than one round (a stream advance: a few thousand rows) is as long as ONE tile is: the 32-row tile spreads it
-  // over four times as many CUs as the 128-row one, each streaming the same weights for a quarter of the rows
-  static const double eff32 = [] { const char *e = TuneEnv("RS_GEMM_B3I_EFF32"); return e ? std::atof(e) : 1.7; }();
-  const double c_32 = rounds((rows + 31) / 32) * 32 * eff32;
-  int mr = 4, nbig = (rows + 127) / 128;
-  bool mixed = false;
-  if (c_32 < c_64 && c_32 < c_128 && c_32 <= c_mixed) { mr = 1; nbig = (rows + 31) / 32; }
-  else if (c_64 < c_128 && c_64 <= c_mixed) { mr = 2; nbig = (rows + 63) / 64; }
-  else if (full > 0 && c_mixed < c_128) { mixed = true; nbig = (int)full; }
-  if (force_mr == 1) { mr = 1; nbig = (rows + 31) / 32; mixed = false; }
-  if (force_mr == 2) { mr = 2; nbig = (rows + 63) / 64; mixed = false; }
-  if (force_mr == 4) { mr = 4; nbig = (rows + 127) / 128; mixed = false; }
-  static const int kps1 = [] { const char *e = TuneEnv("RS_GEMM_B3I_KPS"); return e ? std::atoi(e) : 8; }();
-  if (mr == 1 && GemmB3JSmallUsable(d0)) { LaunchGemmB3JSmall(d0, rows, s); return; }      // (adds a folded residual itself)
-  if (mr == 1 && kps1 == 8) LaunchB3I<1, false, 8>(d, rows, nbig, s);
-  else if (mr == 1 && kps1 == 4) LaunchB3I<1, false, 4>(d, rows, nbig, s);
-  else if (mr == 1) LaunchB3I<1, false>(d, rows, nbig, s);
-  else if (mr == 2) LaunchB3I<2, false>(d, rows, nbig, s);
-  else if (mixed) LaunchB3I<4, true>(d, rows, nbig, s);
-  else LaunchB3I<4, false>(d, rows, nbig, s);
-  if (d0.res) LaunchResidualAdd(d0, rows, s);
+void DispatchGemmB3I(const GemmLaunch &p, const GemmDev &d, int rows, hipStream_t s) {
+  switch (p.mr * 100 + p.mixed * 10 + p.kps) {      // MR, MIXED, KPS
+    case 108: return LaunchB3I<1, false, 8>(p, d, rows, s);
+    case 104: return LaunchB3I<1, false, 4>(p, d, rows, s);
+    case 100 + kKPS: return LaunchB3I<1, false>(p, d, rows, s);
+    case 200 + kKPS: return LaunchB3I<2, false>(p, d, rows, s);
+    case 410 + kKPS: return LaunchB3I<4, true>(p, d, rows, s);
+    case 400 + kKPS: return LaunchB3I<4, false>(p, d, rows, s);
+    default: GemmNoInstantiation(p);
+  }
 }
 
 }  // namespace rs

@@ -36,7 +36,6 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <type_traits>
 #include <vector>
 #include "env.h"
 
@@ -689,9 +688,8 @@ _Pragma("unroll") \
 }
 
 template <int WM, bool MIXED, bool STRIP, int SDIV = 2, int MRT = 4, int WN = 4>
-void LaunchB3J(const GemmDev &d, int rows, int nbig, int nfirst, hipStream_t s) {
+void LaunchB3J(const GemmLaunch &p, const GemmDev &d, int rows, hipStream_t s) {
   typedef JShape<WM, MRT, WN> SH;
-  constexpr int BM = 32 * SH::kRowBlocks, kSmallBM = 32 * WM * (MRT / SDIV), BN = 64 * WN;
   // (STRIP: the ring holds weights only, two strips of 32 MRT + 64 rows x 16 columns x two parts behind it)
   constexpr size_t ring = STRIP ? (size_t)SH::kStages * SH::kBBytes + 2 * (size_t)(kJP * 2 * (32 * MRT + 64) * 16) : (size_t)SH::kStages * SH::kStage, ctile = kB3EpiBytes;
   constexpr size_t smem0 = ring > ctile ? ring : ctile;
@@ -703,14 +701,7 @@ void LaunchB3J(const GemmDev &d, int rows, int nbig, int nfirst, hipStream_t s) 
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&GemmKernelB3J<WM, MIXED, STRIP, SDIV, MRT, WN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max<size_t>(smem, 100 * 1024));
     attr_set = true;
   }
-  const int ncol = (d.n + BN - 1) / BN;
-  const int rest = std::max(rows - nbig * BM, 0), nsmall = MIXED ? (rest + kSmallBM - 1) / kSmallBM : 0;
-  // the half-height tiles are numbered through both of their block ranges: the first range holds a multiple of 8 of them
-  const bool alt = nfirst < 0;
-  nfirst = MIXED ? std::min(std::abs(nfirst) / 8 * 8, nsmall / 8 * 8) : 0;
-  if (alt && nbig < nfirst) nfirst = 0;
-  const int blocks = ((nbig + 7) / 8 * 8 + nfirst + (std::max(nsmall - nfirst, 0) + 7) / 8 * 8) * ncol;
-  hipLaunchKernelGGL((GemmKernelB3J<WM, MIXED, STRIP, SDIV, MRT, WN>), dim3(blocks), dim3(SH::kThreads), smem, s, d, rows, nbig, alt ? -nfirst : nfirst, GemmEpiMode(d, rows));
+  hipLaunchKernelGGL((GemmKernelB3J<WM, MIXED, STRIP, SDIV, MRT, WN>), dim3(p.blocks), dim3(p.threads), smem, s, d, rows, p.nbig, p.nfirst, GemmEpiMode(d, rows));
 #ifdef RS_B3J_TRACE
   static int traced = 0;
   const char *tf = TuneEnv("RS_B3J_TRACE_FILE");
@@ -720,8 +711,8 @@ void LaunchB3J(const GemmDev &d, int rows, int nbig, int nfirst, hipStream_t s) 
     std::vector<unsigned long long> h(8192 * 6);
     (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_b3j_trace), h.size() * sizeof(unsigned long long));
     if (FILE *f = std::fopen(tf, "w")) {
-      std::fprintf(f, "# blocks %d rows %d nbig %d nfirst %d ncol %d\n", blocks, rows, nbig, nfirst, ncol);
-      for (int b = 0; b < blocks && b < 8192; b++)
+      std::fprintf(f, "# blocks %d rows %d nbig %d nfirst %d ncol %d\n", p.blocks, rows, p.nbig, std::abs(p.nfirst), (d.n + 64 * WN - 1) / (64 * WN));
+      for (int b = 0; b < p.blocks && b < 8192; b++)
         std::fprintf(f, "%d %llu %llu %llu %llx %llu\n", b, h[b * 6], h[b * 6 + 1], h[b * 6 + 2], h[b * 6 + 3], h[b * 6 + 5] - h[b * 6 + 4]);
       std::fclose(f);
     }
@@ -729,114 +720,24 @@ void LaunchB3J(const GemmDev &d, int rows, int nbig, int nfirst, hipStream_t s) 
 #endif
 }
 
-// The strip form applies to a layer whose three segments are the same 16-column groups of ONE image at three ascending row offsets
-// no more than 64 rows apart (a TDNN layer's splice); with a row map (layers evaluated on the rows somebody reads) only when the tile's
-// rows, skipped halo rows included, still fit the strip.  RS_GEMM_B3J_STRIP=0 (tests, profiles: read per call)
-// keeps the one-fragment-set-per-offset form.
-bool JStripOk(const GemmDev &d, int tile_rows = 128) {
-  const char *e = TuneEnv("RS_GEMM_B3J_STRIP");
-  if (e && std::atoi(e) == 0) return false;
-  if (!d.interleave || d.nsegs != 3) return false;
-  const int span = tile_rows == 128 ? d.row_map_span128 : d.row_map_span160;      // physical rows the tile's list rows reach over
-  if (d.row_map && (span <= 0 || span + (d.segs[2].row_off - d.segs[0].row_off) > tile_rows + 64)) return false;
-  const GemmSegDev &a = d.segs[0];
-  if (!a.img.base || a.per_utt) return false;
-  for (int i = 1; i < 3; i++) {
-    const GemmSegDev &b = d.segs[i];
-    if (b.img.base != a.img.base || b.img.part_bytes != a.img.part_bytes || b.img.nks != a.img.nks || b.img.guard != a.img.guard || b.per_utt ||
-        b.col0 != a.col0 || b.ncols != a.ncols || b.row_off <= d.segs[i - 1].row_off)
-      return false;
-  }
-  return a.col0 % kB3KS == 0 && d.segs[2].row_off - a.row_off <= 64;
-}
-
-int JWaveRows() {          // RS_GEMM_B3J_WM = 1 | 2 (read per call)
-  const char *e = std::getenv("RS_GEMM_B3J_WM");
-  return e && std::atoi(e) == 2 ? 2 : 1;
-}
-long JSlots(const GemmDev &d, int wm) {
-  static int num_cu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  const char *es = std::getenv("RS_GEMM_B3J_SLOTS");          // tests: pretend the device runs this many workgroups at a time
-  if (es) return std::max(std::atol(es), 1L);
-  return std::max((long)(wm == 1 ? 2 : 1) * num_cu / std::max(d.share, 1), 8L);
-}
-
 }  // namespace
 
-// RS_GEMM_B3J=0 switches the kernel off, a value > 1 is the smallest launch (rows) it takes (read per call: tests flip it).
-bool GemmB3JUsable(const GemmDev &d, int rows) {
-  const char *e = std::getenv("RS_GEMM_B3J");
-  if (e && std::atoi(e) == 0) return false;
-  const int wm = JWaveRows();
-  const int ncol = (d.n + kB3BN - 1) / kB3BN;
-  // the 256-row tile needs whole rounds to pay off; a launch that GemmKernelB3I's 32-row tiles finish in one round (a stream
-  // advance: a few thousand rows) is faster there -- one tile's worth of time on four times as many CUs
-  const long min_default = wm == 2 ? JSlots(d, wm) * 256 / ncol : JSlots(d, 1) * 32 / ncol + 1;
-  const int min_rows = e && std::atoi(e) > 1 ? std::atoi(e) : (int)std::min<long>(min_default, 1 << 30);
-  return rows >= min_rows;
-}
-
-// A launch of less than one round of tiles (a stream advance: a few thousand rows) as 32-row tiles of this kernel: GemmKernelB3I's
-// ordinary weight loads are waited for with vmcnt(0) in every k-step (the compiler drains the counter in front of the first use of a
-// load result while an LDS-DMA is in flight), 0.59 us per k-step for a workgroup alone on its CU; here nothing in the loop is a load
-// the compiler sees.  RS_GEMM_B3J_SMALL=0 (read per call: a test compares the two kernels bit for bit) keeps GemmKernelB3I.
-bool GemmB3JSmallUsable(const GemmDev &d) {
-  const char *e = std::getenv("RS_GEMM_B3J_SMALL");
-  if (e && std::atoi(e) == 0) return false;
-  const char *e2 = std::getenv("RS_GEMM_B3J");
-  return !(e2 && std::atoi(e2) == 0) && JWaveRows() == 1;
-}
-void LaunchGemmB3JSmall(const GemmDev &d, int rows, hipStream_t s) { LaunchB3J<1, true, false, 4>(d, rows, 0, 0, s); }
-
-void LaunchGemmB3J(const GemmDev &d, int rows, hipStream_t s) {
-  const int wm = JWaveRows();
-  const int ncol = (d.n + kB3BN - 1) / kB3BN, bm = 128 * wm;
-  const long slots = JSlots(d, wm);
-  // whole rounds of full-height tiles; the remaining rows as half-height tiles of the same launch
-  const long tiles = rows / bm;
-  const long full = tiles * ncol / slots * slots / ncol;
-  const bool all_big = full * bm >= rows;
-  const int nbig = all_big ? (rows + bm - 1) / bm : (int)full;
-  static const int stagger = [] { const char *e = TuneEnv("RS_GEMM_B3J_STAGGER"); return e ? std::atoi(e) : 1; }();
-  int nfirst = stagger ? (int)(slots / 2) : 0;          // half-height tiles that go first (LaunchB3J clips it to what there is)
-  if (stagger == 2 && nbig >= nfirst) nfirst = -nfirst;
-  // Layers of at most 128 columns: the 256 x 128 tile (two wave rows x two wave columns).  RS_GEMM_B3J_NARROW=0 (tests: same bits) keeps
-  // the 256-column shapes, half of whose weight stream and MFMAs are padding for such a layer.
-  if (wm == 1 && d.n <= 128) {
-    const char *en = std::getenv("RS_GEMM_B3J_NARROW");
-    if (!(en && std::atoi(en) == 0)) {
-      const long tiles_n = rows / 256, full_n = tiles_n / slots * slots;
-      const bool all_n = full_n * 256 >= rows || (rows + 255) / 256 <= slots;
-      if (all_n) LaunchB3J<2, false, false, 2, 4, 2>(d, rows, (rows + 255) / 256, 0, s);
-      else LaunchB3J<2, true, false, 2, 4, 2>(d, rows, (int)full_n, 0, s);
-      return;
-    }
+void DispatchGemmB3J(const GemmLaunch &p, const GemmDev &d, int rows, hipStream_t s) {
+  // WM, MIXED, STRIP, SDIV, MRT, WN
+  switch (((((p.wm * 10 + p.mixed) * 10 + p.strip) * 10 + p.sdiv) * 10 + p.mr) * 10 + p.wn) {
+    case 110444: return LaunchB3J<1, true, false, 4>(p, d, rows, s);             // 32-row tiles only
+    case 200242: return LaunchB3J<2, false, false, 2, 4, 2>(p, d, rows, s);      // 256 x 128 (narrow)
+    case 210242: return LaunchB3J<2, true, false, 2, 4, 2>(p, d, rows, s);
+    case 101254: return LaunchB3J<1, false, true, 2, 5>(p, d, rows, s);          // 160 x 256
+    case 100254: return LaunchB3J<1, false, false, 2, 5>(p, d, rows, s);
+    case 200244: return LaunchB3J<2, false, false>(p, d, rows, s);               // 256 x 256
+    case 210244: return LaunchB3J<2, true, false>(p, d, rows, s);
+    case 101244: return LaunchB3J<1, false, true>(p, d, rows, s);                // 128 x 256
+    case 111244: return LaunchB3J<1, true, true>(p, d, rows, s);
+    case 100244: return LaunchB3J<1, false, false>(p, d, rows, s);
+    case 110244: return LaunchB3J<1, true, false>(p, d, rows, s);
+    default: GemmNoInstantiation(p);
   }
-  // The 160-row tile (five row blocks per wave) where it turns a launch of two rounds of tiles into ONE: a tile's k loop is as long as
-  // staging its weights takes, whatever its height, so a long-K launch costs about one loop time per round -- the half-height tiles of
-  // the last, partly filled round included.  Measured (profiles/r06/notes_experiments.txt): hidden layers (K = 750) 101 -> 90 us; no gain
-  // where K is short (the pre-final and output layers, K = 250: the tile's time is its epilogue, which grows with its rows) or where
-  // the taller tiles still need several rounds.  RS_GEMM_B3J_MR=4|5 forces a height (tests: same bits either way).
-  if (wm == 1) {
-    const char *em = std::getenv("RS_GEMM_B3J_MR");
-    const int force = em ? std::atoi(em) : 0;
-    int ksteps = 0;
-    for (int i = 0; i < d.nsegs; i++) ksteps += (d.segs[i].ncols + kB3KS - 1) / kB3KS;
-    const long rounds4 = ((long)((rows + 127) / 128) * ncol + slots - 1) / slots, rounds5 = ((long)((rows + 159) / 160) * ncol + slots - 1) / slots;
-    if (force == 5 || (force != 4 && rounds5 == 1 && rounds4 > 1 && ksteps >= 32)) {
-      const int nbig5 = (rows + 159) / 160;
-      if (JStripOk(d, 160)) LaunchB3J<1, false, true, 2, 5>(d, rows, nbig5, 0, s);
-      else LaunchB3J<1, false, false, 2, 5>(d, rows, nbig5, 0, s);
-      return;
-    }
-  }
-  if (wm == 2) { if (all_big) LaunchB3J<2, false, false>(d, rows, nbig, 0, s); else LaunchB3J<2, true, false>(d, rows, nbig, nfirst, s); }
-  else if (JStripOk(d)) { if (all_big) LaunchB3J<1, false, true>(d, rows, nbig, 0, s); else LaunchB3J<1, true, true>(d, rows, nbig, nfirst, s); }
-  else { if (all_big) LaunchB3J<1, false, false>(d, rows, nbig, 0, s); else LaunchB3J<1, true, false>(d, rows, nbig, nfirst, s); }
 }
 
 }  // namespace rs

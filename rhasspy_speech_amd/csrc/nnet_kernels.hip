@@ -10,14 +10,14 @@
 // producer's output; halo rows make the row offset a constant (kernels.h).
 //
 // FP32 in / FP32 accumulate on v_mfma_f32_16x16x4_f32 (exact f32, 157 TF peak).  Layers at least 192 columns wide take
-// the split-bf16 kernel instead (nnet_gemm_b3.hip: three bf16 parts per operand, six bf16 MFMAs per product, the same
+// the split-fp16 kernels instead (nnet_gemm_b3.hip: two fp16 parts per operand, three fp16 MFMAs per product, the same
 // accuracy); this file serves the narrow layers (LDA, bottlenecks) and RS_GEMM_B3=0.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include "env.h"
+#include <string>
 
+#include "kaldi_io.h"
 #include "kernels.h"
 #include "nnet_common.h"
 
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void GemmKernelDma(GemmDev d, int rows, con
 }
 
 template <int MT, int WM, int WN, bool VEC>
-static void LaunchGemmV(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
+static void LaunchGemmV(const GemmLaunch &p, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
   constexpr int BM = 16 * MT * WM, BN = 64 * WN;
   constexpr size_t smem = 2 * (size_t)(BM + BN) * 36 * sizeof(float);
   static bool attr_set = false;
@@ -353,12 +353,10 @@ static void LaunchGemmV(const GemmDev &d, int rows, const int *row_ivec, hipStre
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&GemmKernel<MT, WM, WN, VEC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
-  const int nrow = (rows + BM - 1) / BM, ncol = (d.n + BN - 1) / BN;
-  const int nrow8 = (nrow + 7) / 8 * 8;      // row tiles are dealt to the 8 XCDs round-robin
-  hipLaunchKernelGGL((GemmKernel<MT, WM, WN, VEC>), dim3(nrow8 * ncol), dim3(256), smem, s, d, rows, row_ivec, GemmEpiMode(d, rows));
+  hipLaunchKernelGGL((GemmKernel<MT, WM, WN, VEC>), dim3(p.blocks), dim3(p.threads), smem, s, d, rows, row_ivec, GemmEpiMode(d, rows));
 }
 template <int MT, int WM, int WN>
-static void LaunchGemmDma(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
+static void LaunchGemmDma(const GemmLaunch &p, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
   constexpr int BM = 16 * MT * WM, BN = 64 * WN;
   constexpr size_t stages = 2 * (size_t)(BM + BN) * kGemmBK * sizeof(float), ctile = (size_t)BM * (BN + 4) * sizeof(float);
   constexpr size_t smem = stages > ctile ? stages : ctile;
@@ -367,58 +365,59 @@ static void LaunchGemmDma(const GemmDev &d, int rows, const int *row_ivec, hipSt
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&GemmKernelDma<MT, WM, WN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     attr_set = true;
   }
-  const int nrow = (rows + BM - 1) / BM, ncol = (d.n + BN - 1) / BN;
-  const int nrow8 = (nrow + 7) / 8 * 8;
-  hipLaunchKernelGGL((GemmKernelDma<MT, WM, WN>), dim3(nrow8 * ncol), dim3(256), smem, s, d, rows, row_ivec, GemmEpiMode(d, rows));
+  hipLaunchKernelGGL((GemmKernelDma<MT, WM, WN>), dim3(p.blocks), dim3(p.threads), smem, s, d, rows, row_ivec, GemmEpiMode(d, rows));
 }
 
 template <int MT, int WM, int WN>
-static void LaunchGemmT(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
-  bool vec = true;
-  for (int i = 0; i < d.nsegs; i++)
-    vec = vec && (d.segs[i].ld & 3) == 0 && (d.segs[i].col0 & 3) == 0 && (reinterpret_cast<uintptr_t>(d.segs[i].src) & 15) == 0;
-  static int use_dma = [] { const char *e = TuneEnv("RS_GEMM_DMA"); return e ? std::atoi(e) : 1; }();
-  if (vec && use_dma) LaunchGemmDma<MT, WM, WN>(d, rows, row_ivec, s);
-  else if (vec) LaunchGemmV<MT, WM, WN, true>(d, rows, row_ivec, s);
-  else LaunchGemmV<MT, WM, WN, false>(d, rows, row_ivec, s);
+static void LaunchGemmT(const GemmLaunch &p, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
+  if (p.dma) LaunchGemmDma<MT, WM, WN>(p, d, rows, row_ivec, s);
+  else if (p.vec) LaunchGemmV<MT, WM, WN, true>(p, d, rows, row_ivec, s);
+  else LaunchGemmV<MT, WM, WN, false>(p, d, rows, row_ivec, s);
 }
 
-void LaunchGemm(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
-  if (rows <= 0) return;
-  if (GemmB3IUsable(d)) {
-    if (GemmB3JUsable(d, rows)) LaunchGemmB3J(d, rows, s);
-    else LaunchGemmB3I(d, rows, s);
-    return;
+static void DispatchGemmExact(const GemmLaunch &p, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
+  if (p.dma && !p.vec) GemmNoInstantiation(p);
+  switch (p.mr * 100 + p.wm * 10 + p.wn) {      // MT, WM, WN
+    case 141: return LaunchGemmT<1, 4, 1>(p, d, rows, row_ivec, s);
+    case 241: return LaunchGemmT<2, 4, 1>(p, d, rows, row_ivec, s);
+    case 422: return LaunchGemmT<4, 2, 2>(p, d, rows, row_ivec, s);
+    case 322: return LaunchGemmT<3, 2, 2>(p, d, rows, row_ivec, s);
+    case 222: return LaunchGemmT<2, 2, 2>(p, d, rows, row_ivec, s);
+    default: GemmNoInstantiation(p);
   }
-  if (GemmB3Usable(d)) { LaunchGemmB3(d, rows, row_ivec, s); return; }
+}
+
+void GemmNoInstantiation(const GemmLaunch &p) {
+  char what[160];
+  Fail(std::string("layer GEMM: no kernel instantiation for the planned launch ") + DescribeGemmLaunch(p, what, sizeof(what)));
+}
+
+// compute units of the device, asked once per process (256 where the query fails)
+static int GemmNumCu() {
   static int num_cu = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n > 0 ? n : 256;
   }();
-  // tile height: the one whose busiest CU does the least work; at equal work the shorter tile wins (more workgroups
-  // per CU hide the staging latency better: measured 808 vs 848 us on the output layer for 64- vs 128-row tiles)
-  auto cost = [&](int bm, int bn) {
-    const long tiles = (long)((rows + bm - 1) / bm) * ((d.n + bn - 1) / bn);
-    const double pref = bm == 64 ? 0.97 : (bm == 96 ? 0.985 : 1.0);
-    return (double)(((tiles + num_cu - 1) / num_cu) * bm * bn) * pref;
-  };
-  if (d.n <= 64) {
-    static int narrow_bm = [] { const char *e = TuneEnv("RS_GEMM_NARROW_BM"); return e ? std::atoi(e) : 0; }();
-    if (narrow_bm ? narrow_bm == 64 : cost(64, 64) < cost(128, 64)) LaunchGemmT<1, 4, 1>(d, rows, row_ivec, s);
-    else LaunchGemmT<2, 4, 1>(d, rows, row_ivec, s);
-    return;
-  }
-  double c128 = cost(128, 128), c96 = cost(96, 128), c64 = cost(64, 128);
-  static int force_bm = [] { const char *e = TuneEnv("RS_GEMM_BM"); return e ? std::atoi(e) : 0; }();
-  if (force_bm == 128) c128 = 0; else if (force_bm == 96) c96 = 0; else if (force_bm == 64) c64 = 0;
-  if (c128 <= c96 && c128 <= c64) LaunchGemmT<4, 2, 2>(d, rows, row_ivec, s);
-  else if (c96 <= c64) LaunchGemmT<3, 2, 2>(d, rows, row_ivec, s);
-  else LaunchGemmT<2, 2, 2>(d, rows, row_ivec, s);
+  return num_cu;
 }
 
-// true when the kernel LaunchGemm picks for d writes d.out_img itself (the split-bf16 kernels' epilogue does)
-bool GemmWritesImage(const GemmDev &d) { return GemmB3IUsable(d) || GemmB3Usable(d); }
+static void DispatchGemm(const GemmLaunch &p, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s) {
+  switch (p.family) {
+    case GemmLaunch::kExact: return DispatchGemmExact(p, d, rows, row_ivec, s);
+    case GemmLaunch::kB3: return DispatchGemmB3(p, d, rows, row_ivec, s);
+    case GemmLaunch::kB3I: return DispatchGemmB3I(p, d, rows, s);
+    case GemmLaunch::kB3J: return DispatchGemmB3J(p, d, rows, s);
+  }
+}
+
+void LaunchGemm(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw) {
+  if (rows <= 0) return;
+  const GemmLaunch p = PlanGemmLaunch(d, rows, GemmNumCu(), sw ? *sw : ReadGemmSwitches());
+  if (!p.residual_pass) return DispatchGemm(p, d, rows, row_ivec, s);
+  DispatchGemm(p, GemmWithoutResidual(d), rows, row_ivec, s);      // (the kernel's epilogue does not add a folded residual)
+  LaunchResidualAdd(d, rows, s);
+}
 
 // ------------------------------------------------------------------------------------------ elementwise
 __global__ void EltwiseKernel(EltwiseDev d, int rows) {
