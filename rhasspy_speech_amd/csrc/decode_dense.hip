@@ -10,8 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <cfloat>
 #include <cmath>
-#include <cstdlib>
-#include "env.h"
+#include <string>
+#include "kaldi_io.h"
 
 #include "decode_common.h"
 
@@ -25,17 +25,7 @@ namespace rs {
 
 using namespace dd;
 
-static inline size_t Al16(size_t x) { return (x + 15) & ~(size_t)15; }
-size_t DenseDecodeSmemBytes(int S, int P) {
-  // cost_cur (f32) + key_next (u64) per state, one log-likelihood row, 16-byte aligned carve-outs
-  return Al16((size_t)S * 8) + Al16((size_t)S * 4) + Al16((size_t)P * 4);
-}
-// bytes of the reverse graph when it is cached in LDS as well
-static size_t RevGraphSmemBytes(int S, int n_e, int n_x, int n_eps_dst) {
-  return 2 * Al16((size_t)(S + 1) * 4) + Al16((size_t)n_e * 16) + Al16((size_t)n_x * 16) + Al16((size_t)n_eps_dst * 4);
-}
-static const size_t kDenseSmemBudget = 144 * 1024;
-bool DenseDecodeFits(int S, int P) { return DenseDecodeSmemBytes(S, P) + sizeof(Red<4>) + 1024 <= kDenseSmemBudget; }
+static_assert(kDenseRedBytes == sizeof(Red<4>), "search_dev.h: the planner budgets LDS with the size of DenseDecodeKernel<256, .>'s static part");
 
 // NT = 256: one workgroup of four waves per utterance (larger graphs).  NT = 64: ONE WAVEFRONT per utterance --
 // every __syncthreads() below is then elided by the compiler (single-wave workgroup) and all reductions are
@@ -49,16 +39,15 @@ __global__ __launch_bounds__(NT) void DenseDecodeKernel(HclgDev h, RevGraphDev r
   const int u = blockIdx.x, tid = threadIdx.x;
   const int T = g.d_num_frames[u], S = h.num_states;
   unsigned long long *key_next = reinterpret_cast<unsigned long long *>(smem);
-  float *cost_cur = reinterpret_cast<float *>(smem + (((size_t)S * 8 + 15) & ~(size_t)15));
-  float *llr = reinterpret_cast<float *>(smem + (((size_t)S * 8 + 15) & ~(size_t)15) + (((size_t)S * 4 + 15) & ~(size_t)15));
+  float *cost_cur = reinterpret_cast<float *>(smem + lds::DenseCost(S));
+  float *llr = reinterpret_cast<float *>(smem + lds::DenseLoglikes(S));
   // reverse graph: cached in LDS when it fits (every frame re-reads it several times), else read through L1/L2
   const int n_e = rgg.in_begin_e_host_total, n_x = rgg.in_begin_x_host_total;
-  unsigned char *gp = smem + (((size_t)S * 8 + 15) & ~(size_t)15) + (((size_t)S * 4 + 15) & ~(size_t)15) + (((size_t)P * 4 + 15) & ~(size_t)15);
-  uint32_t *l_be = reinterpret_cast<uint32_t *>(gp);
-  uint32_t *l_bx = reinterpret_cast<uint32_t *>(gp + (((size_t)(S + 1) * 4 + 15) & ~(size_t)15));
-  int4 *l_ie = reinterpret_cast<int4 *>(gp + 2 * (((size_t)(S + 1) * 4 + 15) & ~(size_t)15));
-  int4 *l_ix = reinterpret_cast<int4 *>(reinterpret_cast<unsigned char *>(l_ie) + (((size_t)n_e * 16 + 15) & ~(size_t)15));
-  int *l_ed = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(l_ix) + (((size_t)n_x * 16 + 15) & ~(size_t)15));
+  uint32_t *l_be = reinterpret_cast<uint32_t *>(smem + lds::DenseGraph(S, P));
+  uint32_t *l_bx = reinterpret_cast<uint32_t *>(smem + lds::DenseGraphBeginX(S, P));
+  int4 *l_ie = reinterpret_cast<int4 *>(smem + lds::DenseGraphInE(S, P));
+  int4 *l_ix = reinterpret_cast<int4 *>(smem + lds::DenseGraphInX(S, P, n_e));
+  int *l_ed = reinterpret_cast<int *>(smem + lds::DenseGraphEpsDst(S, P, n_e, n_x));
   if (GRAPH_IN_LDS) {
     for (int i = tid; i <= S; i += NT) { l_be[i] = rgg.in_begin_e[i]; l_bx[i] = rgg.in_begin_x[i]; }
     for (int i = tid; i < n_e; i += NT) l_ie[i] = rgg.in_e[i];
@@ -254,20 +243,10 @@ __global__ __launch_bounds__(NT) void DenseDecodeKernel(HclgDev h, RevGraphDev r
 #endif
 }
 
+// the planned shape -> its instantiation (workgroup size, graph in LDS or not, LDS bytes: search_plan.cc)
 void LaunchDecodeDense(const HclgDev &h, const RevGraphDev &r, const DecodeOptsDev &o, const BatchGeom &g,
-                       const float *loglikes, int ld, int num_pdfs, const DenseWork &w, hipStream_t s) {
+                       const float *loglikes, int ld, int num_pdfs, const DenseWork &w, const DenseLaunch &p, hipStream_t s) {
   if (g.n_utts == 0) return;
-  size_t smem = DenseDecodeSmemBytes(h.num_states, num_pdfs);
-  const size_t with_graph = smem + RevGraphSmemBytes(h.num_states, r.in_begin_e_host_total, r.in_begin_x_host_total, r.num_eps_dst);
-  const bool graph_in_lds = with_graph + sizeof(Red<4>) + 1024 <= kDenseSmemBudget;
-  if (graph_in_lds) smem = with_graph;
-  // RS_DENSE_NT selects the workgroup size per utterance (64 / 256 / 1024); measured on MI355X (625-state grammar graph,
-  // 298 frames): 64 -> 18 us/frame, 256 -> 10 us/frame: the frame is a chain of dependent LDS reads, more lanes hide more.
-  static int nt_env = [] { const char *e = TuneEnv("RS_DENSE_NT"); return e ? std::atoi(e) : 256; }();
-  const bool one_wave = nt_env == 64 && h.num_states <= 4096 && num_pdfs <= 2048;
-  const bool big = nt_env == 1024;
-  const size_t stage_min = one_wave ? 40 * 1024 : 64 * 1024;     // room to stage back-pointer rows for the traceback
-  if (smem < stage_min) smem = stage_min;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&DenseDecodeKernel<256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
@@ -278,11 +257,11 @@ void LaunchDecodeDense(const HclgDev &h, const RevGraphDev &r, const DecodeOptsD
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&DenseDecodeKernel<64, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     attr_set = true;
   }
-#define RS_DD(NTV, GV) hipLaunchKernelGGL((DenseDecodeKernel<NTV, GV>), dim3(g.n_utts), dim3(NTV), smem, s, h, r, o, g, loglikes, ld, num_pdfs, w, (int)smem)
-  if (one_wave) { if (graph_in_lds) RS_DD(64, true); else RS_DD(64, false); }
-  else if (big) { if (graph_in_lds) RS_DD(1024, true); else RS_DD(1024, false); }
-  else { if (graph_in_lds) RS_DD(256, true); else RS_DD(256, false); }
+  const size_t smem = p.lds_bytes;
+#define RS_DD(NTV, GV) if (p.nt == NTV && p.graph_in_lds == GV) { hipLaunchKernelGGL((DenseDecodeKernel<NTV, GV>), dim3(g.n_utts), dim3(NTV), smem, s, h, r, o, g, loglikes, ld, num_pdfs, w, (int)smem); return; }
+  RS_DD(64, true); RS_DD(64, false); RS_DD(256, true); RS_DD(256, false); RS_DD(1024, true); RS_DD(1024, false);
 #undef RS_DD
+  Fail("search: no DenseDecodeKernel<" + std::to_string(p.nt) + "," + std::to_string((int)p.graph_in_lds) + ">");
 }
 
 }  // namespace rs

@@ -52,9 +52,7 @@ namespace rs {
 using namespace tok;
 namespace {
 
-constexpr int kGlobalLog = 15;                      // second-level table: 32768 entries (tag + key) per utterance in global memory
-constexpr int kGlobalSize = 1 << kGlobalLog;
-constexpr int kSlotCap = 24576;                     // live states / tokens per frame (records name a token of a frame in 16 bits)
+constexpr int kGlobalLog = kLiveGlobalLog, kGlobalSize = kLiveGlobalSize, kSlotCap = kLiveSlotCap;      // (search_dev.h: the host sizes the arrays with them)
 constexpr unsigned kFree = 0xFFFFFFFFu;
 #ifndef RS_LIVE_BUCKETS
 #define RS_LIVE_BUCKETS 3
@@ -251,7 +249,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                                                        const float *__restrict__ loglikes, int ld, DecodeWork w) {
   using Ctx = LiveCtx<NT>;
   constexpr int NW = NT / 64;
-  static_assert(HS % 4 == 0 && HS + kGlobalSize <= 65536, "slots are named in 16 bits");
+  static_assert(HS % 4 == 0 && HS + kGlobalSize <= kLiveTableSize, "slots are named in 16 bits");
   // One LDS object with the workgroup's scalars FIRST: an LDS word at a constant address below 64 KB is a zero base register plus
   // an instruction offset; laid out by the linker the scalars sat behind the table (0x27090...) and every one of them that a loop
   // touches held a VGPR with its address for the whole kernel -- fifteen of the 128 a wave of this workgroup has, with spills.
@@ -892,12 +890,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 }
 
 }  // namespace
-
-bool DecodeLiveUsable(const HclgDev &h) { return h.num_states > 0 && h.arcs_f != nullptr && h.nodes != nullptr && h.num_arcs < (1 << 30); }
-int DecodeLiveSlotCap() { return kSlotCap; }
-int DecodeLiveGlobalTable() { return kGlobalSize; }
-// length of the slot-indexed arrays (a slot is the position of the state's table entry: LDS part, then the global part)
-int DecodeLiveTableSize() { return 65536; }
 
 void LaunchDecodeLive(const HclgDev &h, const DecodeOptsDev &o, const BatchGeom &g, const float *loglikes, int ld,
                       const DecodeWork &w, hipStream_t s) {

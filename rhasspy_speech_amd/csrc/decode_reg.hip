@@ -20,11 +20,9 @@
 #include "decode_common.h"
 #include "decode_tok.h"
 #include "wave_ops.h"
-#include "env.h"
+#include "kaldi_io.h"
 
 #include <string>
-
-#include <cstdlib>
 
 namespace rs {
 using namespace dd;
@@ -513,7 +511,7 @@ __global__ __launch_bounds__(NT) void RegDecodeKernel(HclgDev h, RegGraphDev rg,
 //     position + one prefix sum of the masks' populations.
 // Everything else -- GetCutoff on all tokens of the list, the closure against the final cutoff, ties, back-pointers -- is the
 // reference's already.  Costs equal the CPU oracle's (oracle/decoder.c follows the hash order too) bit for bit.
-// Eligible graphs: <= 1000 states, epsilon depth <= 1, at most 32 emitting and 32 epsilon arcs per state (RegGraphDev::exact_ok).
+// Eligible graphs: <= 1000 states, epsilon depth <= 1, at most 32 emitting and 32 epsilon arcs per state (SearchLoad::exact_ok).
 // Seven block-wide steps more per frame than RegDecodeKernel and 14 S + 4 E bytes of LDS: rs_decode_opts.exact_token_order.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ unsigned DppId(unsigned v, unsigned ident) {
@@ -591,9 +589,8 @@ __global__ __launch_bounds__(NT) void RegDecodeExactKernel(HclgDev h, RegGraphDe
   float *cost_cur = reinterpret_cast<float *>(smem);
   unsigned long long *key_next = reinterpret_cast<unsigned long long *>(smem + rg.key_base);
   // the order's arrays, behind the keys
-  const int xb = (rg.key_base + 8 * (S + 1) + 15) & ~15;
-  unsigned short *rank16 = reinterpret_cast<unsigned short *>(smem + xb);                       // position of a state's token in the frame's list
-  unsigned *fkey = reinterpret_cast<unsigned *>(smem + xb + ((2 * S + 15) & ~15));               // smallest insertion key of the frame under construction
+  unsigned short *rank16 = reinterpret_cast<unsigned short *>(smem + lds::RegOrderRank(rg.key_base, S));      // position of a state's token in the frame's list
+  unsigned *fkey = reinterpret_cast<unsigned *>(smem + lds::RegOrderKeys(rg.key_base, S));      // smallest insertion key of the frame under construction
   unsigned *ordm = fkey + S;                                                                     // per list position: min over the token's arcs of tot + adaptive_beam; later the prefix sums
   unsigned *maskE = ordm + S;                                                                    // per source position: which of its arcs inserted a state first
   float *arcv = reinterpret_cast<float *>(maskE + S);                                            // per emitting arc (table order): tot + adaptive_beam
@@ -894,23 +891,16 @@ __global__ __launch_bounds__(NT) void RegDecodeExactKernel(HclgDev h, RegGraphDe
 
 template <int NT, int KE, int KX>
 static void LaunchOne(const HclgDev &h, const RegGraphDev &r, const DecodeOptsDev &o, const BatchGeom &g, const float *loglikes, int ld,
-                      const DenseWork &w, size_t smem, int f_begin, int f_end, hipStream_t s) {
+                      const DenseWork &w, const RegLaunch &p, int f_begin, int f_end, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&RegDecodeKernel<NT, KE, KX>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&RegDecodeExactKernel<NT, KE, KX>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     attr_set = true;
   }
-  if (o.exact_order && r.exact_ok && h.num_states <= 4 * NT) {
-    // the order's arrays behind the keys (RegDecodeExactKernel): list positions, insertion keys, per-position minima / sums, masks, per-arc values
-    const int S = h.num_states, E = NT * KE;
-    const size_t xb = ((size_t)r.key_base + 8 * (size_t)(S + 1) + 15) & ~(size_t)15;
-    const size_t need = xb + (((size_t)2 * S + 15) & ~(size_t)15) + (size_t)12 * S + (size_t)4 * (E > S ? E : S);
-    const size_t sm = smem > need ? smem : need;
-    hipLaunchKernelGGL((RegDecodeExactKernel<NT, KE, KX>), dim3(g.n_utts), dim3(NT), sm, s, h, r, o, g, loglikes, ld, w, (int)sm, f_begin, f_end);
-    return;
-  }
-  hipLaunchKernelGGL((RegDecodeKernel<NT, KE, KX>), dim3(g.n_utts), dim3(NT), smem, s, h, r, o, g, loglikes, ld, w, (int)smem, f_begin, f_end);
+  const size_t smem = p.lds_bytes;
+  if (p.exact) hipLaunchKernelGGL((RegDecodeExactKernel<NT, KE, KX>), dim3(g.n_utts), dim3(NT), smem, s, h, r, o, g, loglikes, ld, w, (int)smem, f_begin, f_end);
+  else hipLaunchKernelGGL((RegDecodeKernel<NT, KE, KX>), dim3(g.n_utts), dim3(NT), smem, s, h, r, o, g, loglikes, ld, w, (int)smem, f_begin, f_end);
 }
 
 // Dense rows -> token lists.  Three launches, the two that read the rows parallel over (utterance, frame): a wave per frame counts its
@@ -996,7 +986,6 @@ void LaunchDenseToTokens(const HclgDev &h, const BatchGeom &g, const DenseWork &
 // log-likelihoods are requested a frame ahead.  Token numbers are DenseWriteKernel's: the live states of a frame in state order
 // behind frame_tok_off (frame 0: the start state first).  A frame is ~6 barriers of LDS work; the token-list kernel's frame was
 // ~11 barriers with two to four dependent global round trips in each phase (2.3 ms per 256 x 298 frames).
-constexpr int kDLMaxStates = 2048, kDLMaxArcs = 8192;
 #ifdef RS_DL_PROFILE
 #define RS_DLP(i) do { const long long _n = clock64(); if (tid == 0) dlp[i] += _n - dl_last; dl_last = _n; } while (0)
 #else
@@ -1021,8 +1010,8 @@ __global__ __launch_bounds__(NT) void DenseLatticeKernel(HclgDev h, DecodeOptsDe
   LatArc *my_arcs = lw.arcs + (size_t)u * lw.utt_cap;
   const int S = h.num_states, A = h.num_arcs;
   float *cost_a = reinterpret_cast<float *>(dl_smem), *cost_b = cost_a + S, *cost_c = cost_b + S;
-  unsigned *ex_a = reinterpret_cast<unsigned *>(cost_c + S), *ex_b = ex_a + S;
-  unsigned short *rk_a = reinterpret_cast<unsigned short *>(ex_b + S), *rk_b = rk_a + S;
+  unsigned *ex_a = reinterpret_cast<unsigned *>(dl_smem + lds::DenseLatticeExtra(S)), *ex_b = ex_a + S;
+  unsigned short *rk_a = reinterpret_cast<unsigned short *>(dl_smem + lds::DenseLatticeRank(S)), *rk_b = rk_a + S;
   const int *frame_off = w.frame_tok_off + (size_t)u * (g.max_frames + 2);
   const float *finfo = dw.frame_info + (size_t)u * (g.max_frames + 1) * 4;
   const float *rows = dw.cost_rows + (size_t)u * (g.max_frames + 1) * S;
@@ -1268,80 +1257,27 @@ __global__ __launch_bounds__(NT) void DenseLatticeKernel(HclgDev h, DecodeOptsDe
 #endif
 }
 
-bool DenseLatticeUsable(const HclgDev &h) {
-  const char *e = std::getenv("RS_LATTICE_KERNEL");      // "tokens": the token-list kernel (read per call: a test compares the two)
-  if (e && std::string(e) == "tokens") return false;
-  return h.num_states <= kDLMaxStates && h.num_arcs <= kDLMaxArcs;
-}
-
+// the planned shape -> its instantiation (PlanSearchCall walks the arcs-per-thread ladder: search_plan.cc)
 void LaunchDenseLattice(const HclgDev &h, const DecodeOptsDev &o, const BatchGeom &g, const float *loglikes, int ld, const DenseWork &dw,
-                        const DecodeWork &w, const LatticeWork &lw, int eps_rounds, hipStream_t s) {
+                        const DecodeWork &w, const LatticeWork &lw, const DenseLatticeLaunch &p, hipStream_t s) {
   if (g.n_utts == 0) return;
-  { const char *e = std::getenv("RS_LATTICE_KERNEL"); if (e && std::string(e) == "vote" && eps_rounds != 0) eps_rounds = -1; }      // (tests: closure rounds until nothing changes)
-  const size_t smem = (size_t)h.num_states * (3 * 4 + 2 * 4 + 2 * 2) + 16;
-  // 512 threads: a wave alone on its SIMD issues an instruction every ~10 cycles whatever it is, and a frame is per-arc instructions
-  // (256 / 512 / 1024 threads: 1.9 / 1.3 / 1.3 ms per 256 x 298 frames, profiles/micro/dl_nt.sh; RS_DL_NT in a -DRS_TUNING build)
-  static const int nt = [] { const char *e = TuneEnv("RS_DL_NT"); const int v = e ? std::atoi(e) : 512; return v == 256 || v == 1024 ? v : 512; }();
-  const int ka = (h.num_arcs + nt - 1) / nt;
   const dim3 grid(g.n_utts);
-#define RS_DL(NT, KA) hipLaunchKernelGGL((DenseLatticeKernel<NT, KA>), grid, dim3(NT), smem, s, h, o, g, loglikes, ld, dw, w, lw, eps_rounds)
-  if (nt == 1024) { if (ka <= 1) RS_DL(1024, 1); else if (ka <= 2) RS_DL(1024, 2); else if (ka <= 3) RS_DL(1024, 3); else if (ka <= 4) RS_DL(1024, 4); else if (ka <= 6) RS_DL(1024, 6); else RS_DL(1024, 8); }
-  else if (nt == 512) { if (ka <= 2) RS_DL(512, 2); else if (ka <= 4) RS_DL(512, 4); else if (ka <= 6) RS_DL(512, 6); else if (ka <= 8) RS_DL(512, 8); else if (ka <= 12) RS_DL(512, 12); else RS_DL(512, 16); }
-  else { if (ka <= 4) RS_DL(256, 4); else if (ka <= 8) RS_DL(256, 8); else if (ka <= 12) RS_DL(256, 12); else if (ka <= 16) RS_DL(256, 16); else if (ka <= 24) RS_DL(256, 24); else RS_DL(256, 32); }
+#define RS_DL(NT, KA) if (p.nt == NT && p.ka == KA) { hipLaunchKernelGGL((DenseLatticeKernel<NT, KA>), grid, dim3(NT), p.lds_bytes, s, h, o, g, loglikes, ld, dw, w, lw, p.eps_rounds); return; }
+  RS_DL(1024, 1); RS_DL(1024, 2); RS_DL(1024, 3); RS_DL(1024, 4); RS_DL(1024, 6); RS_DL(1024, 8);
+  RS_DL(512, 2); RS_DL(512, 4); RS_DL(512, 6); RS_DL(512, 8); RS_DL(512, 12); RS_DL(512, 16);
+  RS_DL(256, 4); RS_DL(256, 8); RS_DL(256, 12); RS_DL(256, 16); RS_DL(256, 24); RS_DL(256, 32);
 #undef RS_DL
+  Fail("lattice: no DenseLatticeKernel<" + std::to_string(p.nt) + "," + std::to_string(p.ka) + ">");
 }
 
-// the instantiations; RegDecodeConfig picks the first one the graph fits.  Workgroup size measured on MI355X (625-state
-// grammar graph, 298 frames): 64 threads 7.5 us/frame, 256 -> 4.2, 512 -> 3.7, 1024 -> 5.1: the per-lane instruction count
-// dominates until the barriers of 16 waves take over.
-static const int kRegConfigs[][3] = {{512, 4, 2}, {256, 8, 4}, {512, 8, 4}, {256, 16, 8}, {256, 32, 16}};
-
-bool RegDecodeConfig(int num_states, int num_emitting, int num_eps, int *nt, int *ke, int *kx) {
-  if (num_states > kRegMaxStates) return false;
-  static int force_nt = [] { const char *e = TuneEnv("RS_REG_NT"); return e ? std::atoi(e) : 0; }();
-  for (const auto &c : kRegConfigs) {
-    if (force_nt && c[0] != force_nt) continue;
-    if ((long long)c[0] * c[1] >= num_emitting && (long long)c[0] * c[2] >= num_eps) { *nt = c[0]; *ke = c[1]; *kx = c[2]; return true; }
-  }
-  return false;
-}
-
-bool LaunchDecodeReg(const HclgDev &h, const RegGraphDev &r, const DecodeOptsDev &o_in, const BatchGeom &g,
-                     const float *loglikes, int ld, const DenseWork &w, int f_begin, int f_end, hipStream_t s, bool any_final) {
-  if (g.n_utts == 0) return true;
-  DecodeOptsDev o = o_in;
-  { const char *e = std::getenv("RS_REG_NO_HIST"); o.no_commit_hist = e && std::atoi(e) != 0 ? 1 : 0; }      // (read per launch: a test flips it)
-  size_t smem = (size_t)r.key_base + (size_t)(h.num_states + 1) * 8;
-  // room to stage back-pointer rows for the traceback.  48 KB, not more: with 128 KB a search workgroup left no room for
-  // the GEMM workgroups (33 KB each) of the next decode call on its CU, and the overlap of calls in flight was limited to
-  // the feature / iVector stages (3.7 ms per headline batch against 3.35 with 48 KB; the search itself takes the same
-  // time).  A slab that finishes no utterance does not trace back and keeps its LDS footprint minimal.
-  // (12 KB since the calls' stages are chained, engine.cc: 2.51 -> 2.47-2.49 ms per headline step; 4-16 KB are within 1 % of each other.
-  // Round 4: 32 KB -- the 16-bit arc -> source table now sits in front of the rows, and the layer GEMM's 72 KB leave one of its
-  // workgroups room beside a search whatever this is; 12 / 20 / 32 / 44 KB: search 1.26 / 1.23 / 1.20 / 1.20 ms, profiles/micro/stage_kb.sh)
-  static const size_t stage_kb = [] { const char *e = TuneEnv("RS_DECODE_STAGE_KB"); return e ? (size_t)std::atoi(e) : 32; }();
-  const size_t stage = (w.win_begin ? !any_final : f_end <= g.max_frames) ? 0 : stage_kb * 1024;
-  if (smem < stage) smem = stage;
-  // A batch that puts a search workgroup on (nearly) every CU shares those CUs with the GEMM workgroups of the next call: with
-  // half the waves and twice the arcs per thread the search alone is 8 % slower (1.12 -> 1.21 ms for 256 x 3 s) and the step with
-  // calls in flight 2.5 % faster (2.51 -> 2.45 ms together with the smaller traceback staging below).  The tables are the same --
-  // arc i sits in slot i of e_tab / x_tab whatever the shape.  RS_REG_NT pins the shape chosen at load.
-  static const bool pinned = TuneEnv("RS_REG_NT") != nullptr;
-  static const int num_cu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  const bool crowded = !pinned && !w.win_begin && 4 * (long)g.n_utts >= 3 * (long)num_cu;
-  if (crowded && r.nt == 512 && r.ke == 4 && r.kx == 2) LaunchOne<256, 8, 4>(h, r, o, g, loglikes, ld, w, smem, f_begin, f_end, s);
-  else if (crowded && r.nt == 512 && r.ke == 8 && r.kx == 4) LaunchOne<256, 16, 8>(h, r, o, g, loglikes, ld, w, smem, f_begin, f_end, s);
-  else if (r.nt == 512 && r.ke == 4 && r.kx == 2) LaunchOne<512, 4, 2>(h, r, o, g, loglikes, ld, w, smem, f_begin, f_end, s);
-  else if (r.nt == 512 && r.ke == 8 && r.kx == 4) LaunchOne<512, 8, 4>(h, r, o, g, loglikes, ld, w, smem, f_begin, f_end, s);
-  else if (r.nt == 256 && r.ke == 16 && r.kx == 8) LaunchOne<256, 16, 8>(h, r, o, g, loglikes, ld, w, smem, f_begin, f_end, s);
-  else if (r.nt == 256 && r.ke == 32 && r.kx == 16) LaunchOne<256, 32, 16>(h, r, o, g, loglikes, ld, w, smem, f_begin, f_end, s);
-  else if (r.nt == 256 && r.ke == 8 && r.kx == 4) LaunchOne<256, 8, 4>(h, r, o, g, loglikes, ld, w, smem, f_begin, f_end, s);
-  else return false;
-  return true;
+// the planned shape -> its instantiation (the shapes a graph can get and the crowded rule: search_plan.cc)
+void LaunchDecodeReg(const HclgDev &h, const RegGraphDev &r, const DecodeOptsDev &o, const BatchGeom &g,
+                     const float *loglikes, int ld, const DenseWork &w, const RegLaunch &p, int f_begin, int f_end, hipStream_t s) {
+  if (g.n_utts == 0) return;
+#define RS_REG(NT, KE, KX) if (p.nt == NT && p.ke == KE && p.kx == KX) return LaunchOne<NT, KE, KX>(h, r, o, g, loglikes, ld, w, p, f_begin, f_end, s)
+  RS_REG(512, 4, 2); RS_REG(256, 8, 4); RS_REG(512, 8, 4); RS_REG(256, 16, 8); RS_REG(256, 32, 16);
+#undef RS_REG
+  Fail("search: no RegDecodeKernel<" + std::to_string(p.nt) + "," + std::to_string(p.ke) + "," + std::to_string(p.kx) + ">");
 }
 
 }  // namespace rs

@@ -192,15 +192,8 @@ void Model::EndpointOpts(rs_endpoint_opts *o) const {
 Model::Model(const std::string &final_mdl, const std::string &hclg, const std::string &online_conf,
              const rs_decode_opts &opts)
     : opts_(opts) {
-  if (const char *e = TuneEnv("RS_FORCE_SPARSE_DECODER")) force_sparse_ = e[0] == '1';
+  search_sw_ = ReadSearchSwitches();      // (RS_DECODER, RS_FORCE_SPARSE_DECODER: fixed for this model from here on)
   if (const char *e = std::getenv("RS_SUBBATCHES")) max_groups_ = std::atoi(e);
-  if (const char *e = std::getenv("RS_DECODER")) {
-    const std::string v(e);
-    // reg / dense: the LDS-resident searches of small graphs; sparse: DecodeKernel alone (dense per-state tables in HBM); hash: the
-    // token-list search with the live-state table, which is what "auto" runs on graphs the first two cannot hold
-    decoder_choice_ = v == "reg" ? 1 : v == "dense" ? 2 : v == "sparse" ? 3 : v == "hash" ? 4 : 0;
-    if (decoder_choice_ >= 3) force_sparse_ = true;
-  }
   ReadFeatureConfig(online_conf, &fc_);
   ResolveDecoderOptions();
   am_.Read(final_mdl, opts_.frames_per_chunk, 0, opts_.frame_subsampling_factor);
@@ -746,8 +739,6 @@ void Model::ToDevice() {
     hclg_dev_.start = hclg_.start;
     hclg_dev_.arc_begin = Upload(hclg_.arc_begin);
     hclg_dev_.num_ieps = Upload(hclg_.num_ieps);
-    hclg_has_eps_ = false;
-    for (auto n : hclg_.num_ieps) hclg_has_eps_ = hclg_has_eps_ || n != 0;
     {
       const int S = hclg_.num_states();
       std::vector<uint4> rec(S);
@@ -786,9 +777,18 @@ void Model::ToDevice() {
       hclg_dev_.arc_srcx = Upload(srcx);
     }
     hclg_dev_.final_cost = Upload(hclg_.final_cost);
+    // what the searches may do on this graph (search_plan.h)
+    search_graph_.states = hclg_.num_states(); search_graph_.arcs = (int)A; search_graph_.pdfs = am_.nnet.output_dim;
+    search_graph_.live_tables = hclg_dev_.arcs_f != nullptr && hclg_dev_.nodes != nullptr;
+    {
+      std::vector<int> dst(A);
+      std::vector<unsigned char> emitting(A);
+      for (size_t a = 0; a < A; a++) { dst[a] = arcs[a].w; emitting[a] = arcs[a].x != 0; }
+      WalkSearchGraph(src.data(), dst.data(), emitting.data(), A, &search_graph_);
+    }
+    search_load_ = PlanSearchLoad(search_graph_, search_sw_);
     // reverse graph for the dense (pull) decoder: in-arcs per destination state, in forward-arc order
-    dense_ok_ = DenseDecodeFits(hclg_.num_states(), am_.nnet.output_dim);
-    if (dense_ok_) {
+    if (search_load_.dense_ok) {
       const int S = hclg_.num_states();
       std::vector<uint32_t> be(S + 1, 0), bx(S + 1, 0);
       for (size_t a = 0; a < A; a++) (hclg_.arcs[a].ilabel == 0 ? bx : be)[hclg_.arcs[a].nextstate + 1]++;
@@ -811,10 +811,8 @@ void Model::ToDevice() {
       rev_dev_.in_begin_e_host_total = (int)ie.size();
       rev_dev_.in_begin_x_host_total = (int)ix.size();
       // register-resident variant (decode_reg.hip): arcs dealt out to threads in forward order
-      const int P = am_.nnet.output_dim;
-      int nt = 0, ke = 0, kx = 0;
-      if (P > 0 && RegDecodeConfig(S, (int)ie.size(), (int)ix.size(), &nt, &ke, &kx)) {
-        const int key_base = (int)(((size_t)(S + 1) * 4 + 15) & ~(size_t)15);
+      if (search_load_.nt != 0) {
+        const int nt = search_load_.nt, ke = search_load_.ke, kx = search_load_.kx, key_base = search_load_.key_base;
         const int pad_e = (4 * S) | ((key_base + 8 * S) << 16), pad_x = (key_base + 8 * S + 4) | ((key_base + 8 * S) << 16);
         std::vector<int4> et((size_t)ke * nt, make_int4(pad_e, 0, 0, 0)), xt((size_t)kx * nt, make_int4(pad_x, 0, 0, 0));
         std::vector<int> eaux((size_t)ke * nt, 0), xaux((size_t)kx * nt, 0);
@@ -832,30 +830,13 @@ void Model::ToDevice() {
             et[ne++] = make_int4((4 * src[a]) | dst_addr, fa.x - 1, fa.z, (int)a);
           }
         }
-        int max_e = 0, max_x = 0;
-        for (int st = 0; st < S; st++) { max_e = std::max(max_e, cnt_e[st]); max_x = std::max(max_x, cnt_x[st]); }
-        // longest path of the epsilon subgraph = number of closure rounds; cyclic or deep -> the kernel votes instead
-        int depth = 0;
-        {
-          std::vector<int> indeg(S, 0), len(S, 0), order;
-          std::vector<std::vector<int>> out(S);
-          for (size_t a = 0; a < A; a++) if (arcs[a].x == 0) { out[src[a]].push_back(arcs[a].w); indeg[arcs[a].w]++; }
-          for (int st = 0; st < S; st++) if (indeg[st] == 0) order.push_back(st);
-          for (size_t i = 0; i < order.size(); i++)
-            for (int d : out[order[i]]) { len[d] = std::max(len[d], len[order[i]] + 1); if (--indeg[d] == 0) order.push_back(d); }
-          if ((int)order.size() < S) depth = -1;
-          else { for (int st = 0; st < S; st++) depth = std::max(depth, len[st]); if (depth > 6) depth = -1; }
-        }
         reg_dev_.nt = nt; reg_dev_.ke = ke; reg_dev_.kx = kx;
-        reg_dev_.eps_depth = depth;
+        reg_dev_.eps_depth = search_load_.eps_rounds;
         reg_dev_.key_base = key_base;
         reg_dev_.e_tab = static_cast<int4 *>(UploadBytes(et.data(), et.size() * sizeof(int4)));
         reg_dev_.x_tab = static_cast<int4 *>(UploadBytes(xt.data(), xt.size() * sizeof(int4)));
         reg_dev_.e_aux = Upload(eaux);
         reg_dev_.x_aux = Upload(xaux);
-        // the reference's token order can be followed exactly where its hash table cannot collide (it starts with 1000 buckets),
-        // the closure is one round, and a state's arcs fit one 32-bit mask (decode_reg.hip: RegDecodeExactKernel)
-        reg_dev_.exact_ok = (S <= 1000 && depth >= 0 && depth <= 1 && max_e <= 32 && max_x <= 32) ? 1 : 0;
       }
     }
   }
@@ -900,8 +881,9 @@ std::string Model::Describe() const {
      << " frame_subsampling_factor=" << opts_.frame_subsampling_factor << "\n";
   // (state, not structure: calls repeated on the exact-FP32 layer GEMMs because an activation left the fp16 split's range, and
   // whether the model has changed to those kernels for good)
-  os << "token_order: " << (ExactOrder() && reg_dev_.exact_ok ? "exact (the reference's running cutoff in its hash order)" : "final cutoff")
-     << (ExactOrder() && !reg_dev_.exact_ok ? " (exact_token_order asked for: not applicable to this graph)" : "") << "\n";
+  const bool exact_asked = ExactOrder(), exact_ok = search_load_.exact_ok;
+  os << "token_order: " << (exact_asked && exact_ok ? "exact (the reference's running cutoff in its hash order)" : "final cutoff")
+     << (exact_asked && !exact_ok ? " (exact_token_order asked for: not applicable to this graph)" : "") << "\n";
   os << "layer_gemm: range_retries=" << range_retries_.load() << " precision_retries=" << precision_retries_.load() << " exact_fp32=" << (exact_gemm_.load() ? 1 : 0)
      << " regime=" << (exact_gemm_.load() ? "exact-fp32" : "split-fp16")
      << " (split-fp16 carries an operand row to 2^-22 of its largest element while that element lies in [2^-3, 65520): a row with |x| >= 65520, infinity"
@@ -1321,44 +1303,31 @@ void Model::IvecChunkChain(DeviceArena &arena, const BatchGeom &g, int n, int K,
 }
 
 // ------------------------------------------------------------------------------------------------ search
-// Which search kernel a call runs, its token capacity and options; AllocSearch / LaunchSearch take the work buffers from the call's
-// arena.  Shared by the batch path (DecodeGroup) and the end of a stream (stream.cc), whose log-likelihoods live in the stream pool.
-void Model::PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only, bool token_lists) const {
-  const int S = hclg_.num_states();
-  sp->S = S; sp->n_utts = n_utts; sp->maxT = maxT; sp->max_words = 1024;
-  // The reference un-scales the lattice's acoustic costs before lattice-to-nbest ranks its paths (online2-wav-nnet3-latgen-
-  // faster.cc:290-293), so with a decodable --acoustic-scale other than 1 even the 1-best is chosen on the lattice.
-  sp->unscale = opts_.acoustic_scale != 1.0f && opts_.acoustic_scale != 0.0f;
-  sp->want_lattice = !best_path_only && (nbest > 1 || lat_scale != 1.0f || opts_.emit_lattice != 0 || sp->unscale);      // (best_path_only: partial results)
-  sp->use_reg = reg_dev_.nt != 0 && !sp->want_lattice && !force_sparse_ && (decoder_choice_ == 0 || decoder_choice_ == 1);
-  sp->use_dense = dense_ok_ && !sp->want_lattice && !force_sparse_ && decoder_choice_ != 3;
-  if (token_lists) sp->use_reg = sp->use_dense = false;      // (endpoint queries of deferred streams read the token lists: stream.cc)
-  // A lattice needs every token of every frame, which the token-list searches keep and the register-resident one does not (5.8 ms
-  // against 1.1 for the headline batch): it leaves the costs of all (frame, state) pairs beside its back-pointer rows instead and a
-  // compaction kernel writes the token lists LatticeKernel reads (RS_LATTICE_SEARCH=tokens: the token-list search, as before round 4)
-  {
-    const char *e = std::getenv("RS_LATTICE_SEARCH");          // (read per call: a test compares the two)
-    sp->reg_lattice = sp->want_lattice && reg_dev_.nt != 0 && !force_sparse_ && (decoder_choice_ == 0 || decoder_choice_ == 1) &&
-                      !(ExactOrder() && reg_dev_.exact_ok) && !(e && std::string(e) == "tokens");
-    if (sp->reg_lattice) { sp->use_reg = true; sp->use_dense = true; }
-  }
-  int cap_pf = opts_.max_tokens_per_frame > 0 ? opts_.max_tokens_per_frame : (int)std::min<long long>(std::max(4ll * opts_.max_active, 8192ll), 0x7fffffffll);
-  cap_pf = std::min(cap_pf, S);
-  // (the register-resident search behind an n-best / lattice call keeps every live state of every frame -- it has no per-frame token
-  // limit -- and DenseToTokensKernel writes them all: the utterance's slice of the token array holds S per frame whatever
-  // max_tokens_per_frame says)
-  if (sp->reg_lattice) cap_pf = S;
-  const long tok_cap_l = (long)(maxT + 2) * cap_pf;
-  if (tok_cap_l > 0x7fffffffL) Fail("decoder token capacity overflows; lower max_tokens_per_frame");
-  sp->tok_cap = (int)tok_cap_l;
-  sp->dopts.beam = opts_.beam; sp->dopts.lattice_beam = opts_.lattice_beam; sp->dopts.beam_delta = opts_.beam_delta;
-  sp->dopts.max_active = opts_.max_active; sp->dopts.min_active = opts_.min_active;
-  sp->dopts.exact_order = ExactOrder() ? 1 : 0;
-  sp->use_hash = !sp->use_dense && decoder_choice_ != 3 && DecodeLiveUsable(hclg_dev_);      // token-list search: the live-state tables
+// Which search a call runs, its capacities and options: decided by search_plan.cc.  AllocSearch takes every work buffer of the search
+// from the call's arena, LaunchSearch issues the kernels.  Shared by the batch path (DecodeGroup) and the streams (stream.cc), whose
+// log-likelihoods live in the stream pool.
+SearchRequest Model::SearchRequestFor(int n_utts, int maxT, int nbest, float lat_scale) const {
+  SearchRequest rq;
+  rq.n_utts = n_utts; rq.maxT = maxT; rq.nbest = nbest; rq.lat_scale = lat_scale;
+  rq.beam = opts_.beam; rq.lattice_beam = opts_.lattice_beam; rq.beam_delta = opts_.beam_delta; rq.acoustic_scale = opts_.acoustic_scale;
+  rq.max_active = opts_.max_active; rq.min_active = opts_.min_active; rq.max_tokens_per_frame = opts_.max_tokens_per_frame;
+  rq.emit_lattice = opts_.emit_lattice; rq.exact_token_order = opts_.exact_token_order;
+  return rq;
 }
 
-void Model::AllocSearch(SearchPlan *sp, DeviceArena &arena_, hipStream_t s, bool pooled_frames) const {
+void Model::PlanSearch(const SearchRequest &rq, SearchPlan *sp) const {
+  const SearchCall c = PlanSearchCall(search_graph_, search_load_, rq, DeviceNumCu(), ReadSearchSwitches());
+  if (c.error) Fail(c.error);
+  sp->call = c;
+  sp->unscale = c.unscale; sp->want_lattice = c.want_lattice;
+  sp->S = c.S; sp->n_utts = c.n_utts; sp->maxT = c.maxT; sp->max_words = c.max_words; sp->tok_cap = c.tok_cap;
+  sp->dopts = c.opts;
+}
+
+void Model::AllocSearch(SearchPlan *sp, DeviceArena &arena_, hipStream_t s) const {
+  const SearchCall &c = sp->call;
   const int n_utts = sp->n_utts, maxT = sp->maxT, S = sp->S, max_words = sp->max_words;
+  const bool pooled_frames = c.windows;      // (streams keep back-pointer rows, frame info, parked costs and counters in their pool)
   DecodeWork &w = sp->w;
   std::memset(&w, 0, sizeof(w));
   w.max_words = max_words;
@@ -1369,17 +1338,17 @@ void Model::AllocSearch(SearchPlan *sp, DeviceArena &arena_, hipStream_t s, bool
   if (!pooled_frames) w.frame_info = arena_.AllocT<float>((size_t)n_utts * (maxT + 1) * 4);
   DenseWork &dw = sp->dw;
   std::memset(&dw, 0, sizeof(dw));
-  if (sp->use_dense) {
+  if (c.rows()) {
     dw.out_words = w.out_words; dw.out_nwords = w.out_nwords; dw.out_costs = w.out_costs; dw.counters = w.counters;
     dw.frame_info = w.frame_info; dw.max_words = max_words;
-    dw.path_cap = 4 * (maxT + 2);
+    dw.path_cap = c.path_cap;
     dw.path = arena_.AllocT<int>((size_t)n_utts * dw.path_cap * 2);
-    if (!pooled_frames) {      // (streams keep back-pointer rows, frame info, parked costs and counters in their pool)
+    if (!pooled_frames) {
       dw.bp = arena_.AllocT<int>((size_t)n_utts * (maxT + 1) * S);
       dw.state_cost = arena_.AllocT<float>((size_t)n_utts * (2 * (size_t)S + 4));
       RS_HIP(hipMemsetAsync(w.counters, 0, sizeof(long long) * 8 * (size_t)n_utts, s));
     }
-    if (sp->reg_lattice && !pooled_frames) {
+    if (c.rows_lattice() && !pooled_frames) {
       dw.cost_rows = arena_.AllocT<float>((size_t)n_utts * (maxT + 1) * S);
       w.tok_cap = sp->tok_cap;
       w.tokens = arena_.AllocT<int4>((size_t)n_utts * sp->tok_cap);
@@ -1389,18 +1358,9 @@ void Model::AllocSearch(SearchPlan *sp, DeviceArena &arena_, hipStream_t s, bool
       RS_HIP(hipMemsetAsync(w.map_a, 0xFF, sizeof(int) * (size_t)n_utts * S, s));      // LatticeKernel expects both state -> token maps empty
       RS_HIP(hipMemsetAsync(w.map_b, 0xFF, sizeof(int) * (size_t)n_utts * S, s));
     }
-  }
-}
-
-void Model::LaunchSearch(SearchPlan *sp, DeviceArena &arena_, const BatchGeom &g, const float *ll, int ll_ld, hipStream_t s) const {
-  const int n_utts = sp->n_utts, maxT = sp->maxT, S = sp->S;
-  if (sp->use_dense) {
-    if (sp->use_reg) LaunchDecodeReg(hclg_dev_, reg_dev_, sp->dopts, g, ll, ll_ld, sp->dw, -1, maxT + 1, s);
-    else LaunchDecodeDense(hclg_dev_, rev_dev_, sp->dopts, g, ll, ll_ld, am_.nnet.output_dim, sp->dw, s);
-    if (sp->reg_lattice) LaunchDenseToTokens(hclg_dev_, g, sp->dw, sp->w, s, /*write_tokens=*/!DenseLatticeUsable(hclg_dev_));
     return;
   }
-  DecodeWork &w = sp->w;
+  // the token-list searches: dense per-state tables, the token lists
   w.best = arena_.AllocT<unsigned long long>((size_t)n_utts * S);
   w.map_a = arena_.AllocT<int>((size_t)n_utts * S);
   w.map_b = arena_.AllocT<int>((size_t)n_utts * S);
@@ -1410,30 +1370,45 @@ void Model::LaunchSearch(SearchPlan *sp, DeviceArena &arena_, const BatchGeom &g
   w.tok_cap = sp->tok_cap;
   w.tokens = arena_.AllocT<int4>((size_t)n_utts * sp->tok_cap);
   w.frame_tok_off = arena_.AllocT<int>((size_t)n_utts * (maxT + 2));
-  if (sp->use_hash) {
+  if (c.search == SearchCall::kLive) {
     // live states of a frame in a two-level table (LDS, then global memory: decode_live.hip); the dense tables above are only touched
     // for utterances that outgrow it (w.redo)
-    const size_t cap = (size_t)DecodeLiveSlotCap(), tab = (size_t)DecodeLiveTableSize();
-    w.h_tab = (int)tab;
-    w.h_keys = arena_.AllocT<unsigned long long>((size_t)n_utts * tab);
-    w.h_slot_tok = arena_.AllocT<int>((size_t)n_utts * tab);
+    w.h_tab = c.live_tab;
+    w.h_keys = arena_.AllocT<unsigned long long>((size_t)n_utts * c.live_tab);
+    w.h_slot_tok = arena_.AllocT<int>((size_t)n_utts * c.live_tab);
     w.h_cand_cap = kHashCandCap;
-    { const char *e = std::getenv("RS_HASH_SLOT_LIMIT"); w.h_slot_limit = e ? std::atoi(e) : DecodeLiveSlotCap(); }      // (tests)
+    w.h_slot_limit = c.live_slot_limit;
     w.h_cand = arena_.AllocT<int>((size_t)n_utts * 2 * kHashCandCap);
-    w.h_gtags = arena_.AllocT<unsigned>((size_t)n_utts * DecodeLiveGlobalTable());
+    w.h_gtags = arena_.AllocT<unsigned>((size_t)n_utts * kLiveGlobalSize);
     w.h_qcap = kLiveQueueCap;
     w.h_q4 = arena_.AllocT<int4>((size_t)n_utts * 2 * kLiveQueueCap);
     w.h_qne = arena_.AllocT<int>((size_t)n_utts * 2 * kLiveQueueCap);
-    { const char *e = std::getenv("RS_HASH_LDS_LOG"); w.h_lds_log = e ? std::atoi(e) : 0; }                                 // (tests)
-    w.h_comp = arena_.AllocT<int4>((size_t)n_utts * cap);
+    w.h_lds_log = c.live_lds_log;
+    w.h_comp = arena_.AllocT<int4>((size_t)n_utts * kLiveSlotCap);
     w.redo = arena_.AllocT<int>(n_utts);
-    LaunchDecodeLive(hclg_dev_, sp->dopts, g, ll, ll_ld, w, s);
-    if (sp->want_lattice) {      // LatticeKernel expects both state -> token maps empty (DecodeKernel leaves them so for the utterances it decodes)
-      RS_HIP(hipMemsetAsync(w.map_a, 0xFF, sizeof(int) * (size_t)n_utts * S, s));
-      RS_HIP(hipMemsetAsync(w.map_b, 0xFF, sizeof(int) * (size_t)n_utts * S, s));
-    }
   }
-  LaunchDecode(hclg_dev_, sp->dopts, g, ll, ll_ld, w, s);
+}
+
+void Model::LaunchSearch(SearchPlan *sp, const BatchGeom &g, const float *ll, int ll_ld, hipStream_t s) const {
+  const SearchCall &c = sp->call;
+  const int n_utts = sp->n_utts, maxT = sp->maxT, S = sp->S;
+  DecodeWork &w = sp->w;
+  switch (c.search) {
+    case SearchCall::kReg:
+    case SearchCall::kRegExact: LaunchDecodeReg(hclg_dev_, reg_dev_, sp->dopts, g, ll, ll_ld, sp->dw, c.reg, -1, maxT + 1, s); break;
+    case SearchCall::kDense: LaunchDecodeDense(hclg_dev_, rev_dev_, sp->dopts, g, ll, ll_ld, am_.nnet.output_dim, sp->dw, c.dense, s); break;
+    case SearchCall::kLive:
+      LaunchDecodeLive(hclg_dev_, sp->dopts, g, ll, ll_ld, w, s);
+      if (sp->want_lattice) {      // LatticeKernel expects both state -> token maps empty (DecodeKernel leaves them so for the utterances it decodes)
+        RS_HIP(hipMemsetAsync(w.map_a, 0xFF, sizeof(int) * (size_t)n_utts * S, s));
+        RS_HIP(hipMemsetAsync(w.map_b, 0xFF, sizeof(int) * (size_t)n_utts * S, s));
+      }
+      LaunchDecode(hclg_dev_, sp->dopts, g, ll, ll_ld, w, s);
+      break;
+    case SearchCall::kTokens: LaunchDecode(hclg_dev_, sp->dopts, g, ll, ll_ld, w, s); break;
+  }
+  // the lattice pass reads token lists, or at least the frames' token offsets, made from the rows
+  if (c.rows_lattice()) LaunchDenseToTokens(hclg_dev_, g, sp->dw, w, s, /*write_tokens=*/c.lattice == SearchCall::kRowsToTokens);
 }
 
 // Result records to the host, and -- when the call asked for more than the traceback gives -- the reference's
@@ -1516,7 +1491,7 @@ void Model::CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const Batc
       }
       RS_HIP(hipMemsetAsync(d_count, 0, sizeof(int) * n_utts, s));
       lw.arcs = static_cast<LatArc *>(ab.d); lw.utt_cap = (int)std::min<size_t>(ab.cap / n_utts, 0x7fffffff); lw.arcs_count = d_count;
-      if (sp.reg_lattice && DenseLatticeUsable(hclg_dev_)) LaunchDenseLattice(hclg_dev_, dopts, g, ll, ll_ld, sp.dw, w, lw, hclg_has_eps_ ? reg_dev_.eps_depth : 0, s);
+      if (sp.call.lattice == SearchCall::kDenseRows) LaunchDenseLattice(hclg_dev_, dopts, g, ll, ll_ld, sp.dw, w, lw, sp.call.dl, s);
       else LaunchLatticePrune(hclg_dev_, dopts, g, ll, ll_ld, w, lw, s);
       // (counts and arcs travel by kernels that store into the pinned block, not by the copy engine: with other calls in flight their
       // 25 MB sample uploads are queued on that engine and these copies waited behind them -- 0.15 ms alone, 5.4 ms with four calls
@@ -1900,7 +1875,7 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   BatchFrames(sample_offsets, &b);
   for (int u = 0; u < n_utts; u++) out_utts[u].num_frames = b.T_dec[u];
   SearchPlan sp;
-  PlanSearch(n_utts, b.maxT_dec, nbest, lat_scale, &sp);
+  PlanSearch(SearchRequestFor(n_utts, b.maxT_dec, nbest, lat_scale), &sp);
   b.arena->Reset(s);
   // The last layer and the search can be pipelined over time slabs when the search is the register-resident kernel: the
   // output GEMM of slab k+1 (MFMA-bound) runs while slab k is searched (latency-bound) on a second, high-priority stream.
@@ -1909,7 +1884,7 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   const int overlap_env = [] { const char *e = std::getenv("RS_OVERLAP_SLABS"); return e ? std::atoi(e) : 1; }();
   const bool last_is_gemm = !nn.ops.empty() && nn.ops.back().kind == LayerOp::kGemm && nn.ops.back().out_buf == nn.output_buf &&
                             nn.bufs[nn.output_buf].lext == 0 && nn.bufs[nn.output_buf].rext == 0;
-  const bool pipelined = sp.use_reg && !sp.reg_lattice && last_is_gemm && !d_log_priors_ && opts_.acoustic_scale == 1.0f && overlap_env > 1 && b.maxT >= 64 &&
+  const bool pipelined = (sp.call.search == SearchCall::kReg || sp.call.search == SearchCall::kRegExact) && !sp.want_lattice && last_is_gemm && !d_log_priors_ && opts_.acoustic_scale == 1.0f && overlap_env > 1 && b.maxT >= 64 &&
                          s == cx.stream && fsf == 1;
   const int n_slabs = b.n_slabs = pipelined ? std::min(overlap_env, 8) : 1, slab_len = b.slab_len = std::max(1, (b.maxT + n_slabs - 1) / n_slabs);
   BatchSetupUpload(sample_offsets, &b);
@@ -1955,8 +1930,9 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
       LaunchGemm(gd, b.lists.slab_off[k + 1] - b.lists.slab_off[k], b.d_row_ivec, s);
       RS_HIP(hipEventRecord(cx.slab_ev[k], s));
       RS_HIP(hipStreamWaitEvent(cx.stream_dec, cx.slab_ev[k], 0));
-      LaunchDecodeReg(hclg_dev_, reg_dev_, sp.dopts, b.g, b.bufp[nn.output_buf], b.buf_ld[nn.output_buf], sp.dw, k == 0 ? -1 : k * slab_len,
-                      k + 1 == n_slabs ? b.maxT + 1 : (k + 1) * slab_len, cx.stream_dec);
+      const int f_end = k + 1 == n_slabs ? b.maxT + 1 : (k + 1) * slab_len;
+      const RegLaunch slab = PlanRegLaunch(search_graph_, search_load_, n_utts, /*window=*/false, true, f_end, b.maxT, sp.dopts.exact_order != 0, DeviceNumCu(), ReadSearchSwitches());
+      LaunchDecodeReg(hclg_dev_, reg_dev_, sp.dopts, b.g, b.bufp[nn.output_buf], b.buf_ld[nn.output_buf], sp.dw, slab, k == 0 ? -1 : k * slab_len, f_end, cx.stream_dec);
     }
     RS_HIP(hipEventRecord(cx.slab_ev[8], cx.stream_dec));
   } else {
@@ -1971,7 +1947,7 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   tm.Mark();
   // ---- decode
   if (pipelined) RS_HIP(hipStreamWaitEvent(s, cx.slab_ev[8], 0));       // the search of the last slab
-  else { LdsPoison(s); LaunchSearch(&sp, *b.arena, gdec, ll, ll_ld, s); }
+  else { LdsPoison(s); LaunchSearch(&sp, gdec, ll, ll_ld, s); }
   tm.Mark();
   CollectResults(sp, cx, gi, gdec, b.T_dec.data(), ll, ll_ld, nbest, lat_scale, s, out_utts, timings);
   tm.Mark();

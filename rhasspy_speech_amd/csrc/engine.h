@@ -115,10 +115,11 @@ struct RowMaps {
   }
 };
 
-// Which search kernel a call runs and its work buffers (engine.cc: PlanSearch / AllocSearch / LaunchSearch / CollectResults).
+// What a call's search runs (search_plan.h: PlanSearchCall) and its work buffers (engine.cc: PlanSearch / AllocSearch / LaunchSearch /
+// CollectResults).
 struct SearchPlan {
-  bool unscale = false, want_lattice = false, use_reg = false, use_dense = false, use_hash = false;
-  bool reg_lattice = false;      // n-best / lattice call on a grammar graph: register-resident search + its rows turned into token lists
+  SearchCall call{};
+  bool unscale = false, want_lattice = false;      // (call.unscale, call.want_lattice)
   int S = 0, tok_cap = 0, max_words = 1024, maxT = 0, n_utts = 0;
   DecodeOptsDev dopts{};
   DecodeWork w{};
@@ -149,7 +150,7 @@ class Model {
                                           float lat_scale, bool streaming = false);
   const rs_decode_opts &opts() const { return opts_; }
   // rs_decode_opts.exact_token_order, RS_EXACT_ORDER overriding (read per call: tests compare the two searches on one model)
-  bool ExactOrder() const { const char *e = std::getenv("RS_EXACT_ORDER"); return e ? std::atoi(e) != 0 : opts_.exact_token_order != 0; }
+  bool ExactOrder() const { return ExactOrderAsked(ReadSearchSwitches(), opts_.exact_token_order); }
   const FeatureConfig &features() const { return fc_; }
   const AcousticModel &am() const { return am_; }
   const Hclg &hclg() const { return hclg_; }
@@ -200,9 +201,11 @@ class Model {
   // operand images for the buffers the split-bf16 GEMM reads as images, from a call's arena
   std::vector<ActImage> AllocImages(DeviceArena &arena, int rows) const;
   std::vector<char> buf_image_, buf_f32_;      // per nnet buffer: has an operand image / is (also) read as plain floats
-  void PlanSearch(int n_utts, int maxT, int nbest, float lat_scale, SearchPlan *sp, bool best_path_only = false, bool token_lists = false) const;
-  void AllocSearch(SearchPlan *sp, DeviceArena &arena, hipStream_t s, bool pooled_frames = false) const;
-  void LaunchSearch(SearchPlan *sp, DeviceArena &arena, const BatchGeom &g, const float *ll, int ll_ld, hipStream_t s) const;
+  // the request of a call with this model's options; PlanSearch: the choice for it (search_plan.h), failing where the plan refuses
+  SearchRequest SearchRequestFor(int n_utts, int maxT, int nbest, float lat_scale) const;
+  void PlanSearch(const SearchRequest &rq, SearchPlan *sp) const;
+  void AllocSearch(SearchPlan *sp, DeviceArena &arena, hipStream_t s) const;
+  void LaunchSearch(SearchPlan *sp, const BatchGeom &g, const float *ll, int ll_ld, hipStream_t s) const;
   void CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const BatchGeom &g, const int *T, const float *ll, int ll_ld, int nbest,
                       float lat_scale, hipStream_t s, UttResult *out_utts, float *timings);
   void RunNnet(const std::vector<float *> &bufp, const std::vector<int> &buf_ld, float *d_ivec, int ld_i, const int *d_row_ivec, int rows,
@@ -272,7 +275,7 @@ class Model {
   void AdvanceUpload(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, bool final, AdvanceSet *set);
   void AdvanceStageA(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set);
   void AdvanceIvectors(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set);
-  void AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set, bool final, bool reg_windows, SearchPlan *sp);
+  void AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set, bool final, SearchPlan *sp);
   void IssueStagesBC(const StagesBC &j);      // on the caller's thread (a finishing call) or the pool's issuing thread
   void AdvanceBookkeeping(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, int par, bool searched);
   void AdvanceFinish(StreamPool *p, rs_stream *const *streams, const AdvancePlan &plan, const AdvanceSet &set, SearchPlan &sp, bool flush, int nbest,
@@ -323,12 +326,12 @@ class Model {
   std::vector<GemmPlan> gemm_plans_;  // indexed like am_.nnet.ops (unused entries for eltwise ops)
   float *d_log_priors_ = nullptr;
   HclgDev hclg_dev_{};
-  bool hclg_has_eps_ = false;      // the graph has input-epsilon arcs (DenseLatticeKernel skips its closure pass otherwise)
   RevGraphDev rev_dev_{};
   RegGraphDev reg_dev_{};
-  int decoder_choice_ = 0;      // RS_DECODER=reg|dense|sparse forces a kernel variant (tests); 0 = automatic
-  bool dense_ok_ = false;
-  bool force_sparse_ = false;   // RS_FORCE_SPARSE_DECODER=1: always use the general (token-list) kernel
+  // search_plan.h: the graph's sizes, the switches as the constructor found them, what they allow on this graph
+  SearchGraph search_graph_{};
+  SearchSwitches search_sw_{};
+  SearchLoad search_load_{};
   int L_ = 0, R_ = 0;
 };
 

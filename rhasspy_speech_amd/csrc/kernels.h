@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "gemm_launch.h"
+#include "search_plan.h"
 
 namespace rs {
 
@@ -152,6 +153,7 @@ size_t ActImagePartBytes(int rows, int guard, int dim);      // bytes of one par
 // Plans the launch (PlanGemmLaunch, gemm_launch.h), runs the kernel it names and, where the plan asks for it, the residual pass.
 // sw: the switches to plan with (null: read from the environment now)
 void LaunchGemm(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw = nullptr);
+int DeviceNumCu();      // compute units of the current device, asked once per process (what the launch planners are given)
 
 struct SumTermDev { const float *src; int ld, col0, row_off; float scale; };
 struct EltwiseDev {
@@ -233,14 +235,8 @@ struct HclgDev {
   const uint4 *nodes;
   const float *final_cost;     // S
 };
-struct DecodeOptsDev {
-  float beam, lattice_beam, beam_delta;
-  int max_active, min_active;
-  int exact_order;            // rs_decode_opts.exact_token_order: the reference's order-dependent token creation (decode_reg.hip), where the graph allows it
-  int no_commit_hist = 0;     // RS_REG_NO_HIST=1 (tests): RegDecodeKernel's GetCutoff always selects the slow way (KthFromHist)
-  int no_final = 0;           // partial results of streams (rs_streams_partial): the final stage ignores final costs -- the
-                              // "not reached" branch every search kernel already has (GetBestPath(use_final_probs = false))
-};
+// (DecodeOptsDev, the kernels' size limits and their LDS carve-ups: search_dev.h; which search runs, in which shape: search_plan.h --
+// both host-only)
 struct DecodeWork {
   // per utterance
   unsigned long long *best;   // n_utts x S : packed (ordered cost bits << 32 | arc), ~0 = empty
@@ -253,13 +249,13 @@ struct DecodeWork {
   int *in_queue;              // n_utts x S : round stamp of the state's last push onto a closure queue (token-list search)
   // live-state-table search (LiveDecodeKernel, decode_live.hip): a slot is the position of a state's entry in the utterance's table
   // (LDS part, then the global part); null = not in use
-  int h_tab;                  // DecodeLiveTableSize(): length of the slot-indexed arrays
+  int h_tab;                  // kLiveTableSize: length of the slot-indexed arrays
   unsigned long long *h_keys; // n_utts x h_tab : packed (cost, arc) of the states in the global part of the table (its first entries)
   int *h_slot_tok;            // n_utts x h_tab : slot -> token index in the frame under construction, for the states the closure can reach
-  unsigned *h_gtags;          // n_utts x DecodeLiveGlobalTable() : state ids of the global part of the table
+  unsigned *h_gtags;          // n_utts x kLiveGlobalSize : state ids of the global part of the table
   int *h_cand;                // n_utts x 2 x h_cand_cap : candidate records of a frame {arc | flags, slot << 16 | source token}
   int h_cand_cap;
-  int h_slot_limit;           // live states a frame may hold before the utterance is handed to DecodeKernel (<= DecodeLiveSlotCap())
+  int h_slot_limit;           // live states a frame may hold before the utterance is handed to DecodeKernel (<= kLiveSlotCap)
   int4 *h_q4;                 // n_utts x 2 x h_qcap : closure work lists {slot | writer token << 16, first epsilon arc, key low, key high}
   int *h_qne;                 // n_utts x 2 x h_qcap : ... and the number of epsilon arcs of the entry's state
   int h_qcap;
@@ -277,14 +273,8 @@ void LaunchDecode(const HclgDev &h, const DecodeOptsDev &o, const BatchGeom &g, 
                   const DecodeWork &w, hipStream_t s);
 // The same search with the live states of a frame in a table that follows the beam, not the graph (decode_live.hip): tags and
 // recombination keys in LDS, a second level in global memory behind them.  Utterances that outgrow it (more than
-// DecodeLiveSlotCap() live states in a frame, more records than the lists hold) are flagged in w.redo and decoded by LaunchDecode,
+// kLiveSlotCap live states in a frame, more records than the lists hold) are flagged in w.redo and decoded by LaunchDecode,
 // which the caller issues behind it on the same stream.
-constexpr int kHashCandCap = 65536;      // candidate records per utterance and frame (the ARPA workload's largest frame: 24 k)
-constexpr int kLiveQueueCap = 65536;     // closure work-list entries per round
-bool DecodeLiveUsable(const HclgDev &h);
-int DecodeLiveSlotCap();
-int DecodeLiveTableSize();
-int DecodeLiveGlobalTable();
 void LaunchDecodeLive(const HclgDev &h, const DecodeOptsDev &o, const BatchGeom &g, const float *loglikes, int ld,
                       const DecodeWork &w, hipStream_t s);
 
@@ -325,39 +315,32 @@ struct DenseWork {
 // Register-resident variant (decode_reg.hip): the arcs are dealt out to the threads of an NT-thread workgroup (arc i ->
 // thread i % NT, register slot i / NT) and live in VGPRs for the whole utterance.  Tables are [slot][thread] so that
 // loading them is coalesced; LDS addresses are baked in on the host (cost_cur at byte 0, keys at key_base).
-constexpr int kRegMaxStates = 5000;      // 16-bit LDS byte addresses: key_base + 8 * (S + 1) < 65536
 struct RegGraphDev {
   int nt = 0;                 // 0 = graph does not fit this variant
   int ke = 0, kx = 0;         // register slots per thread for emitting / epsilon arcs (a kernel instantiation)
   int eps_depth = 0;          // longest epsilon path (rounds to the fixpoint); 0 = no epsilon arcs; -1 = cyclic or deep -> vote
-  int key_base = 0;           // byte offset of key_next[] in the dynamic LDS region
+  int key_base = 0;           // byte offset of key_next[] in the dynamic LDS region (lds::RegKeyBase)
   const int4 *e_tab;          // [ke][nt] {4*src | (key_base + 8*dst) << 16, pdf, weight bits, forward arc index}
   const int4 *x_tab;          // [kx][nt] {(key_base + 8*src + 4) | (key_base + 8*dst) << 16, 0, weight bits, forward arc index}
   // RegDecodeExactKernel: per emitting arc (table position of its source state's first emitting arc) << 8 | its number among
-  // them; per epsilon arc its number among its source's epsilon arcs.  exact_ok: <= 1000 states, epsilon depth <= 1, <= 32 arcs of
-  // either kind per state.
+  // them; per epsilon arc its number among its source's epsilon arcs (where SearchLoad::exact_ok).
   const int *e_aux, *x_aux;
-  int exact_ok = 0;
 };
-bool RegDecodeConfig(int num_states, int num_emitting, int num_eps, int *nt, int *ke, int *kx);
 // Decodes frames [f_begin, f_end) of every utterance (f_begin = -1 starts an utterance; the slab that contains an
 // utterance's last frame also does its traceback).  w.counters must be zeroed before the first slab.
-// With w.win_begin set (streams) f_begin / f_end are ignored; `any_final` then says whether some utterance ends in this launch
-// (LDS for the traceback staging is only requested then).
-bool LaunchDecodeReg(const HclgDev &h, const RegGraphDev &r, const DecodeOptsDev &o, const BatchGeom &g,
-                     const float *loglikes, int ld, const DenseWork &w, int f_begin, int f_end, hipStream_t s, bool any_final = true);
+// With w.win_begin set (streams) f_begin / f_end are ignored.  p: the shape planned for this launch (PlanRegLaunch); fails on a
+// shape without an instantiation.
+void LaunchDecodeReg(const HclgDev &h, const RegGraphDev &r, const DecodeOptsDev &o, const BatchGeom &g,
+                     const float *loglikes, int ld, const DenseWork &w, const RegLaunch &p, int f_begin, int f_end, hipStream_t s);
 // Token lists (DecodeWork: tokens {state, cost bits, -, back-pointer arc}, frame_tok_off) out of the dense cost / back-pointer rows a
 // register-resident search with DenseWork::cost_rows left behind: what LatticeKernel reads.  Frame 0's first token is the start state's.
 void LaunchDenseToTokens(const HclgDev &h, const BatchGeom &g, const DenseWork &dw, const DecodeWork &w, hipStream_t s, bool write_tokens = true);
-// the lattice's links straight from the dense rows (graphs of at most 2048 states / 8192 arcs; RS_LATTICE_KERNEL=tokens: never)
+// the lattice's links straight from the dense rows (SearchCall::kDenseRows: graphs of at most 2048 states / 8192 arcs)
 struct LatticeWork;
-bool DenseLatticeUsable(const HclgDev &h);
 void LaunchDenseLattice(const HclgDev &h, const DecodeOptsDev &o, const BatchGeom &g, const float *loglikes, int ld, const DenseWork &dw,
-                        const DecodeWork &w, const LatticeWork &lw, int eps_rounds, hipStream_t s);   // eps_rounds: RegGraphDev::eps_depth
-size_t DenseDecodeSmemBytes(int num_states, int num_pdfs);
-bool DenseDecodeFits(int num_states, int num_pdfs);
+                        const DecodeWork &w, const LatticeWork &lw, const DenseLatticeLaunch &p, hipStream_t s);
 void LaunchDecodeDense(const HclgDev &h, const RevGraphDev &r, const DecodeOptsDev &o, const BatchGeom &g,
-                       const float *loglikes, int ld, int num_pdfs, const DenseWork &w, hipStream_t s);
+                       const float *loglikes, int ld, int num_pdfs, const DenseWork &w, const DenseLaunch &p, hipStream_t s);
 
 // Lattice extraction = FinalizeDecoding (lattice-faster-decoder.cc:625-640): backward pass over the stored
 // token lists that recomputes every forward link, derives the exact extra_cost of every token

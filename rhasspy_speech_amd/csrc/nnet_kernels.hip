@@ -393,7 +393,7 @@ void GemmNoInstantiation(const GemmLaunch &p) {
 }
 
 // compute units of the device, asked once per process (256 where the query fails)
-static int GemmNumCu() {
+int DeviceNumCu() {
   static int num_cu = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
@@ -413,7 +413,7 @@ static void DispatchGemm(const GemmLaunch &p, const GemmDev &d, int rows, const 
 
 void LaunchGemm(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw) {
   if (rows <= 0) return;
-  const GemmLaunch p = PlanGemmLaunch(d, rows, GemmNumCu(), sw ? *sw : ReadGemmSwitches());
+  const GemmLaunch p = PlanGemmLaunch(d, rows, DeviceNumCu(), sw ? *sw : ReadGemmSwitches());
   if (!p.residual_pass) return DispatchGemm(p, d, rows, row_ivec, s);
   DispatchGemm(p, GemmWithoutResidual(d), rows, row_ivec, s);      // (the kernel's epilogue does not add a folded residual)
   LaunchResidualAdd(d, rows, s);

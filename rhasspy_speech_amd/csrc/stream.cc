@@ -236,7 +236,7 @@ StreamPool *Model::Pool() {
   p->ld_c = RoundUp(C, 4);
   p->ld_ll = RoundUp(P, 4);
   p->S = hclg_.num_states();
-  p->reg = reg_dev_.nt != 0 && !force_sparse_ && (decoder_choice_ == 0 || decoder_choice_ == 1);
+  p->reg = StreamSearchIncremental(search_load_);
   RS_HIP(hipStreamCreateWithFlags(&p->q, hipStreamNonBlocking));
   RS_HIP(hipStreamCreateWithFlags(&p->qa, hipStreamNonBlocking));
   RS_HIP(hipStreamCreateWithFlags(&p->qc, hipStreamNonBlocking));
@@ -612,6 +612,7 @@ struct StagesBC {
   BatchGeom gd;
   DenseWork dw;
   DecodeOptsDev dopts;
+  RegLaunch reg;                 // the window launch (reg_windows)
   SearchPlan *sp = nullptr;      // (a finishing call only)
 };
 
@@ -812,14 +813,14 @@ static BatchGeom SearchGeom(const AdvancePlan &plan, const int *d_is) {
 }
 
 // 4. the acoustic model over the new chunks (+ context), 5. the search: buffers out of the arena here, the launches as a StagesBC
-void Model::AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set, bool final, bool reg_windows, SearchPlan *sp) {
+void Model::AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const AdvanceSet &set, bool final, SearchPlan *sp) {
   const Nnet &nn = am_.nnet;
   const AdvancePlan::Offsets &o = plan.o;
   DeviceArena &arena = *set.arena;
   auto D = [&](size_t off) { return set.d_is + off; };
   StagesBC job;
   job.p = p; job.arena = &arena; job.par = set.par;
-  job.final = final; job.timed = set.timed; job.reg_windows = reg_windows; job.exact = exact_gemm_.load();
+  job.final = final; job.timed = set.timed; job.reg_windows = sp->call.windows; job.exact = exact_gemm_.load();
   job.ovf_dev = static_cast<DecodeContext *>(p->cx)->gemm_ovf_dev;
   job.nI = plan.nI; job.nN = plan.nN; job.rowsN = plan.rowsN; job.framesN = plan.framesN; job.maxTn = std::max(plan.maxTn, 1); job.n = plan.n;
   job.n_sub = (int)plan.n_lldst.size(); job.have_sub = !plan.n_llsrc.empty();
@@ -837,10 +838,8 @@ void Model::AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const Advanc
   std::memset(&dw, 0, sizeof(dw));
   dw.bp = p->bp; dw.frame_info = p->finfo; dw.state_cost = p->dec_state; dw.counters = p->dec_ctr;
   dw.win_begin = D(o.wb); dw.win_end = D(o.we); dw.win_final = D(o.wf); dw.pool_row = D(o.row0); dw.slot = D(o.slots);
-  DecodeOptsDev &dopts = job.dopts;
-  dopts.beam = opts_.beam; dopts.lattice_beam = opts_.lattice_beam; dopts.beam_delta = opts_.beam_delta;
-  dopts.max_active = opts_.max_active; dopts.min_active = opts_.min_active;
-  dopts.exact_order = ExactOrder() ? 1 : 0;
+  job.dopts = sp->dopts;
+  job.reg = sp->call.reg;
   job.sp = sp;
   if (final || !p->use_issuer) IssueStagesBC(job);
   else p->issuer.Submit([this, job = std::move(job)] { IssueStagesBC(job); });
@@ -872,15 +871,15 @@ void Model::IssueStagesBC(const StagesBC &j) {
   RS_HIP(hipEventRecord(p->ev_b[par], q));
   RS_HIP(hipStreamWaitEvent(qc, p->ev_b[par], 0));
   MarkIf(j.timed, tc);
-  if (j.final) AllocSearch(j.sp, *j.arena, qc, /*pooled_frames=*/j.reg_windows);
+  if (j.final) AllocSearch(j.sp, *j.arena, qc);
   if (j.reg_windows && (j.final || j.nN > 0)) {      // (an advance without new log-likelihood rows has nothing to search)
     DenseWork dw2 = j.dw;
     if (j.final) { dw2 = j.sp->dw; dw2.bp = j.dw.bp; dw2.frame_info = j.dw.frame_info; dw2.state_cost = j.dw.state_cost; dw2.counters = j.dw.counters;
                    dw2.win_begin = j.dw.win_begin; dw2.win_end = j.dw.win_end; dw2.win_final = j.dw.win_final; dw2.pool_row = j.dw.pool_row; dw2.slot = j.dw.slot; }
-    LaunchDecodeReg(hclg_dev_, reg_dev_, j.dopts, j.gd, p->ll, p->ld_ll, dw2, 0, 0, qc, j.final);
+    LaunchDecodeReg(hclg_dev_, reg_dev_, j.dopts, j.gd, p->ll, p->ld_ll, dw2, j.reg, 0, 0, qc);
     if (j.final) LaunchCopyRows(p->dec_ctr, 16, j.d_slots, j.sp->w.counters, 16, nullptr, j.n, 16, qc);
   } else if (j.final) {
-    LaunchSearch(j.sp, *j.arena, j.gd, p->ll, p->ld_ll, qc);
+    LaunchSearch(j.sp, j.gd, p->ll, p->ld_ll, qc);
   }
   MarkIf(j.timed, tc);
   RS_HIP(hipEventRecord(p->ev_done[par], qc));
@@ -990,15 +989,18 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
   const auto wall0 = clock.last;
   AdvancePlan &plan = p->plans[set.par];
   AdvancePlanStreams(p, streams, n, flush, final, &plan);
+  // the search of this call: the streams' new windows (a finishing call that wants a lattice: the retained rows, like a batch)
   SearchPlan sp;
-  if (final) PlanSearch(n, plan.maxT, nbest, lat_scale, &sp);
-  const bool reg_windows = p->reg && !(final && sp.want_lattice);
+  SearchRequest rq = SearchRequestFor(n, plan.maxT, nbest, lat_scale);
+  rq.stream_window = true; rq.any_final = final;
+  PlanSearch(rq, &sp);
+  const bool reg_windows = sp.call.windows;
   clock.Mark(&p->host_ms[0]);
   AdvanceUpload(p, streams, plan, final, &set);
   clock.Mark(&p->host_ms[1]);
   AdvanceStageA(p, plan, set);
   clock.Mark(&p->host_ms[2]);
-  AdvanceStagesBC(p, plan, set, final, reg_windows, &sp);
+  AdvanceStagesBC(p, plan, set, final, &sp);
   clock.Mark(&p->host_ms[3]);
   clock.Mark(&p->host_ms[4]);
   AdvanceBookkeeping(p, streams, plan, set.par, /*searched=*/reg_windows && (final || plan.nN > 0));
@@ -1061,7 +1063,9 @@ void Model::StreamsPartialLocked(rs_stream *const *streams, int n, Result *res) 
   if (p->reg) {
     sp.n_utts = n; sp.S = S; sp.maxT = maxT; sp.max_words = StreamPool::kPartialWords;
   } else {
-    PlanSearch(n, maxT, 1, 1.0f, &sp, /*best_path_only=*/true);
+    SearchRequest rq = SearchRequestFor(n, maxT, 1, 1.0f);
+    rq.best_path_only = true;      // (never a lattice, whatever the model's options ask of a finish)
+    PlanSearch(rq, &sp);
     sp.dopts.no_final = 1;
   }
   arena.Reset(qc);
@@ -1094,7 +1098,7 @@ void Model::StreamsPartialLocked(rs_stream *const *streams, int n, Result *res) 
     LaunchPartialReg(hclg_dev_, pw, n, qc);
   } else {
     AllocSearch(&sp, arena, qc);
-    LaunchSearch(&sp, arena, gd, p->ll, p->ld_ll, qc);
+    LaunchSearch(&sp, gd, p->ll, p->ld_ll, qc);
   }
   { const hipError_t le = hipGetLastError(); if (le != hipSuccess) Fail(std::string("a kernel launch failed: ") + hipGetErrorString(le)); }
   res->utts.assign(n, UttResult());
@@ -1187,7 +1191,11 @@ void Model::StreamsEndpointLocked(rs_stream *const *streams, int n, const std::v
   HostArena &harena = cx.host_arena[par];
   hipStream_t qc = p->qc;
   SearchPlan sp;
-  if (!p->reg) PlanSearch(n, maxT, 1, 1.0f, &sp, /*best_path_only=*/true, /*token_lists=*/true);
+  if (!p->reg) {
+    SearchRequest rq = SearchRequestFor(n, maxT, 1, 1.0f);
+    rq.best_path_only = rq.token_lists = true;
+    PlanSearch(rq, &sp);
+  }
   arena.Reset(qc);
   harena.Reset(qc);
   EndpointWork ew;
@@ -1211,7 +1219,7 @@ void Model::StreamsEndpointLocked(rs_stream *const *streams, int n, const std::v
     // EndpointTokensKernel needs the best token without final costs and the first non-silence arc, so it reduces the last token list
     // and walks the back pointers itself.  The extra traceback is one walk of the path, small beside the search over all frames.)
     AllocSearch(&sp, arena, qc);
-    LaunchSearch(&sp, arena, gd, p->ll, p->ld_ll, qc);
+    LaunchSearch(&sp, gd, p->ll, p->ld_ll, qc);
     ew.tokens = sp.w.tokens; ew.frame_tok_off = sp.w.frame_tok_off; ew.counters = sp.w.counters;
     ew.tok_cap = sp.w.tok_cap; ew.max_frames = maxT;
     LaunchEndpointTokens(hclg_dev_, ew, n, qc);
