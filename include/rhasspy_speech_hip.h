@@ -108,7 +108,15 @@ void rs_model_free(rs_model *model);
  * returns the number of bytes needed (like snprintf).  Two lines are state, not structure: `layer_gemm:` and
  *   arenas: device blocks=B bytes=N allocations=A; host blocks=B bytes=N allocations=A
  * summed over the model's decode contexts: the blocks and bytes their per-call arenas hold now, and the hipMalloc / hipHostMalloc
- * calls they have made since the model was loaded.  `allocations` stands still once every context has seen its largest call twice. */
+ * calls they have made since the model was loaded.  `allocations` stands still once every context has seen its largest call twice.
+ * Once the model is on the device there is also
+ *   search: states=S arcs_e=E arcs_x=X eps_depth=D max_out=Me,Mx reg=<nt,ke,kx> eps_rounds=R exact_ok=0|1 dense_ok=0|1
+ *           dense_lattice=<nt,ka> crowded_at=N
+ * (one line): what the search planner found on the graph -- states, emitting / epsilon arcs, the longest epsilon path (-1: cyclic; 0 also
+ * beyond 5000 states, where nothing asks), the largest emitting / epsilon out-degree -- and decided at load: the register-resident
+ * search's shape (reg=none: the graph fits none), its closure rounds (-1: until nothing changes), whether exact_token_order applies,
+ * whether the LDS-resident dense search does, the lattice kernel of an n-best call (none: the graph is beyond its 2048 states / 8192
+ * arcs), and the smallest batch that gets the crowded shape (half the waves, twice the arcs per thread: 4 n_utts >= 3 CUs). */
 int rs_model_describe(const rs_model *model, char *buf, size_t len);
 /* The check the reference makes when a waveform arrives (OnlineGenericBaseFeature::MaybeCreateResampler, feat/online-feature.cc:
  * 86-101; online2-wav-nnet3-latgen-faster.cc:233 hands it WaveData::SampFreq()): RS_OK when `sample_rate` is the model's

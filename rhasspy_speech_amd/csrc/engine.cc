@@ -875,6 +875,11 @@ std::string Model::Describe() const {
   os << "transition_model: tids=" << am_.trans.id2pdf.size() - 1 << " pdfs=" << am_.trans.num_pdfs << "\n";
   if (pruned_from_) os << "output layer: pruned to the " << am_.nnet.output_dim << " of " << pruned_from_ << " pdfs that occur on HCLG arcs\n";
   os << "hclg: states=" << hclg_.num_states() << " arcs=" << hclg_.arcs.size() << " start=" << hclg_.start << "\n";
+  // (written once the graph is on the device: what the search planner found on it and decided at load, search_plan.h)
+  if (on_device_) {
+    char line[400];
+    os << "search: " << DescribeSearchLoad(search_graph_, search_load_, DeviceNumCu(), ReadSearchSwitches(), line, sizeof(line)) << "\n";
+  }
   os << "halo: L=" << L_ << " R=" << R_ << "\n";
   os << "decoder_opts: beam=" << opts_.beam << " max_active=" << opts_.max_active << " min_active=" << opts_.min_active << " lattice_beam=" << opts_.lattice_beam
      << " beam_delta=" << opts_.beam_delta << " acoustic_scale=" << opts_.acoustic_scale << " frames_per_chunk=" << opts_.frames_per_chunk

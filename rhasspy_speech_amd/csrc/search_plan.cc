@@ -273,4 +273,16 @@ const char *DescribeSearchCall(const SearchCall &c, char *buf, size_t size) {
   return buf;
 }
 
+const char *DescribeSearchLoad(const SearchGraph &g, const SearchLoad &l, int num_cu, const SearchSwitches &sw, char *buf, size_t size) {
+  char reg[48] = "none", dl[48] = "none";
+  if (l.nt != 0) std::snprintf(reg, sizeof(reg), "<%d,%d,%d>", l.nt, l.ke, l.kx);
+  if (DenseLatticeFits(g)) {
+    const DenseLatticeLaunch p = PlanDenseLattice(g, l, sw);
+    std::snprintf(dl, sizeof(dl), "<%d,%d>", p.nt, p.ka);
+  }
+  std::snprintf(buf, size, "states=%d arcs_e=%d arcs_x=%d eps_depth=%d max_out=%d,%d reg=%s eps_rounds=%d exact_ok=%d dense_ok=%d dense_lattice=%s crowded_at=%ld",
+                g.states, g.in_e, g.in_x, g.eps_depth, g.max_out_e, g.max_out_x, reg, l.eps_rounds, (int)l.exact_ok, (int)l.dense_ok, dl, (3 * (long)num_cu + 3) / 4);
+  return buf;
+}
+
 }  // namespace rs

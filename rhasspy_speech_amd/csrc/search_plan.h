@@ -135,5 +135,10 @@ RegLaunch PlanRegLaunch(const SearchGraph &g, const SearchLoad &l, int n_utts, b
 // path_cap=1204 opts=0,0": the search and its kernel's template arguments in their order, grid, threads, LDS bytes; the
 // lattice route (and DenseLatticeKernel's launch); the capacities (error messages, the CPU check's fixture).  Returns buf.
 const char *DescribeSearchCall(const SearchCall &c, char *buf, size_t size);
+// "states=625 arcs_e=1040 arcs_x=208 eps_depth=1 max_out=12,4 reg=<512,4,2> eps_rounds=1 exact_ok=1 dense_ok=1 dense_lattice=<512,4>
+// crowded_at=192": what WalkSearchGraph found and PlanSearchLoad decided (reg=none: no register shape fits), the DenseLatticeKernel
+// instantiation of an n-best call (none: beyond kDLMaxStates / kDLMaxArcs) and the smallest batch the crowded rule applies to on a
+// device of num_cu CUs (the `search:` line of rs_model_describe).  Returns buf.
+const char *DescribeSearchLoad(const SearchGraph &g, const SearchLoad &l, int num_cu, const SearchSwitches &sw, char *buf, size_t size);
 
 }  // namespace rs

@@ -5,6 +5,11 @@
 //     <graph> <request> n<n_utts> T<maxT> cu<CUs> <switches without their RS_ prefix, or -> | <DescribeSearchCall>
 // compared by the test with tests/host/search_plan_expected.txt.  A stream advance that searches nothing prints "no launch", an
 // advance that does prints no capacities (it has none), and a call the plan refuses prints its error alone.
+// A second mode, `--graph FILE CUS n_utts nbest exact [n_utts nbest exact ...]`, plans for a real graph instead (tests/
+// test_search_shapes_cpu.py): FILE holds "states pdfs arcs" and then one "src dst emitting" line per arc in forward order; the program
+// prints what WalkSearchGraph finds ("walk: ..."), DescribeSearchLoad for a device of CUS compute units ("search: ...", the line
+// rs_model_describe reports) and, per triple, DescribeSearchCall of a whole-utterance batch call of 298 frames under the RS_*
+// switches of its environment ("call n<n_utts> nbest<nbest> exact<exact> | ...").  The default run prints what it always printed.
 // For every case the program also asserts that the planned LDS bytes cover the last byte of every region the shared carve-up
 // (search_dev.h) defines, that they stay within a CU's 160 KB, and that tok_cap fits an int unless the plan carries the error.
 //
@@ -254,7 +259,50 @@ static void CheckWalk() {
 }
 #endif
 
-int main() {
+#ifndef SEARCH_PLAN_RECORD
+static int GraphMode(int argc, char **argv) {
+  CHECK(argc >= 7 && (argc - 4) % 3 == 0, "usage: --graph FILE CUS n_utts nbest exact [n_utts nbest exact ...]");
+  FILE *f = std::fopen(argv[2], "r");
+  CHECK(f, "cannot read %s", argv[2]);
+  int S = 0, P = 0;
+  long A = 0;
+  CHECK(std::fscanf(f, "%d %d %ld", &S, &P, &A) == 3 && S > 0 && P >= 0 && A >= 0, "%s: header", argv[2]);
+  std::vector<int> src(A), dst(A);
+  std::vector<unsigned char> em(A);
+  for (long a = 0; a < A; a++) {
+    int e = 0;
+    CHECK(std::fscanf(f, "%d %d %d", &src[a], &dst[a], &e) == 3, "%s: arc %ld", argv[2], a);
+    CHECK(src[a] >= 0 && src[a] < S && dst[a] >= 0 && dst[a] < S && (a == 0 || src[a] >= src[a - 1]), "%s: arc %ld: %d -> %d", argv[2], a, src[a], dst[a]);
+    em[a] = e != 0;
+  }
+  std::fclose(f);
+  SearchGraph g;
+  g.states = S; g.arcs = (int)A; g.pdfs = P; g.live_tables = true;
+  WalkSearchGraph(src.data(), dst.data(), em.data(), (size_t)A, &g);
+  const int num_cu = std::atoi(argv[3]);
+  const SearchLoad l = PlanSearchLoad(g, ReadSearchSwitches());
+  char line[600];
+  std::printf("walk: states=%d in_e=%d in_x=%d eps_dst=%d eps_depth=%d max_out_e=%d max_out_x=%d\n", g.states, g.in_e, g.in_x, g.eps_dst, g.eps_depth, g.max_out_e, g.max_out_x);
+  std::printf("search: %s\n", DescribeSearchLoad(g, l, num_cu, ReadSearchSwitches(), line, sizeof(line)));
+  for (int i = 4; i + 2 < argc; i += 3) {
+    SearchRequest rq;
+    rq.n_utts = std::atoi(argv[i]); rq.maxT = 298; rq.nbest = std::atoi(argv[i + 1]); rq.exact_token_order = std::atoi(argv[i + 2]);
+    rq.beam = 13.0f; rq.lattice_beam = 6.0f; rq.beam_delta = 0.5f; rq.max_active = 7000; rq.min_active = 200;
+    const SearchCall c = PlanSearchCall(g, l, rq, num_cu, ReadSearchSwitches());
+    char what[100];
+    std::snprintf(what, sizeof(what), "call n%d nbest%d exact%d", rq.n_utts, rq.nbest, rq.exact_token_order);
+    CheckLds(g, l, c, what);
+    std::printf("%s | %s\n", what, DescribeSearchCall(c, line, sizeof(line)));
+  }
+  return 0;
+}
+#endif
+
+int main(int argc, char **argv) {
+#ifndef SEARCH_PLAN_RECORD
+  if (argc > 1 && !std::strcmp(argv[1], "--graph")) return GraphMode(argc, argv);
+#endif
+  (void)argc; (void)argv;
   // every graph, every request kind: one utterance of 298 frames on 256 CUs
   for (const GraphSpec &g : kGraphs) {
     bool every_kind = false;
