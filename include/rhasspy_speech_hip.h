@@ -78,7 +78,10 @@ typedef struct rs_decode_opts {
                                 * reference binary's per-tick cadence (online2-cli-nnet3-decode-faster.cc:143-161) -- lowest latency of
                                 * rs_streams_finish, most launches; 0 = the library's default, 16 (about a second of audio per advance: the
                                 * throughput setting).  RS_STREAM_MIN_TICKS=<n> overrides. */
-  int32_t reserved[2];
+  int32_t emit_alignment;      /* 1: results keep, per hypothesis, the transition-id of every decoder frame (rs_result_alignment, rs_result_phones):
+                                * nbest-to-linear's second output.  0 (rs_default_opts): nothing is computed, kept or copied for it.  0 or 1 only --
+                                * RS_OPT_UNSET is not a value (the reference has no such flag to take a value from): the model load refuses others. */
+  int32_t reserved[1];
 } rs_decode_opts;
 #define RS_FIXED_ONLINE 1
 #define RS_FIXED_DO_ENDPOINTING 2
@@ -333,6 +336,28 @@ int rs_result_costs(const rs_result *r, int32_t utt, int32_t k, float *graph_cos
  * "utt-<k> <id> <id> ... \n" per hypothesis (key prefix `key`, "utt" in the reference).  Returns the number
  * of bytes needed, like snprintf. */
 int rs_result_text(const rs_result *r, int32_t utt, const char *key, char *buf, size_t len);
+/* Alignments = the second output of nbest-to-linear (nbest-to-linear.cc:67-87: GetLinearSymbolSequence's input labels), which the
+ * reference sends to ark:/dev/null.  Needs rs_decode_opts.emit_alignment = 1; without it all three calls return RS_ERR_ARG with a
+ * message that names the option.  Results of rs_streams_partial carry none (RS_ERR_ARG: the partial traceback joins a cached path
+ * instead of walking every frame), nor do the records of rs_decode_batch_sharded (they are not rs_result objects).
+ * rs_result_alignment: the transition-ids of hypothesis k, one per DECODER frame (*n == rs_result_num_frames; with
+ *   --frame-subsampling-factor=f one per f feature frames) -- what the reference writes for key utt-<k+1>.  *tids stays valid until
+ *   rs_result_free.  A 1-best call without a lattice (nbest = 1, lattice scale 1, no emit_lattice) takes them from the search's own
+ *   traceback on the device; every other call from the lattice: the best alignment of the word sequence, ties of bit-identical
+ *   (total, graph) cost going to the shorter, then lexicographically smaller string (CompactLatticeWeight's order).
+ * rs_result_alignment_text: exactly the bytes `nbest-to-linear ark:- ark,t:- ark:/dev/null` prints ("<key>-<k> tid tid ... \n" per
+ *   hypothesis); returns the number of bytes needed, like rs_result_text.
+ * rs_result_phones: the alignment split into phones as SplitToPhones does (hmm/hmm-utils.cc:659-732; what `ali-to-phones
+ *   --write-lengths` prints): segment i is phone[i] over decoder frames [start_frame[i], start_frame[i] + num_frames[i]).  Host work
+ *   on the transition model the result's model was loaded with, following the reordered self-loop convention of graphs built with
+ *   --reorder=true (a phone's final transition-id may be followed by self-loops of the same transition-state).  An alignment that
+ *   does not split cleanly -- an rs_streams_finalize may end inside a phone -- fails with RS_ERR_DECODE and the reference's warning
+ *   "Could not split word into phones correctly (forced-out?)" (word-align-lattice-lexicon.cc:752), not with a guess. */
+int rs_result_alignment(const rs_result *r, int32_t utt, int32_t k, const int32_t **tids, int32_t *n);
+int rs_result_alignment_text(const rs_result *r, int32_t utt, const char *key, char *buf, size_t len);
+int rs_result_phones(const rs_result *r, int32_t utt, int32_t k, const int32_t **phone, const int32_t **start_frame, const int32_t **num_frames,
+                     int32_t *n);
+
 /* Fixed-size result records of the best hypothesis of every utterance, for the multi-GPU gather (one RCCL
  * all_gather of these records is the path's only exchange step): out[u * (max_words + 4)] =
  * {status (0 ok), n_words, word ids (max_words slots, truncated), graph cost bits, acoustic cost bits}. */
@@ -471,6 +496,22 @@ void rs_rescorer_free(rs_rescorer *r);
 int64_t rs_lattice_entry_from_raw(int32_t num_states, int32_t start, const float *final_cost, int32_t n_arcs, const int32_t *arc_src,
                                   const int32_t *arc_dst, const int32_t *arc_word, const int32_t *arc_tid, const float *arc_graph,
                                   const float *arc_acoustic, float beam, const char *key, char *buf, int64_t cap);
+
+/* Host-side entries for tests and tools (no GPU needed): what results with rs_decode_opts.emit_alignment carry, from the same code.
+ * rs_lattice_nbest_alignments_from_raw: the n-best word sequences of a raw lattice (given as for rs_lattice_entry_from_raw) with the
+ *   costs and the transition-ids of the best alignment of each, best first.  *n_out = hypotheses found (<= nbest); hypothesis k has
+ *   words word_buf[word_off[k] .. word_off[k + 1]) and transition-ids tid_buf[tid_off[k] .. tid_off[k + 1]) (the offset arrays hold
+ *   nbest + 1 entries; the offsets are always the true ones, ids beyond word_cap / tid_cap are not written -- RS_ERR_ARG then);
+ *   graph_cost / acoustic_cost: nbest entries, may be null.
+ * rs_alignment_phones: rs_result_phones' splitting of a transition-id sequence, with the transition model of `final_mdl`; *n_out =
+ *   segments (all of them counted, at most cap written). */
+int rs_lattice_nbest_alignments_from_raw(int32_t num_states, int32_t start, const float *final_cost, int32_t n_arcs, const int32_t *arc_src,
+                                         const int32_t *arc_dst, const int32_t *arc_word, const int32_t *arc_tid, const float *arc_graph,
+                                         const float *arc_acoustic, float beam, int32_t nbest, float acoustic_scale, int32_t *n_out,
+                                         int32_t *word_off, int32_t *word_buf, int32_t word_cap, int32_t *tid_off, int32_t *tid_buf, int32_t tid_cap,
+                                         float *graph_cost, float *acoustic_cost);
+int rs_alignment_phones(const char *final_mdl, const int32_t *tids, int32_t n_tids, int32_t *phone, int32_t *start_frame, int32_t *num_frames,
+                        int32_t cap, int32_t *n_out);
 
 #ifdef __cplusplus
 }

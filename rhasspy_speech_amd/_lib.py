@@ -24,7 +24,8 @@ class DecodeOpts(C.Structure):
         ("beam", C.c_float), ("max_active", C.c_int32), ("min_active", C.c_int32), ("lattice_beam", C.c_float),
         ("beam_delta", C.c_float), ("acoustic_scale", C.c_float), ("frames_per_chunk", C.c_int32),
         ("frame_subsampling_factor", C.c_int32), ("device_id", C.c_int32), ("keep_intermediates", C.c_int32),
-        ("max_tokens_per_frame", C.c_int32), ("emit_lattice", C.c_int32), ("prune_output_pdfs", C.c_int32), ("exact_token_order", C.c_int32), ("command_line_fixed", C.c_int32), ("stream_min_ticks", C.c_int32), ("reserved", C.c_int32 * 2),
+        ("max_tokens_per_frame", C.c_int32), ("emit_lattice", C.c_int32), ("prune_output_pdfs", C.c_int32), ("exact_token_order", C.c_int32), ("command_line_fixed", C.c_int32), ("stream_min_ticks", C.c_int32), ("emit_alignment", C.c_int32),
+        ("reserved", C.c_int32 * 1),
     ]
 
 
@@ -68,6 +69,7 @@ EXPORTS = [
     "rs_adaptation_new", "rs_streams_adaptation", "rs_stream_adaptation", "rs_stream_open_adapted", "rs_adaptation_export", "rs_adaptation_import",
     "rs_adaptation_free", "rs_result_num_utts", "rs_result_num_hyps",
     "rs_result_num_frames", "rs_result_words", "rs_result_costs", "rs_result_text", "rs_result_lattice", "rs_result_matrix",
+    "rs_result_alignment", "rs_result_alignment_text", "rs_result_phones", "rs_lattice_nbest_alignments_from_raw", "rs_alignment_phones",
     "rs_result_counters", "rs_result_timings", "rs_result_pack", "rs_result_free",
     "rs_mkgraph", "rs_fst_tool", "rs_fuzzy_open", "rs_fuzzy_match", "rs_result_fuzzy", "rs_fuzzy_free", "rs_lattice_entry_from_raw",
     "rs_rescorer_open", "rs_rescore_result", "rs_rescore_lattice", "rs_rescorer_free",
@@ -152,6 +154,12 @@ def load_library() -> C.CDLL:
     pf, pi = C.POINTER(f32), C.POINTER(i32)
     lib.rs_lattice_entry_from_raw.argtypes = [i32, i32, pf, i32, pi, pi, pi, pi, pf, pf, f32, C.c_char_p, C.c_char_p, C.c_int64]
     lib.rs_lattice_entry_from_raw.restype = C.c_int64
+    ppi = C.POINTER(pi)
+    lib.rs_result_alignment.argtypes = [vp, i32, i32, ppi, pi]
+    lib.rs_result_alignment_text.argtypes = [vp, i32, C.c_char_p, C.c_char_p, C.c_size_t]
+    lib.rs_result_phones.argtypes = [vp, i32, i32, ppi, ppi, ppi, pi]
+    lib.rs_lattice_nbest_alignments_from_raw.argtypes = [i32, i32, pf, i32, pi, pi, pi, pi, pf, pf, f32, i32, f32, pi, pi, pi, i32, pi, pi, i32, pf, pf]
+    lib.rs_alignment_phones.argtypes = [C.c_char_p, pi, i32, pi, pi, pi, i32, pi]
     return lib
 
 
@@ -243,6 +251,33 @@ class Result:
         buf = C.create_string_buffer(n + 1)
         lib().rs_result_text(self._h, utt, key.encode(), buf, n + 1)
         return buf.value
+
+    def alignment(self, utt: int, k: int = 0) -> np.ndarray:
+        """The transition-id of every decoder frame of hypothesis k (nbest-to-linear's second output); needs emit_alignment=1."""
+        ids = C.POINTER(C.c_int32)()
+        n = C.c_int32()
+        _check(lib().rs_result_alignment(self._h, utt, k, C.byref(ids), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, np.int32)
+        return np.ctypeslib.as_array(ids, shape=(n.value,)).copy()
+
+    def alignment_text(self, utt: int, key: str = "utt") -> bytes:
+        """The bytes `nbest-to-linear ark:- ark,t:- ark:/dev/null` would print for this utterance; needs emit_alignment=1."""
+        n = lib().rs_result_alignment_text(self._h, utt, key.encode(), None, 0)
+        if n < 0:
+            _check(n)
+        buf = C.create_string_buffer(n + 1)
+        lib().rs_result_alignment_text(self._h, utt, key.encode(), buf, n + 1)
+        return buf.value
+
+    def phones(self, utt: int, k: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(phone, start_frame, num_frames) of the phone segments of hypothesis k's alignment (SplitToPhones); needs emit_alignment=1."""
+        ph, st, ln = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+        n = C.c_int32()
+        _check(lib().rs_result_phones(self._h, utt, k, C.byref(ph), C.byref(st), C.byref(ln), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32)
+        return tuple(np.ctypeslib.as_array(p, shape=(n.value,)).copy() for p in (ph, st, ln))
 
     def lattice(self, utt: int, key: str = "utt") -> bytes:
         """One binary CompactLattice table entry (what online2-wav-nnet3-latgen-faster writes); needs emit_lattice=1."""
@@ -704,3 +739,39 @@ def lattice_entry_from_raw(num_states: int, start: int, final_cost, arcs, beam: 
     buf = C.create_string_buffer(int(size))
     lib().rs_lattice_entry_from_raw(*args, buf, size)
     return buf.raw
+
+
+def lattice_nbest_alignments_from_raw(num_states: int, start: int, final_cost, arcs, beam: float, nbest: int, acoustic_scale: float = 1.0):
+    """Host-only (no GPU): the n-best word sequences of a raw lattice (arguments as lattice_entry_from_raw) with the costs and the
+    transition-ids of the best alignment of each -- the code results with emit_alignment=1 take their alignments from.  Returns a
+    list of (words, transition_ids, graph_cost, acoustic_cost), best first."""
+    arcs = list(arcs)
+    n = len(arcs)
+    fc = np.ascontiguousarray(final_cost, dtype=np.float32)
+    cols = [np.ascontiguousarray([a[k] for a in arcs], dtype=np.int32) for k in range(4)]
+    g = np.ascontiguousarray([a[4] for a in arcs], dtype=np.float32)
+    ac = np.ascontiguousarray([a[5] for a in arcs], dtype=np.float32)
+    pi, pf = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    args = [num_states, start, fc.ctypes.data_as(pf), n, *[c.ctypes.data_as(pi) for c in cols], g.ctypes.data_as(pf), ac.ctypes.data_as(pf),
+            float(beam), int(nbest), float(acoustic_scale)]
+    cap = max(n, 1) * nbest        # a path uses an arc at most once
+    n_out = C.c_int32()
+    w_off, t_off = np.zeros(nbest + 1, np.int32), np.zeros(nbest + 1, np.int32)
+    w_buf, t_buf = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    gc, acc = np.zeros(nbest, np.float32), np.zeros(nbest, np.float32)
+    _check(lib().rs_lattice_nbest_alignments_from_raw(*args, C.byref(n_out), w_off.ctypes.data_as(pi), w_buf.ctypes.data_as(pi), cap,
+                                                      t_off.ctypes.data_as(pi), t_buf.ctypes.data_as(pi), cap, gc.ctypes.data_as(pf),
+                                                      acc.ctypes.data_as(pf)))
+    return [(w_buf[w_off[k]:w_off[k + 1]].tolist(), t_buf[t_off[k]:t_off[k + 1]].tolist(), float(gc[k]), float(acc[k])) for k in range(n_out.value)]
+
+
+def alignment_phones(final_mdl, tids) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host-only (no GPU): Result.phones' splitting of a transition-id sequence with the transition model of `final_mdl`."""
+    t = np.ascontiguousarray(tids, dtype=np.int32)
+    pi = C.POINTER(C.c_int32)
+    cap = max(len(t), 1)
+    ph, st, ln = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    n = C.c_int32()
+    _check(lib().rs_alignment_phones(str(final_mdl).encode(), t.ctypes.data_as(pi), len(t), ph.ctypes.data_as(pi), st.ctypes.data_as(pi),
+                                     ln.ctypes.data_as(pi), cap, C.byref(n)))
+    return ph[:n.value].copy(), st[:n.value].copy(), ln[:n.value].copy()

@@ -67,6 +67,10 @@ int ArgError(const char *msg) {
   g_last_error = msg;
   return RS_ERR_ARG;
 }
+// whether the hypotheses of a finished decode carry alignments (rs_decode_opts.emit_alignment)
+void MarkAlignment(rs::Result *r, const rs_model *model) {
+  if (r) r->alignment = model->m->opts().emit_alignment ? rs::Result::kAlignment : rs::Result::kNoAlignment;
+}
 }  // namespace
 
 extern "C" {
@@ -162,6 +166,7 @@ int rs_decode_batch(rs_model *model, const int16_t *const *pcm, const int32_t *n
     auto r = model->m->DecodeBatchHost(pcm, n_samples, n_utts, nbest, lattice_acoustic_scale);
     rs_result *res = new rs_result();
     res->r = std::move(r);
+    MarkAlignment(res->r.get(), model);
     *out = res;
     return RS_OK;
   });
@@ -174,6 +179,7 @@ int rs_decode_batch_device(rs_model *model, const int16_t *d_pcm, const int64_t 
     auto r = model->m->DecodeBatchDevice(d_pcm, sample_offsets, n_utts, nbest, lattice_acoustic_scale, (hipStream_t)stream);
     rs_result *res = new rs_result();
     res->r = std::move(r);
+    MarkAlignment(res->r.get(), model);
     *out = res;
     return RS_OK;
   });
@@ -357,6 +363,7 @@ int rs_streams_finish(rs_stream *const *streams, int32_t n_streams, int32_t nbes
       for (int i = 0; i < n_streams; i++) streams[i]->finished = true;      // whatever happens below, these streams are over
       streams[0]->model->m->StreamsAdvance(streams, n_streams, /*final=*/true, nbest, lattice_acoustic_scale, res->r.get());
     }
+    MarkAlignment(res->r.get(), streams[0]->model);
     for (int i = 0; i < n_streams; i++) {
       streams[i]->finished = true;
       std::vector<int16_t>().swap(streams[i]->pcm);
@@ -383,6 +390,7 @@ int rs_streams_partial(rs_stream *const *streams, int32_t n_streams, rs_result *
       for (int i = 0; i < n_streams; i++) streams[i]->failed = true;
       throw;
     }
+    res->r->alignment = rs::Result::kPartialResult;
     *out = res.release();
     return RS_OK;
   });
@@ -493,6 +501,7 @@ int rs_streams_finalize(rs_stream *const *streams, int32_t n_streams, int32_t nb
     res->r.reset(new rs::Result());
     for (int i = 0; i < n_streams; i++) streams[i]->finished = true;      // whatever happens below, these streams are over
     streams[0]->model->m->StreamsFinalize(streams, n_streams, nbest, lattice_acoustic_scale, res->r.get());
+    MarkAlignment(res->r.get(), streams[0]->model);
     for (int i = 0; i < n_streams; i++) {
       std::vector<int16_t>().swap(streams[i]->pcm);
       streams[i]->model->m->StreamEnd(streams[i], /*flushed=*/false);
@@ -672,6 +681,69 @@ int rs_result_text(const rs_result *r, int32_t utt, const char *key, char *buf, 
     buf[n] = 0;
   }
   return (int)s.size();
+}
+
+// The hypothesis list of utterance `utt` if its result carries alignments; else the status to return (message set).
+static int AlignedUtt(const rs_result *r, int32_t utt, const char *fn, const rs::UttResult **out) {
+  const rs::UttResult *u = Utt(r, utt);
+  if (!u) return ArgError((std::string(fn) + ": bad argument").c_str());
+  if (r->r->alignment == rs::Result::kPartialResult)
+    return ArgError((std::string(fn) + ": results of rs_streams_partial carry no alignment (rs_streams_finish / rs_streams_finalize results do, with "
+                     "rs_decode_opts.emit_alignment = 1)").c_str());
+  if (r->r->alignment != rs::Result::kAlignment)
+    return ArgError((std::string(fn) + ": the model was not opened with rs_decode_opts.emit_alignment = 1").c_str());
+  if (u->status != RS_OK) { g_last_error = u->error; return u->status; }
+  *out = u;
+  return RS_OK;
+}
+
+int rs_result_alignment(const rs_result *r, int32_t utt, int32_t k, const int32_t **tids, int32_t *n) {
+  if (!tids || !n) return ArgError("rs_result_alignment: bad argument");
+  const rs::UttResult *u = nullptr;
+  const int rc = AlignedUtt(r, utt, "rs_result_alignment", &u);
+  if (rc != RS_OK) return rc;
+  if (k < 0 || k >= (int32_t)u->hyps.size()) return ArgError("rs_result_alignment: hypothesis index out of range");
+  *tids = u->hyps[k].tids.data();
+  *n = (int32_t)u->hyps[k].tids.size();
+  return RS_OK;
+}
+
+int rs_result_alignment_text(const rs_result *r, int32_t utt, const char *key, char *buf, size_t len) {
+  const rs::UttResult *u = nullptr;
+  const int rc = AlignedUtt(r, utt, "rs_result_alignment_text", &u);
+  if (rc != RS_OK) return rc;
+  // BasicVectorHolder text form, like rs_result_text: "<key>-<k> tid tid ... \n"
+  std::string s;
+  const std::string ky = key ? key : "utt";
+  for (size_t k = 0; k < u->hyps.size(); k++) {
+    s += ky + "-" + std::to_string(k + 1) + " ";
+    for (int32_t t : u->hyps[k].tids) s += std::to_string(t) + " ";
+    s += "\n";
+  }
+  if (buf && len) {
+    size_t n = s.size() < len - 1 ? s.size() : len - 1;
+    std::memcpy(buf, s.data(), n);
+    buf[n] = 0;
+  }
+  return (int)s.size();
+}
+
+static const char *const kSplitWarning = "Could not split word into phones correctly (forced-out?)";      // word-align-lattice-lexicon.cc:752
+
+int rs_result_phones(const rs_result *r, int32_t utt, int32_t k, const int32_t **phone, const int32_t **start_frame, const int32_t **num_frames,
+                     int32_t *n) {
+  if (!phone || !start_frame || !num_frames || !n) return ArgError("rs_result_phones: bad argument");
+  const rs::UttResult *u = nullptr;
+  const int rc = AlignedUtt(r, utt, "rs_result_phones", &u);
+  if (rc != RS_OK) return rc;
+  if (k < 0 || k >= (int32_t)u->hyps.size()) return ArgError("rs_result_phones: hypothesis index out of range");
+  const rs::Hypothesis &h = u->hyps[k];
+  if (!h.phones_ok) { g_last_error = std::string("rs_result_phones: ") + kSplitWarning; return RS_ERR_DECODE; }
+  *phone = h.phones.data();
+  *start_frame = h.phone_start.data();
+  *num_frames = h.phone_len.data();
+  *n = (int32_t)h.phones.size();
+  return RS_OK;
 }
 
 int64_t rs_result_lattice(const rs_result *r, int32_t utt, const char *key, char *buf, int64_t cap) {
@@ -978,6 +1050,61 @@ int64_t rs_lattice_entry_from_raw(int32_t num_states, int32_t start, const float
     g_last_error = e.what();
     return RS_ERR_DECODE;
   }
+}
+
+int rs_lattice_nbest_alignments_from_raw(int32_t num_states, int32_t start, const float *final_cost, int32_t n_arcs, const int32_t *arc_src,
+                                         const int32_t *arc_dst, const int32_t *arc_word, const int32_t *arc_tid, const float *arc_graph,
+                                         const float *arc_acoustic, float beam, int32_t nbest, float acoustic_scale, int32_t *n_out,
+                                         int32_t *word_off, int32_t *word_buf, int32_t word_cap, int32_t *tid_off, int32_t *tid_buf, int32_t tid_cap,
+                                         float *graph_cost, float *acoustic_cost) {
+  if (num_states <= 0 || start < 0 || start >= num_states || !final_cost || n_arcs < 0 || nbest < 1 || !n_out || !word_off || !tid_off ||
+      word_cap < 0 || tid_cap < 0 || (word_cap > 0 && !word_buf) || (tid_cap > 0 && !tid_buf) ||
+      (n_arcs > 0 && (!arc_src || !arc_dst || !arc_word || !arc_tid || !arc_graph || !arc_acoustic)))
+    return ArgError("rs_lattice_nbest_alignments_from_raw: bad argument");
+  return Guard([&]() {
+    rs::RawLattice lat;
+    lat.start = start;
+    lat.num_states = num_states;
+    lat.final_cost.assign(final_cost, final_cost + num_states);
+    for (int i = 0; i < n_arcs; i++) {
+      if (arc_src[i] < 0 || arc_src[i] >= num_states || arc_dst[i] < 0 || arc_dst[i] >= num_states)
+        return ArgError("rs_lattice_nbest_alignments_from_raw: arc state out of range");
+      lat.arcs.push_back({arc_src[i], arc_dst[i], arc_word[i], (double)arc_graph[i], (double)arc_acoustic[i], arc_tid[i]});
+    }
+    const std::vector<rs::NbestPath> paths = rs::LatticeNbest(lat, nbest, beam, acoustic_scale, /*with_alignments=*/true);
+    *n_out = (int32_t)paths.size();
+    int64_t nw = 0, nt = 0;
+    word_off[0] = tid_off[0] = 0;
+    for (size_t k = 0; k < paths.size(); k++) {
+      for (int32_t w : paths[k].words) { if (nw < word_cap) word_buf[nw] = w; nw++; }
+      for (int32_t t : paths[k].tids) { if (nt < tid_cap) tid_buf[nt] = t; nt++; }
+      if (nw > INT32_MAX || nt > INT32_MAX) return ArgError("rs_lattice_nbest_alignments_from_raw: result too large");
+      word_off[k + 1] = (int32_t)nw;
+      tid_off[k + 1] = (int32_t)nt;
+      if (graph_cost) graph_cost[k] = (float)paths[k].graph_cost;
+      if (acoustic_cost) acoustic_cost[k] = (float)paths[k].acoustic_cost;
+    }
+    for (int k = (int)paths.size(); k < nbest; k++) { word_off[k + 1] = (int32_t)nw; tid_off[k + 1] = (int32_t)nt; }
+    if (nw > word_cap || nt > tid_cap) return ArgError("rs_lattice_nbest_alignments_from_raw: a buffer is too small (the offsets say how much is needed)");
+    return (int)RS_OK;
+  });
+}
+
+int rs_alignment_phones(const char *final_mdl, const int32_t *tids, int32_t n_tids, int32_t *phone, int32_t *start_frame, int32_t *num_frames,
+                        int32_t cap, int32_t *n_out) {
+  if (!final_mdl || n_tids < 0 || (n_tids > 0 && !tids) || cap < 0 || !n_out || (cap > 0 && (!phone || !start_frame || !num_frames)))
+    return ArgError("rs_alignment_phones: bad argument");
+  return Guard([&]() {
+    rs::KaldiReader rd(final_mdl);
+    rs::TransitionModel tm;
+    tm.Read(rd);
+    std::vector<int32_t> ph, st, ln;
+    const bool ok = rs::SplitAlignment(tm, std::vector<int32_t>(tids, tids + n_tids), &ph, &st, &ln);
+    *n_out = (int32_t)ph.size();
+    for (size_t i = 0; i < ph.size() && (int32_t)i < cap; i++) { phone[i] = ph[i]; start_frame[i] = st[i]; num_frames[i] = ln[i]; }
+    if (!ok) { g_last_error = std::string("rs_alignment_phones: ") + kSplitWarning; return (int)RS_ERR_DECODE; }
+    return (int)RS_OK;
+  });
 }
 
 }  // extern "C"

@@ -358,11 +358,15 @@ __device__ void FinishUtterance(Red<NT / 64> &red, const HclgDev &h, const Batch
   const bool path_ok = ok && path_len <= w.path_cap;
   double pg = 0.0, pa = 0.0;
   if (path_ok) {
+    int *ali = w.ali != nullptr ? w.ali + (size_t)u * w.ali_ld : nullptr;      // (emit_alignment; workgroup-uniform)
     for (int i = tid; i < path_len; i += NT) {
       const int arc = path[2 * i], Fs = path[2 * i + 1];
       const int4 a = h.arcs[arc];
       pg += (double)__int_as_float(a.z);
       if (a.x != 0) {
+        // the alignment: every emitting arc of the path has its own source frame, so this is one store per lane to a row the
+        // wave walks downwards (the path is stored last arc first)
+        if (ali != nullptr && (unsigned)Fs < (unsigned)w.ali_ld) ali[Fs] = arc;
         const float off = finfo[Fs * 4 + 0];
         const float lk = loglikes[(ll_base + Fs) * ld + (a.x - 1)];
         const float link_ac = off - lk;             // ForwardLink::acoustic_cost

@@ -485,6 +485,7 @@ __global__ __launch_bounds__(NT) void DecodeKernel(HclgDev h, DecodeOptsDev o, B
       int nw = 0;
       int *words = w.out_words + (size_t)u * w.max_words;
       bool truncated = false;
+      int *ali = w.ali != nullptr ? w.ali + (size_t)u * w.ali_ld : nullptr;      // (emit_alignment: the path's arc per frame)
       if (F >= 0 && n_cur > 0) {
         if (reached) graph += (double)h.final_cost[cur[idx].x];
         while (true) {
@@ -494,6 +495,7 @@ __global__ __launch_bounds__(NT) void DecodeKernel(HclgDev h, DecodeOptsDev o, B
           graph += (double)__int_as_float(arc.z);
           if (arc.x != 0) {
             F -= 1;
+            if (ali != nullptr && (unsigned)F < (unsigned)w.ali_ld) ali[F] = tk.w;      // (this stage has no parallel pass: the store rides on the walk, off its load chain)
             const float off = finfo[F * 4 + 0];
             const float lk = loglikes[(ll_base + F) * ld + (arc.x - 1)];
             const float link_ac = off - lk;                   // ForwardLink::acoustic_cost

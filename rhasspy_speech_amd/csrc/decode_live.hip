@@ -806,6 +806,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     double graph = 0.0, ac = 0.0;                  // (thread-local partial sums, reduced at the end)
     int nw = 0;                                    // (wave 0's lanes all hold it)
     bool truncated = false;
+    int *ali = w.ali != nullptr ? w.ali + (size_t)u * w.ali_ld : nullptr;      // (emit_alignment: the path's arc per frame)
     if (tid == 0) { c.bcast_i[0] = reached ? i1 : i2; c.bcast_i[1] = c.error ? -1 : T; c.bcast_i[2] = 0; }
     __syncthreads();
     bool done = c.error != 0 || n_cur == 0;
@@ -838,6 +839,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const int4 arc = h.arcs[hp.x];
         graph += (double)__int_as_float(arc.z);
         if (hp.y >= 0) {
+          if (ali != nullptr && hp.y < w.ali_ld) ali[hp.y] = hp.x;      // (one emitting arc per frame: nobody else writes this entry)
           const float off = finfo[hp.y * 4 + 0];
           const float lk = loglikes[(ll_base + hp.y) * ld + (arc.x - 1)];
           const float link_ac = off - lk;                   // ForwardLink::acoustic_cost

@@ -138,6 +138,8 @@ void Model::ResolveDecoderOptions() {
   // GetChunkSize (nnet-compile-looped.cc:81-94): the advised chunk rounded up to a multiple of the subsampling factor (and of the
   // network's modulus, which is 1 for every network the layer plan accepts)
   while (opts_.frames_per_chunk % opts_.frame_subsampling_factor != 0) opts_.frames_per_chunk++;
+  if (opts_.emit_alignment != 0 && opts_.emit_alignment != 1)
+    Fail("rs_decode_opts.emit_alignment must be 0 or 1, not " + std::to_string(opts_.emit_alignment) + " (RS_OPT_UNSET is not a value for it)");
 }
 
 // OnlineEndpointConfig's defaults (online-endpoint.h:152-157)
@@ -1341,8 +1343,12 @@ void Model::AllocSearch(SearchPlan *sp, DeviceArena &arena_, hipStream_t s) cons
   w.out_costs = arena_.AllocT<float>((size_t)n_utts * 4);
   w.counters = arena_.AllocT<long long>((size_t)n_utts * 8);
   if (!pooled_frames) w.frame_info = arena_.AllocT<float>((size_t)n_utts * (maxT + 1) * 4);
+  // emit_alignment: the traceback's arc per frame, [utt][frame].  Only where the traceback is the result: a call that goes on to the
+  // lattice takes its alignments from there (CollectResults)
+  if (sp->want_alignment && !sp->want_lattice && maxT > 0) { w.ali_ld = maxT; w.ali = arena_.AllocT<int>((size_t)n_utts * maxT); }
   DenseWork &dw = sp->dw;
   std::memset(&dw, 0, sizeof(dw));
+  dw.ali = w.ali; dw.ali_ld = w.ali_ld;
   if (c.rows()) {
     dw.out_words = w.out_words; dw.out_nwords = w.out_nwords; dw.out_costs = w.out_costs; dw.counters = w.counters;
     dw.frame_info = w.frame_info; dw.max_words = max_words;
@@ -1433,7 +1439,9 @@ void Model::CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const Batc
   int *h_nw = harena.AllocT<int>(n_utts), *h_words = harena.AllocT<int>((size_t)n_utts * kWordsInline);
   float *h_costs = harena.AllocT<float>((size_t)n_utts * 4);
   long long *h_ctr = harena.AllocT<long long>((size_t)n_utts * 8);
-  LaunchResultsToHost(w.out_nwords, w.out_costs, w.counters, w.out_words, max_words, std::min(kWordsInline, max_words), kWordsInline, n_utts, h_nw, h_costs, h_ctr, h_words, s);
+  int *h_ali = w.ali ? harena.AllocT<int>((size_t)n_utts * w.ali_ld) : nullptr;
+  LaunchResultsToHost(w.out_nwords, w.out_costs, w.counters, w.out_words, max_words, std::min(kWordsInline, max_words), kWordsInline, n_utts, h_nw, h_costs, h_ctr, h_words, s,
+                      w.ali, w.ali_ld, h_ali);
   RS_HIP(hipStreamSynchronize(s));
   RS_HIP(hipGetLastError());
   if (CheckGemmRange(cx)) throw RangeRetry{};      // an activation beyond the fp16 split's range: the call is repeated on the exact-FP32 GEMMs
@@ -1468,6 +1476,20 @@ void Model::CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const Batc
     }
     hy.graph_cost = h_costs[(size_t)u * 4 + 0];
     hy.acoustic_cost = h_costs[(size_t)u * 4 + 1];
+    if (h_ali) {      // arc -> transition-id (the device arcs carry pdf + 1)
+      const int *row = h_ali + (size_t)u * w.ali_ld;
+      bool good = T[u] <= w.ali_ld;
+      hy.tids.resize(good ? T[u] : 0);
+      for (int t = 0; good && t < T[u]; t++) {
+        good = row[t] >= 0 && (size_t)row[t] < arc_ilabel_.size() && arc_ilabel_[row[t]] != 0;
+        if (good) hy.tids[t] = arc_ilabel_[row[t]];
+      }
+      if (!good) {      // (cannot happen: a path that fits path_cap has exactly one emitting arc per frame)
+        ur.status = RS_ERR_DECODE;
+        ur.error = "internal error: the best path's alignment does not name one emitting arc per frame";
+        continue;
+      }
+    }
     ur.hyps.push_back(std::move(hy));
   }
   // ---- n-best through the lattice (the reference's determinise | lattice-to-nbest | nbest-to-linear tail)
@@ -1551,7 +1573,7 @@ void Model::CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const Batc
         if (a->arc < 0) { lat.final_cost[id_of[a->src]] = a->graph; continue; }
         lat.arcs.push_back({id_of[a->src], id_of[a->dst], hclg_.arcs[a->arc].olabel, (double)a->graph, (double)a->acoustic, hclg_.arcs[a->arc].ilabel});
       }
-      std::vector<NbestPath> paths = LatticeNbest(lat, nbest, opts_.lattice_beam, unscale ? lat_scale / opts_.acoustic_scale : lat_scale);
+      std::vector<NbestPath> paths = LatticeNbest(lat, nbest, opts_.lattice_beam, unscale ? lat_scale / opts_.acoustic_scale : lat_scale, sp.want_alignment);
       ur.counters[4] = (int64_t)lat.arcs.size();
       if (opts_.emit_lattice) {
         ur.clat = std::make_shared<CompactLat>(DeterminizeLattice(lat, opts_.lattice_beam));
@@ -1568,6 +1590,7 @@ void Model::CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const Batc
         hy.words = p.words;
         hy.graph_cost = (float)p.graph_cost;
         hy.acoustic_cost = (float)(unscale ? p.acoustic_cost / opts_.acoustic_scale : p.acoustic_cost);
+        hy.tids = std::move(p.tids);
         ur.hyps.push_back(std::move(hy));
       }
     };
@@ -1601,7 +1624,11 @@ void Model::CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const Batc
       std::fprintf(stderr, "lattice tail: kernel + count %.2f ms, %zu arcs (%.1f MB) to the host %.2f ms, grouping %.2f ms, %d utterances on %d threads %.2f ms\n",
                    lt_ms[0], n_arcs, n_arcs * sizeof(LatArc) / 1e6, lt_ms[1], lt_ms[2], n_utts, nthr, lt_ms[3]);
     timings[7] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_l0).count();
-  }}
+  }
+  if (sp.want_alignment)
+    for (int u = 0; u < n_utts; u++)
+      for (Hypothesis &hy : out_utts[u].hyps) hy.phones_ok = SplitAlignment(am_.trans, hy.tids, &hy.phones, &hy.phone_start, &hy.phone_len);
+}
 
 // One utterance group of a batch call: its host geometry, and what each stage of DecodeGroup leaves for the next
 struct BatchCall {
@@ -1881,6 +1908,7 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   for (int u = 0; u < n_utts; u++) out_utts[u].num_frames = b.T_dec[u];
   SearchPlan sp;
   PlanSearch(SearchRequestFor(n_utts, b.maxT_dec, nbest, lat_scale), &sp);
+  sp.want_alignment = opts_.emit_alignment != 0;
   b.arena->Reset(s);
   // The last layer and the search can be pipelined over time slabs when the search is the register-resident kernel: the
   // output GEMM of slab k+1 (MFMA-bound) runs while slab k is searched (latency-bound) on a second, high-priority stream.

@@ -51,6 +51,9 @@ using HostArena = Arena<PinnedBlocks>;
 struct Hypothesis {
   std::vector<int32_t> words;
   float graph_cost = 0, acoustic_cost = 0;
+  // emit_alignment only: the transition-id of every decoder frame, and its phone segments (SplitAlignment)
+  std::vector<int32_t> tids, phones, phone_start, phone_len;
+  bool phones_ok = false;
 };
 struct UttResult {
   int status = RS_OK;
@@ -63,6 +66,8 @@ struct UttResult {
   std::shared_ptr<CompactLat> clat;              // emit_lattice only
 };
 struct Result {
+  enum { kNoAlignment = 0, kAlignment = 1, kPartialResult = 2 };
+  int alignment = kNoAlignment;      // whether the hypotheses carry alignments; if not, why
   std::vector<UttResult> utts;
   float timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
@@ -120,6 +125,7 @@ struct RowMaps {
 struct SearchPlan {
   SearchCall call{};
   bool unscale = false, want_lattice = false;      // (call.unscale, call.want_lattice)
+  bool want_alignment = false;       // rs_decode_opts.emit_alignment, set by the calls whose results carry alignments (not the partials)
   int S = 0, tok_cap = 0, max_words = 1024, maxT = 0, n_utts = 0;
   DecodeOptsDev dopts{};
   DecodeWork w{};

@@ -605,17 +605,21 @@ void LaunchCopyRows(const void *src, long src_ld_words, const int *src_row, void
 // (their 25 MB sample uploads).
 __global__ __launch_bounds__(64) void ResultsToHostKernel(const int *__restrict__ nw, const float *__restrict__ costs, const long long *__restrict__ ctr,
                                                           const int *__restrict__ words, int max_words, int inline_words, int h_stride, int *h_nw,
-                                                          float *h_costs, long long *h_ctr, int *h_words) {
+                                                          float *h_costs, long long *h_ctr, int *h_words, const int *__restrict__ ali, int ali_ld,
+                                                          int *h_ali) {
   const int u = blockIdx.x, t = threadIdx.x;
   if (t == 0) h_nw[u] = nw[u];
   if (t < 4) h_costs[(size_t)u * 4 + t] = costs[(size_t)u * 4 + t];
   if (t < 8) h_ctr[(size_t)u * 8 + t] = ctr[(size_t)u * 8 + t];
   for (int k = t; k < inline_words; k += 64) h_words[(size_t)u * h_stride + k] = words[(size_t)u * max_words + k];
+  if (ali != nullptr)      // (rs_decode_opts.emit_alignment: the alignment rows ride along)
+    for (int k = t; k < ali_ld; k += 64) h_ali[(size_t)u * ali_ld + k] = ali[(size_t)u * ali_ld + k];
 }
 void LaunchResultsToHost(const int *nw, const float *costs, const long long *ctr, const int *words, int max_words, int inline_words, int h_stride, int n,
-                         int *h_nw, float *h_costs, long long *h_ctr, int *h_words, hipStream_t s) {
+                         int *h_nw, float *h_costs, long long *h_ctr, int *h_words, hipStream_t s, const int *ali, int ali_ld, int *h_ali) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(ResultsToHostKernel, dim3(n), dim3(64), 0, s, nw, costs, ctr, words, max_words, inline_words, h_stride, h_nw, h_costs, h_ctr, h_words);
+  hipLaunchKernelGGL(ResultsToHostKernel, dim3(n), dim3(64), 0, s, nw, costs, ctr, words, max_words, inline_words, h_stride, h_nw, h_costs, h_ctr, h_words,
+                     h_ali ? ali : nullptr, ali_ld, h_ali);
 }
 
 // ------------------------------------------------------------------------------------------ row geometry

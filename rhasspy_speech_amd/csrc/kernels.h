@@ -79,8 +79,10 @@ struct CopyRowsSet {
 void LaunchCopyRowsMulti(const CopyRowsSet &set, const int *src_row, const int *dst_row, int n, hipStream_t s);
 // h_*: page-locked host memory the device can store into (hipHostMalloc); the first inline_words word ids of utterance u go to
 // h_words[u * h_stride ...] (copy count and destination pitch are separate: ADVICE r05)
+// ali (null: none): the alignment rows [n][ali_ld] (DecodeWork::ali) go to h_ali in the same layout
 void LaunchResultsToHost(const int *nw, const float *costs, const long long *ctr, const int *words, int max_words, int inline_words, int h_stride, int n,
-                         int *h_nw, float *h_costs, long long *h_ctr, int *h_words, hipStream_t s);
+                         int *h_nw, float *h_costs, long long *h_ctr, int *h_words, hipStream_t s, const int *ali = nullptr, int ali_ld = 0,
+                         int *h_ali = nullptr);
 void LaunchCopyRows(const void *src, long src_ld_words, const int *src_row, void *dst, long dst_ld_words, const int *dst_row, int n, int width_words,
                     hipStream_t s);
 
@@ -268,6 +270,10 @@ struct DecodeWork {
   float *out_costs;           // n_utts x 4 : graph, acoustic, total, final-reached flag
   long long *counters;        // n_utts x 8
   int max_words;
+  // rs_decode_opts.emit_alignment: the best path's arc per decoder frame, [utt][frame] with row stride ali_ld (>= the call's largest
+  // frame count; a stream's frames are its absolute decoder frames); null = not asked for, nothing is written
+  int *ali;
+  int ali_ld;
 };
 void LaunchDecode(const HclgDev &h, const DecodeOptsDev &o, const BatchGeom &g, const float *loglikes, int ld,
                   const DecodeWork &w, hipStream_t s);
@@ -301,6 +307,8 @@ struct DenseWork {
   int max_words;
   int *path;                  // n_utts x path_cap x 2 scratch: best path as (arc, frame) pairs
   int path_cap;
+  int *ali = nullptr;         // DecodeWork::ali / ali_ld
+  int ali_ld = 0;
   // n-best / lattice calls on grammar graphs (RegDecodeKernel + LaunchDenseToTokens): the costs of every (frame, state) beside the
   // back-pointer rows, +inf = no token; null = not kept
   float *cost_rows = nullptr; // n_utts x (max_frames + 1) x S

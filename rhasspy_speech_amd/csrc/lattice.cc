@@ -11,6 +11,7 @@
 #include <unordered_map>
 
 #include "kaldi_io.h"
+#include "model.h"
 
 namespace rs {
 namespace {
@@ -36,9 +37,78 @@ struct HeapItem {
   bool operator<(const HeapItem &o) const { return f > o.f || (f == o.f && id > o.id); }   // min-heap
 };
 
+// The best alignment of one word sequence: a shortest path through (words consumed, lattice state), the states of a layer
+// in topological order.  An arc without a word stays in its layer, an arc with the layer's next word goes one layer up.
+// Sums are taken in path order like LatticeNbest's own, so the winner's costs are the ones it reports.  Ties of (total,
+// graph) go to the shorter, then the lexicographically smaller transition-id string; both strings are read off the back
+// pointers only then.  Only the (layer, state) pairs that are reached get a cell: a state lies in few layers.
+std::vector<int32_t> BestAlignment(const RawLattice &lat, const std::vector<int> &begin, const std::vector<int> &order, const std::vector<int> &topo,
+                                   const std::vector<int32_t> &words) {
+  const int N = lat.num_states, L = (int)words.size();
+  const double INF = std::numeric_limits<double>::infinity();
+  struct Cell { Pair w; int state, arc, parent; };      // arc: the lattice arc the cell was reached by, from cell `parent` (-1: the start)
+  std::vector<Cell> cells;
+  auto string_of = [&](int arc, int parent) {           // the transition-ids of the path that ends with `arc` out of cell `parent`
+    std::vector<int32_t> rev;
+    while (arc >= 0) {
+      if (lat.arcs[arc].ilabel != 0) rev.push_back(lat.arcs[arc].ilabel);
+      arc = cells[parent].arc;
+      parent = cells[parent].parent;
+    }
+    std::reverse(rev.begin(), rev.end());
+    return rev;
+  };
+  auto loses = [](const std::vector<int32_t> &x, const std::vector<int32_t> &y) { return x.size() > y.size() || (x.size() == y.size() && !(x < y)); };
+  std::vector<int> idx[2] = {std::vector<int>(N, -1), std::vector<int>(N, -1)}, stamp[2] = {std::vector<int>(N, -1), std::vector<int>(N, -1)};
+  using QItem = std::pair<int, int>;                    // (topological rank, state)
+  std::priority_queue<QItem, std::vector<QItem>, std::greater<QItem>> q[2];
+  // a state new in its layer is queued; one seen before keeps the better of the two ways in
+  auto relax = [&](int layer, int dst, const Pair &w, int arc, int parent) {
+    const int b = layer & 1;
+    if (stamp[b][dst] != layer) {
+      stamp[b][dst] = layer;
+      idx[b][dst] = (int)cells.size();
+      cells.push_back(Cell{w, dst, arc, parent});
+      q[b].push({topo[dst], dst});
+      return;
+    }
+    Cell &c = cells[idx[b][dst]];
+    if (Better(c.w, w)) return;
+    if (!Better(w, c.w) && loses(string_of(arc, parent), string_of(c.arc, c.parent))) return;      // bit-identical weights: the strings decide
+    c.w = w; c.arc = arc; c.parent = parent;
+  };
+  relax(0, lat.start, Pair{0, 0}, -1, -1);
+  bool have = false;
+  Pair best{0, 0};
+  std::vector<int32_t> best_str;
+  for (int l = 0; l <= L; l++) {
+    const int b = l & 1;
+    while (!q[b].empty()) {
+      const int s = q[b].top().second;
+      q[b].pop();
+      const int ci = idx[b][s];
+      const Cell c = cells[ci];                         // (final: every arc into it came from a lower layer or a lower rank)
+      for (int k = begin[s]; k < begin[s + 1]; k++) {
+        const RawLattice::Arc &a = lat.arcs[order[k]];
+        const Pair w{c.w.g + a.graph, c.w.a + a.acoustic};
+        if (a.olabel == 0) relax(l, a.dst, w, order[k], ci);
+        else if (l < L && a.olabel == words[l]) relax(l + 1, a.dst, w, order[k], ci);
+      }
+      if (l == L && lat.final_cost[s] < INF) {
+        const Pair w{c.w.g + lat.final_cost[s], c.w.a};
+        if (have && Better(best, w)) continue;
+        std::vector<int32_t> str = string_of(c.arc, c.parent);
+        if (have && !Better(w, best) && loses(str, best_str)) continue;
+        best = w; best_str = std::move(str); have = true;
+      }
+    }
+  }
+  return best_str;
+}
+
 }  // namespace
 
-std::vector<NbestPath> LatticeNbest(const RawLattice &lat, int n, double lattice_beam, double acoustic_scale) {
+std::vector<NbestPath> LatticeNbest(const RawLattice &lat, int n, double lattice_beam, double acoustic_scale, bool with_alignments) {
   std::vector<NbestPath> out;
   const int N = lat.num_states;
   if (N == 0 || lat.start < 0 || n <= 0) return out;
@@ -189,7 +259,63 @@ std::vector<NbestPath> LatticeNbest(const RawLattice &lat, int n, double lattice
       return x.graph_cost + acoustic_scale * x.acoustic_cost < y.graph_cost + acoustic_scale * y.acoustic_cost;
     });
   if ((int)found.size() > n) found.resize(n);
+  if (with_alignments)
+    for (NbestPath &p : found) p.tids = BestAlignment(lat, begin, order, topo, p.words);
   return found;
+}
+
+// ------------------------------------------------------------------------------------------ phone segments
+bool SplitAlignment(const TransitionModel &tm, const std::vector<int32_t> &ali, std::vector<int32_t> *phone, std::vector<int32_t> *start,
+                    std::vector<int32_t> *len) {
+  phone->clear(); start->clear(); len->clear();
+  const size_t n = ali.size();
+  if (n == 0) return true;
+  const int ntid = tm.NumTransitionIds();
+  for (int32_t t : ali) if (t < 1 || t > ntid) Fail("alignment holds " + std::to_string(t) + ", which is no transition-id of the model");
+  auto tstate = [&](size_t i) { return tm.id2tstate[ali[i]]; };
+  auto self_loop = [&](size_t i) { return tm.id2self_loop[ali[i]] != 0; };
+  // TransitionModel::IsFinal (transition-model.cc:434-446): the transition leads to the topology entry's last state
+  auto is_final = [&](size_t i) {
+    const int ts = tstate(i);
+    const TransitionModel::Tuple &tp = tm.tuples[ts - 1];
+    const std::vector<TransitionModel::HmmState> &entry = tm.topo_entries[tm.phone2entry[tp.phone]];
+    const int idx = ali[i] - tm.tstate_first_tid[ts];
+    return entry[tp.hmm_state].trans[idx].first + 1 == (int)entry.size();
+  };
+  // IsReordered: does the self-loop follow the transition out of its state?
+  bool reordered = false, decided = false;
+  for (size_t i = 0; i + 1 < n && !decided; i++)
+    if (tstate(i) != tstate(i + 1)) {
+      if (self_loop(i)) { reordered = true; decided = true; }
+      else if (self_loop(i + 1)) { reordered = false; decided = true; }
+    }
+  if (!decided) reordered = !self_loop(0) && self_loop(n - 1);
+  bool ok = true;
+  std::vector<size_t> ends;
+  for (size_t i = 0; i < n; i++) {
+    if (is_final(i)) {
+      if (reordered) while (i + 1 < n && self_loop(i + 1) && tstate(i + 1) == tstate(i)) i++;
+      // (the reference asserts the equal transition-state; here an alignment that breaks it ends the phone and fails the check below)
+      ends.push_back(i + 1);
+    } else if (i + 1 == n) {
+      ok = false;
+      ends.push_back(i + 1);
+    } else if (tstate(i) != tstate(i + 1) && tm.tuples[tstate(i) - 1].phone != tm.tuples[tstate(i + 1) - 1].phone) {
+      ok = false;
+      ends.push_back(i + 1);
+    }
+  }
+  size_t cur = 0;
+  for (size_t e : ends) {
+    const TransitionModel::Tuple &tp = tm.tuples[tstate(cur) - 1];
+    // a phone whose initial state emits must start in it
+    if (tm.topo_entries[tm.phone2entry[tp.phone]][0].fwd != -1 && tp.hmm_state != 0) ok = false;
+    phone->push_back(tp.phone);
+    start->push_back((int32_t)cur);
+    len->push_back((int32_t)(e - cur));
+    cur = e;
+  }
+  return ok;
 }
 
 // ------------------------------------------------------------------------------------------ determinisation

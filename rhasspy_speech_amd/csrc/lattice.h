@@ -18,13 +18,23 @@ struct RawLattice {
 struct NbestPath {
   std::vector<int32_t> words;
   double graph_cost = 0, acoustic_cost = 0;
+  std::vector<int32_t> tids;      // with_alignments only: the transition-ids of the best alignment, one per frame
 };
 
 // Up to n distinct word sequences in increasing (graph + acoustic_scale * acoustic) order, restricted to
 // sequences whose best alignment is within lattice_beam of the best path (the determinisation beam,
 // lat/determinize-lattice-pruned.cc:1488-1513); each with the (graph, acoustic) costs of its best alignment
 // (LatticeWeight comparison: total, then graph part; fstext/lattice-weight.h:294-307).
-std::vector<NbestPath> LatticeNbest(const RawLattice &lat, int n, double lattice_beam, double acoustic_scale);
+// with_alignments: every path also carries the transition-ids of that alignment -- what nbest-to-linear writes as its second
+// output.  Among alignments of bit-identical (total, graph) the order is CompactLatticeWeight's (fstext/lattice-weight.h:
+// 603-640): the shorter string, then the lexicographically smaller one.
+std::vector<NbestPath> LatticeNbest(const RawLattice &lat, int n, double lattice_beam, double acoustic_scale, bool with_alignments = false);
+
+// SplitToPhones (hmm/hmm-utils.cc:659-732) with IsReordered (:625-650): the phone segments of an alignment, as `ali-to-phones
+// --write-lengths` prints them.  false = the reference's function returns false (the segments are its output all the same).
+struct TransitionModel;
+bool SplitAlignment(const TransitionModel &tm, const std::vector<int32_t> &tids, std::vector<int32_t> *phone, std::vector<int32_t> *start,
+                    std::vector<int32_t> *len);
 
 // Word-determinised lattice in Kaldi's CompactLattice form: an acceptor over word ids whose arc / final weights carry
 // (graph cost, acoustic cost) and the transition-id string of the best alignment.

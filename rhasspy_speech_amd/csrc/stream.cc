@@ -994,6 +994,7 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
   SearchRequest rq = SearchRequestFor(n, plan.maxT, nbest, lat_scale);
   rq.stream_window = true; rq.any_final = final;
   PlanSearch(rq, &sp);
+  sp.want_alignment = final && opts_.emit_alignment != 0;
   const bool reg_windows = sp.call.windows;
   clock.Mark(&p->host_ms[0]);
   AdvanceUpload(p, streams, plan, final, &set);
