@@ -896,7 +896,8 @@ std::string Model::Describe() const {
      << " (split-fp16 carries an operand row to 2^-22 of its largest element while that element lies in [2^-3, 65520): a row with |x| >= 65520, infinity"
         " or NaN, or a non-zero row whose largest |x| is below 2^-3, raises a flag and the call is repeated on the exact-FP32 kernels; the third such call"
         " makes them permanent)\n";
-  // (what the decode contexts' arenas hold; `allocations` stands still once the model has seen its largest call twice)
+  // (what the decode contexts' arenas hold; `allocations` stands still once the model has seen its largest call twice -- but for
+  // one per arena when a further context serves its first call: PublishRounds)
   size_t dev[3] = {0, 0, 0}, host[3] = {0, 0, 0};
   auto add = [&](const DecodeContext &c) {
     for (const DeviceArena &a : c.arena) { dev[0] += a.blocks(); dev[1] += a.bytes(); dev[2] += a.allocations(); }
@@ -1012,9 +1013,11 @@ std::unique_ptr<Result> Model::DecodeBatchHost(const int16_t *const *pcm, const 
     res->timings[0] = h2d_ms;
     res->timings[6] += h2d_ms;
   } catch (...) {
+    PublishRounds(*cx);      // (an arena stays consistent whatever its call throws: a round cut short counts for what it asked for)
     ReleaseContext(cx);
     throw;
   }
+  PublishRounds(*cx);
   ReleaseContext(cx);
   return res;
 }
@@ -1028,9 +1031,11 @@ std::unique_ptr<Result> Model::DecodeBatchDevice(const int16_t *d_pcm, const int
   try {
     res = DecodeInContext(*cx, d_pcm, sample_offsets, n_utts, nbest, lat_scale, user_stream, streaming);
   } catch (...) {
+    PublishRounds(*cx);      // (an arena stays consistent whatever its call throws: a round cut short counts for what it asked for)
     ReleaseContext(cx);
     throw;
   }
+  PublishRounds(*cx);
   ReleaseContext(cx);
   return res;
 }
@@ -1066,6 +1071,14 @@ Model::DecodeContext *Model::AcquireContext() {
 bool Model::OthersInFlight() {
   static const bool on = [] { const char *e = TuneEnv("RS_MFCC_EXCLUSIVE"); return e && std::atoi(e) != 0; }();
   return on && g_calls_in_flight.load() > 1;
+}
+// What this context's arenas asked for in their last rounds, for the siblings' (and its own) next Resets: engine.h, round_mark_.
+// Called by the thread that owns the context, after the call's group threads have been joined.
+void Model::PublishRounds(const DecodeContext &cx) {
+  for (int i = 0; i < DecodeContext::kSets; i++) {
+    round_mark_[0][i].Raise(cx.arena[i].round());
+    round_mark_[1][i].Raise(cx.host_arena[i].round());
+  }
 }
 void Model::ReleaseContext(DecodeContext *cx) {
   { std::lock_guard<std::mutex> lk(ctx_mu_); cx->busy = false; g_calls_in_flight.fetch_sub(1); }
@@ -1634,6 +1647,7 @@ void Model::CollectResults(SearchPlan &sp, DecodeContext &cx, int gi, const Batc
 struct BatchCall {
   DeviceArena *arena = nullptr;
   HostArena *harena = nullptr;
+  int set = 0;      // which of the context's arena sets (Model::round_mark_ is kept per set)
   hipStream_t s = nullptr;
   int n_utts = 0, share = 1;
   bool streaming = false;
@@ -1692,7 +1706,7 @@ void Model::BatchFrames(const int64_t *sample_offsets, BatchCall *b) const {
   }
   b->rows = b->row_base[n];
   b->guard = L_ + R_ + 8;
-  b->harena->Reset(b->s);
+  b->harena->Reset(b->s, round_mark_[1][b->set].get());
   if (b->streaming && fc_.ie.present) {
     b->row_ivec = b->harena->AllocT<int>(b->rows);
     PlanBatchSchedule(PlanCfg(), b->ns.data(), b->T.data(), b->row_base.data(), n, b->row_ivec, &b->sched);
@@ -1903,13 +1917,13 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   const Nnet &nn = am_.nnet;
   const int fsf = opts_.frame_subsampling_factor;
   BatchCall b;
-  b.arena = &cx.arena[gi]; b.harena = &cx.host_arena[gi]; b.s = s; b.n_utts = n_utts; b.share = cx.active_groups; b.streaming = streaming;
+  b.arena = &cx.arena[gi]; b.harena = &cx.host_arena[gi]; b.set = gi; b.s = s; b.n_utts = n_utts; b.share = cx.active_groups; b.streaming = streaming;
   BatchFrames(sample_offsets, &b);
   for (int u = 0; u < n_utts; u++) out_utts[u].num_frames = b.T_dec[u];
   SearchPlan sp;
   PlanSearch(SearchRequestFor(n_utts, b.maxT_dec, nbest, lat_scale), &sp);
   sp.want_alignment = opts_.emit_alignment != 0;
-  b.arena->Reset(s);
+  b.arena->Reset(s, round_mark_[0][gi].get());
   // The last layer and the search can be pipelined over time slabs when the search is the register-resident kernel: the
   // output GEMM of slab k+1 (MFMA-bound) runs while slab k is searched (latency-bound) on a second, high-priority stream.
   // Measured on the bench batch: 5.07 -> 4.97 ms with 3 slabs -- the search runs at half speed while it shares the CUs

@@ -27,7 +27,8 @@ void HipCheck(hipError_t e, const char *what, const char *file, int line);
 #define RS_HIP(x) ::rs::HipCheck((x), #x, __FILE__, __LINE__)
 
 // The two arenas of a decode call (arena.h: blocks appended on demand, coalesced into one by the Reset that follows, so that a warm
-// call allocates nothing).  Device memory: every block zero-filled when it is allocated, and its last 1 MiB never handed out -- some
+// call allocates nothing; the first call of a further decode context of a model is told the rounds its siblings have completed --
+// Model::round_mark_ -- and starts with that one block).  Device memory: every block zero-filled when it is allocated, and its last 1 MiB never handed out -- some
 // kernels read a little past the end of their last buffer (the + 256 / + 8 / + 64 at the allocation sites), which has to stay in
 // mapped memory.  Page-locked host staging: the small H2D / D2H transfers of a call are truly asynchronous from it and never wait on
 // a pageable-memory bounce buffer.
@@ -253,6 +254,13 @@ class Model {
   };
   std::vector<std::unique_ptr<DecodeContext>> ctx_;
   std::mutex ctx_mu_;
+  // The largest round any context's arena of a set has completed, [0] device, [1] host.  The contexts of a model serve the same
+  // traffic: a context publishes its rounds when its call ends (PublishRounds, before ReleaseContext -- not at its next Reset, which
+  // in a burst of first calls comes after the siblings have started), and the Resets of a batch call pass the mark on, so that a
+  // context's first call makes one allocation per arena instead of a spill and a coalescing call in the middle of the others' work.
+  // (atomic: written and read by calls on different threads, like the counters Describe reads)
+  RoundMark round_mark_[2][DecodeContext::kSets];
+  void PublishRounds(const DecodeContext &cx);
   // Calls in flight on one model pass through the feature + iVector stage and through the acoustic-model stage ONE AFTER THE
   // OTHER (each stage's kernels fill the device; two calls in the same stage only slow each other down), so calls that arrive
   // at the same moment come out staggered -- the first after one call's latency, not all of them after four -- and the pipeline
