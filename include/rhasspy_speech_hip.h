@@ -119,7 +119,15 @@ void rs_model_free(rs_model *model);
  * beyond 5000 states, where nothing asks), the largest emitting / epsilon out-degree -- and decided at load: the register-resident
  * search's shape (reg=none: the graph fits none), its closure rounds (-1: until nothing changes), whether exact_token_order applies,
  * whether the LDS-resident dense search does, the lattice kernel of an n-best call (none: the graph is beyond its 2048 states / 8192
- * arcs), and the smallest batch that gets the crowded shape (half the waves, twice the arcs per thread: 4 n_utts >= 3 CUs). */
+ * arcs), and the smallest batch that gets the crowded shape (half the waves, twice the arcs per thread: 4 n_utts >= 3 CUs).
+ * A model opened with keep_intermediates = 1 also prints, for every distinct layer GEMM its most recent decode call or stream advance
+ * launched (in launch order; the iVector branch's two splice + LDA launches included)
+ *   gemm_launch: <op name> rows=R n=N ksteps=K <kernel> blocks=B threads=T nbig=F nfirst=S res=0|1 img=0|1
+ * the op as on its `op:` line (the name may hold blanks), the rows and columns of the product, the 16-wide k-steps of the split-fp16
+ * k loop, the kernel instantiation by its template arguments -- Exact<MT,WM,WN,vec,dma>, B3<MR,MIXED,WM>, B3I<MR,MIXED,KPS> or
+ * B3J<WM,MIXED,STRIP,SDIV,MRT,WN> -- the grid, the full-height row tiles, the small tiles launched in front of them, whether a
+ * residual pass follows the kernel and whether the launch writes the operand image.  With keep_intermediates = 0 nothing is recorded
+ * and no such line is printed. */
 int rs_model_describe(const rs_model *model, char *buf, size_t len);
 /* The check the reference makes when a waveform arrives (OnlineGenericBaseFeature::MaybeCreateResampler, feat/online-feature.cc:
  * 86-101; online2-wav-nnet3-latgen-faster.cc:233 hands it WaveData::SampFreq()): RS_OK when `sample_rate` is the model's

@@ -891,6 +891,10 @@ std::string Model::Describe() const {
   const bool exact_asked = ExactOrder(), exact_ok = search_load_.exact_ok;
   os << "token_order: " << (exact_asked && exact_ok ? "exact (the reference's running cutoff in its hash order)" : "final cutoff")
      << (exact_asked && !exact_ok ? " (exact_token_order asked for: not applicable to this graph)" : "") << "\n";
+  if (opts_.keep_intermediates) {      // (the most recent decode call's or stream advance's, one line per distinct launch)
+    std::lock_guard<std::mutex> lk(gemm_rec_mu_);
+    for (const std::string &l : gemm_rec_) os << "gemm_launch: " << l << "\n";
+  }
   os << "layer_gemm: range_retries=" << range_retries_.load() << " precision_retries=" << precision_retries_.load() << " exact_fp32=" << (exact_gemm_.load() ? 1 : 0)
      << " regime=" << (exact_gemm_.load() ? "exact-fp32" : "split-fp16")
      << " (split-fp16 carries an operand row to 2^-22 of its largest element while that element lies in [2^-3, 65520): a row with |x| >= 65520, infinity"
@@ -1047,6 +1051,27 @@ static std::atomic<int> g_calls_in_flight{0};      // decode calls of any model 
 thread_local bool tls_exact_gemm = false;
 thread_local int *tls_gemm_ovf_dev = nullptr;
 void SampleGemmMode(bool exact, int *ovf_dev) { tls_exact_gemm = exact; tls_gemm_ovf_dev = ovf_dev; }
+
+// keep_intermediates: which layer GEMMs the most recent call launched (engine.h: gemm_rec_)
+thread_local uint64_t tls_gemm_rec_gen = 0;
+void GemmRecordJoin(uint64_t gen) { tls_gemm_rec_gen = gen; }
+uint64_t GemmRecordJoined() { return tls_gemm_rec_gen; }
+uint64_t Model::GemmRecordBegin() const {
+  if (!opts_.keep_intermediates) return 0;
+  std::lock_guard<std::mutex> lk(gemm_rec_mu_);
+  gemm_rec_.clear();
+  return ++gemm_rec_gen_;
+}
+void Model::LaunchGemmRecorded(const std::string &name, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw) const {
+  if (!opts_.keep_intermediates || rows <= 0) return LaunchGemm(d, rows, row_ivec, s, sw);
+  GemmLaunch p;
+  LaunchGemm(d, rows, row_ivec, s, sw, &p);
+  char line[400];
+  DescribeGemmLaunchLine(name.c_str(), d, rows, p, line, sizeof(line));
+  std::lock_guard<std::mutex> lk(gemm_rec_mu_);
+  if (tls_gemm_rec_gen != gemm_rec_gen_) return;
+  if (std::find(gemm_rec_.begin(), gemm_rec_.end(), line) == gemm_rec_.end()) gemm_rec_.push_back(line);
+}
 bool Model::CheckGemmRange(DecodeContext &cx) {
   if (tls_exact_gemm || !cx.gemm_ovf) return false;
   // (RS_GEMM_B3_NOUNDER=1, -DRS_TUNING builds: the precision flag is ignored -- what the split kernels do to small rows, measured)
@@ -1096,6 +1121,7 @@ std::unique_ptr<Result> Model::DecodeInContext(DecodeContext &cx, const int16_t 
   // two concurrent groups unless the caller pinned a stream, the batch is small, or RS_SUBBATCHES=1
   const int ngroups = (user_stream || n_utts < 32 || max_groups_ < 2) ? 1 : 2;
   cx.active_groups = ngroups;
+  cx.gemm_rec_gen = GemmRecordBegin();
   for (int attempt = 0;; attempt++) {
   cx.gemm_ovf[0] = cx.gemm_ovf[1] = 0;
   cx.force_exact = attempt > 0;
@@ -1246,10 +1272,10 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
         gd.row_map = rm->rows;
         gd.row_map_span128 = rm->span128;
         gd.row_map_span160 = rm->span160;
-        LaunchGemm(gd, rm->count, d_row_ivec, s, &sw);
+        LaunchGemmRecorded(op.name, gd, rm->count, d_row_ivec, s, &sw);
         conv_map = rm->rows; conv_rows = rm->count;
       } else {
-        LaunchGemm(gd, rows, d_row_ivec, s, &sw);
+        LaunchGemmRecorded(op.name, gd, rows, d_row_ivec, s, &sw);
       }
     } else {
       EltwiseDev d;
@@ -1807,9 +1833,9 @@ void Model::BatchIvectors(BatchCall *b) {
   LdsPoison(s);
   LaunchOnlineCmvn(cmvn_iv_dev_, g, b->raw, cm, ld_c, s);
   LdsPoison(s);
-  LaunchGemm(MakeGemm(LdaPlan(b->raw_ld), {b->raw}, {b->raw_ld}, nullptr, 0, lda_raw, ld_l, share), rows, b->d_row_ivec, s);
+  LaunchGemmRecorded(LdaPlan(b->raw_ld).op->name, MakeGemm(LdaPlan(b->raw_ld), {b->raw}, {b->raw_ld}, nullptr, 0, lda_raw, ld_l, share), rows, b->d_row_ivec, s);
   LdsPoison(s);
-  LaunchGemm(MakeGemm(LdaPlan(ld_c), {cm}, {ld_c}, nullptr, 0, lda_norm, ld_l, share), rows, b->d_row_ivec, s);
+  LaunchGemmRecorded(LdaPlan(ld_c).op->name, MakeGemm(LdaPlan(ld_c), {cm}, {ld_c}, nullptr, 0, lda_norm, ld_l, share), rows, b->d_row_ivec, s);
   int *post_idx = arena_.AllocT<int>((size_t)rows * nsel);
   float *post_w = arena_.AllocT<float>((size_t)rows * nsel);
   LdsPoison(s);
@@ -1914,6 +1940,7 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   auto wall0 = std::chrono::steady_clock::now();
   if (n_utts == 0) return;
   SampleGemmMode(exact_gemm_.load() || cx.force_exact, cx.gemm_ovf_dev);
+  GemmRecordJoin(cx.gemm_rec_gen);
   const Nnet &nn = am_.nnet;
   const int fsf = opts_.frame_subsampling_factor;
   BatchCall b;
@@ -1974,7 +2001,7 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
                           (int)nn.ops[i].out_buf);
     for (int k = 0; k < n_slabs; k++) {
       gd.row_map = b.d_frame_rows + b.lists.slab_off[k];
-      LaunchGemm(gd, b.lists.slab_off[k + 1] - b.lists.slab_off[k], b.d_row_ivec, s);
+      LaunchGemmRecorded(nn.ops[i].name, gd, b.lists.slab_off[k + 1] - b.lists.slab_off[k], b.d_row_ivec, s);
       RS_HIP(hipEventRecord(cx.slab_ev[k], s));
       RS_HIP(hipStreamWaitEvent(cx.stream_dec, cx.slab_ev[k], 0));
       const int f_end = k + 1 == n_slabs ? b.maxT + 1 : (k + 1) * slab_len;

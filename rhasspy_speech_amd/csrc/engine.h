@@ -105,6 +105,8 @@ struct StreamPool;                                                 // stream.cc
 struct AdvanceSet;
 struct BatchCall;                                                  // engine.cc
 struct StagesBC;
+void GemmRecordJoin(uint64_t gen);                               // engine.cc: the generation of recorded launches this thread enqueues for
+uint64_t GemmRecordJoined();
 void SampleGemmMode(bool exact, int *ovf_dev);                   // engine.cc: which layer GEMMs this thread's launches use, and whose range flag they raise
 struct StreamPoolDeleter { void operator()(StreamPool *p) const; };
 
@@ -219,6 +221,16 @@ class Model {
                const RowMaps &row_maps, int share, size_t op_begin, size_t op_end, hipStream_t s,
                const std::vector<ActImage> *imgs = nullptr) const;
 
+  // keep_intermediates only: the layer GEMMs the most recent decode call or stream advance launched, one line per distinct launch
+  // (Describe: "gemm_launch:").  A call opens a generation (GemmRecordBegin) and every thread that enqueues for it carries the
+  // number (GemmRecordJoin, thread-local like the GEMM mode): what the pool's issuing thread still launches for an older advance
+  // is dropped.  With the option at 0 LaunchGemmRecorded is LaunchGemm and the list stays empty.
+  uint64_t GemmRecordBegin() const;
+  void LaunchGemmRecorded(const std::string &name, const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw = nullptr) const;
+  mutable std::mutex gemm_rec_mu_;
+  mutable uint64_t gemm_rec_gen_ = 0;
+  mutable std::vector<std::string> gemm_rec_;
+
   rs_decode_opts opts_;
   FeatureConfig fc_;
   AcousticModel am_;
@@ -249,6 +261,7 @@ class Model {
     size_t h_pcm_cap = 0;
     int16_t *d_pcm = nullptr;
     int active_groups = 1;
+    uint64_t gemm_rec_gen = 0;             // the call's generation of recorded layer GEMM launches (its group threads join it)
     bool force_exact = false;              // this call is the repetition of one that left the split-fp16 kernels' range
     bool busy = false;
   };

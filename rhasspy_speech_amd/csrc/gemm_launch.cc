@@ -289,6 +289,7 @@ GemmSwitches ReadGemmSwitches() {
   s.b3j_narrow = !IsZero(Env("RS_GEMM_B3J_NARROW"));
   s.b3j_small = !IsZero(Env("RS_GEMM_B3J_SMALL"));
   s.b3_narrow = !IsZero(Env("RS_GEMM_B3_NARROW"));
+  s.cus = std::max(IntOr(Env("RS_GEMM_CUS"), 0), 0);
   s.b3j_strip = !IsZero(TuneEnv("RS_GEMM_B3J_STRIP"));
   return s;
 }
@@ -324,6 +325,12 @@ const char *DescribeGemmLaunch(const GemmLaunch &p, char *buf, size_t size) {
   }
   if (at >= 0 && (size_t)at < size)
     std::snprintf(buf + at, size - at, " blocks=%d threads=%d nbig=%d nfirst=%d res=%d", p.blocks, p.threads, p.nbig, p.nfirst, (int)p.residual_pass);
+  return buf;
+}
+
+const char *DescribeGemmLaunchLine(const char *name, const GemmDev &d, int rows, const GemmLaunch &p, char *buf, size_t size) {
+  char launch[200];
+  std::snprintf(buf, size, "%s rows=%d n=%d ksteps=%d %s img=%d", name, rows, d.n, KSteps(d), DescribeGemmLaunch(p, launch, sizeof(launch)), (int)p.writes_image);
   return buf;
 }
 

@@ -50,6 +50,7 @@ struct GemmSwitches {
   bool b3j_narrow = true;  // RS_GEMM_B3J_NARROW=0: layers of at most 128 columns stay on the 256-column shapes
   bool b3j_small = true;   // RS_GEMM_B3J_SMALL=0: launches of 32-row tiles stay on GemmKernelB3I
   bool b3_narrow = true;   // RS_GEMM_B3_NARROW=0: one-tile layers of 96 columns and more obey the padding rule too
+  int cus = 0;             // RS_GEMM_CUS: plan as if the device had this many compute units (0: ask the device); grid shapes only
   // measurement switches (TuneEnv: unset unless the build has -DRS_TUNING).  b3j_strip is read on every ReadGemmSwitches(), the
   // others once per process
   bool b3j_strip = true;   // RS_GEMM_B3J_STRIP=0
@@ -72,6 +73,14 @@ GemmLaunch PlanGemmLaunch(const GemmDev &d, int rows, int num_cu, const GemmSwit
 // "B3J<1,1,1,2,4,4> blocks=776 threads=256 nbig=512 nfirst=256 res=0": the kernel's template arguments in their order, then the grid
 // (error messages, the CPU check's fixture).  Returns buf.
 const char *DescribeGemmLaunch(const GemmLaunch &p, char *buf, size_t size);
+
+// The compute units LaunchGemm plans with: RS_GEMM_CUS where it is set, else the device's.
+inline int GemmPlanCus(const GemmSwitches &sw, int device_cus) { return sw.cus > 0 ? sw.cus : device_cus; }
+
+// "<name> rows=81920 n=250 ksteps=48 B3J<1,1,1,2,4,4> blocks=776 ... res=0 img=1": what rs_model_describe prints behind "gemm_launch: "
+// for a launch it recorded, and what tests/host/gemm_launch_check.cc prints for a descriptor file.  ksteps: the 16-wide k-steps of the
+// split-fp16 kernels' k loop, every segment rounded up on its own; the launch is DescribeGemmLaunch's text; img: p.writes_image.  Returns buf.
+const char *DescribeGemmLaunchLine(const char *name, const GemmDev &d, int rows, const GemmLaunch &p, char *buf, size_t size);
 
 // The split-fp16 kernels work on 256-column tiles: a layer takes them only while the padding stays below a share of the
 // padded width (45 %; above it the exact-FP32 kernel with its 128-column tiles wins), or is one tile of at least 96 columns.

@@ -153,8 +153,8 @@ void LaunchToImage(const float *src, int ld, int dim, int rows, const ActImage &
 constexpr int kActImageParts = 2;
 size_t ActImagePartBytes(int rows, int guard, int dim);      // bytes of one part for a buffer of `rows` rows
 // Plans the launch (PlanGemmLaunch, gemm_launch.h), runs the kernel it names and, where the plan asks for it, the residual pass.
-// sw: the switches to plan with (null: read from the environment now)
-void LaunchGemm(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw = nullptr);
+// sw: the switches to plan with (null: read from the environment now); planned: where given, receives the plan that was launched
+void LaunchGemm(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw = nullptr, GemmLaunch *planned = nullptr);
 int DeviceNumCu();      // compute units of the current device, asked once per process (what the launch planners are given)
 
 struct SumTermDev { const float *src; int ld, col0, row_off; float scale; };

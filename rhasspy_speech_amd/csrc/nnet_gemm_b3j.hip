@@ -522,10 +522,15 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 4 ? 2 : 1) void GemmKernel
           if (rok[I] && (col >> 4) < d.out_img.nks) {                                                            \
             f32x4 lo = q[2 * ksi], hi = q[2 * ksi + 1];                                                          \
             if (res_on) {                                                                                        \
+              /* product and sum rounded one after the other (GemmDev::res), like the residual pass and the elementwise kernel: */ \
+              /* __fmul_rn / __fadd_rn are plain * and + to this compiler, which fused the unconditional pair here into one FMA */ \
+              _Pragma("clang fp contract(off)")                                                                  \
               const f16x8 r1 = R[ksi][0], r2 = R[ksi][1];                                                        \
               _Pragma("unroll") for (int e = 0; e < 4; e++) {                                                  \
-                lo[e] = __fadd_rn(__fmul_rn((float)r1[e] + (float)r2[e], d.res_scale), lo[e]);                   \
-                hi[e] = __fadd_rn(__fmul_rn((float)r1[4 + e] + (float)r2[4 + e], d.res_scale), hi[e]);           \
+                const float pl = ((float)r1[e] + (float)r2[e]) * d.res_scale;                                    \
+                const float ph = ((float)r1[4 + e] + (float)r2[4 + e]) * d.res_scale;                            \
+                lo[e] = pl + lo[e];                                                                              \
+                hi[e] = ph + hi[e];                                                                              \
               }                                                                                                  \
             }                                                                                                    \
             _Pragma("unroll") for (int e = 0; e < 4; e++) { if (col + e >= d.n) lo[e] = 0.f; if (col + 4 + e >= d.n) hi[e] = 0.f; } \

@@ -411,9 +411,11 @@ static void DispatchGemm(const GemmLaunch &p, const GemmDev &d, int rows, const 
   }
 }
 
-void LaunchGemm(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw) {
+void LaunchGemm(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw, GemmLaunch *planned) {
   if (rows <= 0) return;
-  const GemmLaunch p = PlanGemmLaunch(d, rows, DeviceNumCu(), sw ? *sw : ReadGemmSwitches());
+  const GemmSwitches switches = sw ? *sw : ReadGemmSwitches();
+  const GemmLaunch p = PlanGemmLaunch(d, rows, GemmPlanCus(switches, DeviceNumCu()), switches);
+  if (planned) *planned = p;
   if (!p.residual_pass) return DispatchGemm(p, d, rows, row_ivec, s);
   DispatchGemm(p, GemmWithoutResidual(d), rows, row_ivec, s);      // (the kernel's epilogue does not add a folded residual)
   LaunchResidualAdd(d, rows, s);

@@ -602,6 +602,7 @@ struct StagesBC {
   int par = 0;
   bool final = false, timed = false, reg_windows = false, exact = false;
   int *ovf_dev = nullptr;
+  uint64_t gemm_rec_gen = 0;      // (keep_intermediates: the advance's generation of recorded layer GEMM launches)
   int nI = 0, nN = 0, rowsN = 0, framesN = 0, maxTn = 1, n = 0, n_sub = 0;
   bool have_sub = false;
   const int *d_nsrc = nullptr, *d_nfb = nullptr, *d_nrb = nullptr, *d_nriv = nullptr, *d_nll = nullptr, *d_nlls = nullptr, *d_slots = nullptr;
@@ -770,8 +771,8 @@ void Model::AdvanceIvectors(StreamPool *p, const AdvancePlan &plan, const Advanc
   int *ru = arena.AllocT<int>(rowsI + 8), *rt = arena.AllocT<int>(rowsI + 8);
   LaunchRowGeometry(nI, rowsI, sl, D(o.irb), nullptr, ru, rt, nullptr, qa);
   g.d_row_utt = ru; g.d_row_t = rt;
-  LaunchGemm(MakeGemm(LdaPlan(ld_c), {seg_raw}, {ld_c}, nullptr, 0, lda_raw, ld_l, 1), rowsI, ru, qa);
-  LaunchGemm(MakeGemm(LdaPlan(ld_c), {seg_cm}, {ld_c}, nullptr, 0, lda_norm, ld_l, 1), rowsI, ru, qa);
+  LaunchGemmRecorded(LdaPlan(ld_c).op->name, MakeGemm(LdaPlan(ld_c), {seg_raw}, {ld_c}, nullptr, 0, lda_raw, ld_l, 1), rowsI, ru, qa);
+  LaunchGemmRecorded(LdaPlan(ld_c).op->name, MakeGemm(LdaPlan(ld_c), {seg_cm}, {ld_c}, nullptr, 0, lda_norm, ld_l, 1), rowsI, ru, qa);
   int *post_idx = arena.AllocT<int>((size_t)rowsI * nsel + 64);
   float *post_w = arena.AllocT<float>((size_t)rowsI * nsel + 64);
   LaunchUbmPosteriors(ivec_dev_, g, lda_norm, ld_l, post_idx, post_w, qa);
@@ -822,6 +823,7 @@ void Model::AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const Advanc
   job.p = p; job.arena = &arena; job.par = set.par;
   job.final = final; job.timed = set.timed; job.reg_windows = sp->call.windows; job.exact = exact_gemm_.load();
   job.ovf_dev = static_cast<DecodeContext *>(p->cx)->gemm_ovf_dev;
+  job.gemm_rec_gen = GemmRecordJoined();
   job.nI = plan.nI; job.nN = plan.nN; job.rowsN = plan.rowsN; job.framesN = plan.framesN; job.maxTn = std::max(plan.maxTn, 1); job.n = plan.n;
   job.n_sub = (int)plan.n_lldst.size(); job.have_sub = !plan.n_llsrc.empty();
   job.d_nsrc = D(o.nsrc); job.d_nfb = D(o.nfb); job.d_nrb = D(o.nrb); job.d_nriv = D(o.nriv); job.d_nll = D(o.nll); job.d_nlls = D(o.nlls); job.d_slots = D(o.slots);
@@ -852,6 +854,7 @@ void Model::IssueStagesBC(const StagesBC &j) {
   hipStream_t q = p->q, qc = p->qc;
   Timer *tb = p->tm_b[par].get(), *tc = p->tm_c[par].get();
   SampleGemmMode(j.exact, j.ovf_dev);      // (thread-local: the issuing thread's launches run in the mode this advance was planned in)
+  GemmRecordJoin(j.gemm_rec_gen);
   RS_HIP(hipStreamWaitEvent(q, p->ev_a[par], 0));
   if (j.nI > 0) RS_HIP(hipStreamWaitEvent(q, p->ev_i[par], 0));
   MarkIf(j.timed, tb);
@@ -985,6 +988,7 @@ void Model::StreamsAdvanceLocked(rs_stream *const *streams, int n, bool final, i
   set.arena = &cx.arena[set.par];
   set.harena = &cx.host_arena[set.par];
   SampleGemmMode(exact_gemm_.load(), cx.gemm_ovf_dev);
+  GemmRecordJoin(GemmRecordBegin());
   HostClock clock;
   const auto wall0 = clock.last;
   AdvancePlan &plan = p->plans[set.par];

@@ -4,6 +4,9 @@
 // set in the environment, so ReadGemmSwitches is part of what is checked; the device has 256 CUs.  One line per case:
 //     <layer> <rows> s<share> x<exclusive> <switches without their RS_GEMM_ prefix, or -> | <DescribeGemmLaunch> img=<GemmWritesImage>
 // compared by the test with tests/host/gemm_launch_expected.txt.
+// With an argument (tests/test_gemm_shapes_cpu.py): the name of a text file of descriptors, one per line, as tests/gemm_shape_cases.py
+// writes them (ReadDescriptor below).  For each the program plans the launch with the line's CU count and switches, runs the same
+// coverage check and prints "gemm_launch: " and DescribeGemmLaunchLine -- the line rs_model_describe prints for a launch it recorded.
 // For every case the program also restates how the kernels decode blockIdx (XCD-interleaved row tiles; the first-small, full and
 // remaining-small ranges of a mixed launch; the alternating order of a negative nfirst) and aborts unless every (row, column tile)
 // of [0, rows) x [0, ncol) belongs to exactly one block of the planned grid.
@@ -117,7 +120,7 @@ static std::vector<Layer> Layers() {
 }
 
 // ---------------------------------------------------------------------------------------------- switches
-static const char *const kSwitchNames[] = {"B3", "B3I", "B3J", "B3J_WM", "B3J_SLOTS", "B3J_MR", "B3J_NARROW", "B3J_SMALL", "B3J_STRIP", "B3_NARROW"};
+static const char *const kSwitchNames[] = {"B3", "B3I", "B3J", "B3J_WM", "B3J_SLOTS", "B3J_MR", "B3J_NARROW", "B3J_SMALL", "B3J_STRIP", "B3_NARROW", "CUS"};
 static void SetSwitches(const std::string &spec) {      // "B3J=2,B3J_WM=1" or "-"
   for (const char *n : kSwitchNames) unsetenv((std::string("RS_GEMM_") + n).c_str());
   if (spec == "-") return;
@@ -202,7 +205,77 @@ static void Case(const Layer &l, int rows, int share, int exclusive, const char 
   std::printf("%s | %s img=%d\n", what, dec, (int)img);
 }
 
-int main() {
+#ifndef GEMM_LAUNCH_RECORD
+// One descriptor: "key=value" tokens in any order, then "name=" and the op's name up to the end of the line (it may hold blanks).
+//   rows cu switches(as SetSwitches takes them)  n w3 w3i interleave share exclusive write_f32 out_img res(0 none, 1 floats, 2 operand image)
+//   map(0 | 1) span128 span160  segs=<img 0|1>:<ld>:<col0>:<ncols>:<row_off>:<per_utt>:<source misaligned 0|1>;...
+static long Field(const std::string &line, const char *key, long unset) {
+  const std::string k = std::string(" ") + key + "=";
+  const size_t at = (" " + line).find(k);
+  return at == std::string::npos ? unset : std::atol(line.c_str() + at + k.size() - 1);
+}
+static std::string Text(const std::string &line, const char *key, bool to_end) {
+  const std::string k = std::string(" ") + key + "=", l = " " + line;
+  const size_t at = l.find(k);
+  CHECK(at != std::string::npos, "descriptor without %s: %s", key, line.c_str());
+  const size_t from = at + k.size(), end = to_end ? std::string::npos : l.find(' ', from);
+  return l.substr(from, end == std::string::npos ? std::string::npos : end - from);
+}
+static void DescriptorCase(const std::string &line) {
+  const int n = (int)Field(line, "n", 0), rows = (int)Field(line, "rows", 0), cu = (int)Field(line, "cu", 256);
+  CHECK(n > 0 && rows > 0 && cu > 0, "descriptor: %s", line.c_str());
+  GemmDev d = Base(n, Field(line, "w3", 0) != 0, Field(line, "w3i", 0) != 0);
+  const std::string segs = Text(line, "segs", false);
+  for (size_t at = 0; at < segs.size();) {
+    const size_t end = std::min(segs.find(';', at), segs.size());
+    long v[7] = {0, 0, 0, 0, 0, 0, 0};
+    CHECK(std::sscanf(segs.substr(at, end - at).c_str(), "%ld:%ld:%ld:%ld:%ld:%ld:%ld", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6]) == 7, "segment in %s", line.c_str());
+    CHECK(d.nsegs < (int)(sizeof(d.segs) / sizeof(d.segs[0])), "too many segments: %s", line.c_str());
+    Seg(&d, v[0] ? &kImgA : nullptr, (int)v[1], (int)v[2], (int)v[3], (int)v[4], (int)v[5], v[6] ? 0x20000004 : 0x20000000);
+    at = end + 1;
+  }
+  CHECK(d.nsegs > 0, "no segment: %s", line.c_str());
+  d.interleave = (int)Field(line, "interleave", 0);
+  d.share = (int)Field(line, "share", 1);
+  d.exclusive = (int)Field(line, "exclusive", 0);
+  d.write_f32 = (int)Field(line, "write_f32", 1);
+  if (Field(line, "out_img", 0)) d.out_img = kImgB;
+  const long res = Field(line, "res", 0);
+  if (res) { d.res = Fake<const float>(0x70000000); d.res_ld = 256; d.res_scale = 0.66f; }
+  if (res == 2) d.res_img = kImgA;
+  if (Field(line, "map", 0)) {
+    d.row_map = Fake<const int>(0x78000000);
+    d.row_map_span128 = (int)Field(line, "span128", 0); d.row_map_span160 = (int)Field(line, "span160", 0);
+  }
+  SetSwitches(Text(line, "switches", false));
+  const GemmSwitches sw = ReadGemmSwitches();
+  const std::string name = Text(line, "name", true);
+  const GemmLaunch p = PlanGemmLaunch(d, rows, GemmPlanCus(sw, cu), sw);
+  CHECK(GemmWritesImage(d, sw) == p.writes_image, "%s: GemmWritesImage and the plan disagree", line.c_str());
+  CHECK(!p.residual_pass || d.res, "%s: a residual pass without a residual", line.c_str());
+  CheckCoverage(p, d, rows, line.c_str());
+  char out[400];
+  std::printf("gemm_launch: %s\n", DescribeGemmLaunchLine(name.c_str(), d, rows, p, out, sizeof(out)));
+}
+#endif
+
+int main(int argc, char **argv) {
+#ifndef GEMM_LAUNCH_RECORD
+  if (argc > 1) {
+    FILE *f = std::fopen(argv[1], "r");
+    CHECK(f != nullptr, "cannot read %s", argv[1]);
+    char buf[2048];
+    while (std::fgets(buf, sizeof(buf), f)) {
+      std::string line(buf);
+      while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+      if (!line.empty() && line[0] != '#') DescriptorCase(line);
+    }
+    std::fclose(f);
+    return 0;
+  }
+#else
+  (void)argc; (void)argv;
+#endif
   const std::vector<Layer> layers = Layers();
   const int all_rows[] = {1, 31, 32, 33, 127, 128, 129, 159, 160, 161, 1024, 4096, 4097, 8192, 8193, 8194, 16384, 16385, 16386, 81920, 81921, 83968};
   const int some_rows[] = {33, 4096, 8192, 8193, 81920, 81921};
