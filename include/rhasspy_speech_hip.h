@@ -97,7 +97,10 @@ const char *rs_last_error(void);
 
 /* Replaces the per-process model loading of both binaries
  * (online2-wav-nnet3-latgen-faster.cc:150-190: OnlineNnet2FeaturePipelineInfo from --config=online.conf,
- * TransitionModel + AmNnetSimple from final.mdl, ReadFstKaldiGeneric(HCLG.fst)).  Parses on the host only;
+ * TransitionModel + AmNnetSimple from final.mdl, ReadFstKaldiGeneric(HCLG.fst)).  The base feature is online.conf's
+ * --feature-type: mfcc (--mfcc-config) or fbank (--fbank-config: log-mel filterbank rows, up to 128 columns); only the selected
+ * type's file counts and none means the type's defaults (online-nnet2-feature-pipeline.cc:28-56).  plp, pitch and VTLN warping are
+ * refused with a message.  Parses on the host only;
  * the device copy is made on first use or by rs_model_to_device().  Immutable afterwards, shareable
  * between threads. */
 int rs_model_load_files(const char *final_mdl, const char *hclg_fst, const char *online_conf,
@@ -108,7 +111,9 @@ int rs_model_load(const char *model_dir, const char *graph_dir, const rs_decode_
 int rs_model_to_device(rs_model *model);
 void rs_model_free(rs_model *model);
 /* Writes a one-line-per-item description of the parsed model (dims, layer plan, graph size) into buf;
- * returns the number of bytes needed (like snprintf).  Two lines are state, not structure: `layer_gemm:` and
+ * returns the number of bytes needed (like snprintf).  The first line is the base feature's: `mfcc: win= shift= padded= mel_bins=
+ * ceps= dither=`, or for a filterbank model `fbank: win= shift= padded= mel_bins= dim= use_energy= htk_compat= use_log= use_power=
+ * dither=` (dim = mel_bins + use_energy, the width of a feature row).  Two lines are state, not structure: `layer_gemm:` and
  *   arenas: device blocks=B bytes=N allocations=A; host blocks=B bytes=N allocations=A
  * summed over the model's decode contexts: the blocks and bytes their per-call arenas hold now, and the hipMalloc / hipHostMalloc
  * calls they have made since the model was loaded.  `allocations` stands still once every context has seen its largest call twice.
@@ -133,7 +138,7 @@ int rs_model_describe(const rs_model *model, char *buf, size_t len);
  * 86-101; online2-wav-nnet3-latgen-faster.cc:233 hands it WaveData::SampFreq()): RS_OK when `sample_rate` is the model's
  * --sample-frequency, else an error whose text is Kaldi's "Sampling frequency mismatch, expected 16000, got 8000 ...".  The PCM entry
  * points below take samples, not files: a caller that read a wav header calls this first (rhasspy_speech_amd.transcribe_wav and the
- * online2-wav-nnet3-latgen-faster shim do).  --allow-downsample / --allow-upsample in mfcc.conf (the reference then resamples) are
+ * online2-wav-nnet3-latgen-faster shim do).  --allow-downsample / --allow-upsample in mfcc.conf / fbank.conf (the reference then resamples) are
  * refused with a message: the library does not resample. */
 int rs_model_check_sample_rate(const rs_model *model, float sample_rate);
 
@@ -243,7 +248,7 @@ typedef struct rs_endpoint_status {
  *   trailing_silence_frames = from the best frontier token WITHOUT final costs (rs_streams_partial's token, ties to the lowest state)
  *                             backwards: input-epsilon arcs are skipped, an emitting arc whose transition-id belongs to a phone of the
  *                             silence list counts one, the first other emitting arc ends the walk (online-endpoint.cc:89-106);
- *   frame_shift_seconds     = mfcc.conf's --frame-shift in seconds x --frame-subsampling-factor (online-nnet3-decoding.cc:88-95);
+ *   frame_shift_seconds     = mfcc.conf's (fbank.conf's) --frame-shift in seconds x --frame-subsampling-factor (online-nnet3-decoding.cc:88-95);
  *   detected                = rs_endpoint_rule_fired of these.
  * opts = NULL: the model's (rs_model_endpoint_opts).  An empty silence list fails with RS_ERR_ARG "Endpointing requires nonempty
  * --endpoint.silence-phones option", one that does not parse or holds a phone twice with "Bad --silence-phones option in endpointing
@@ -459,12 +464,12 @@ int rs_fst_tool(const char *tool, const char *in1, const char *in2, const char *
  * Both binaries (kaldi/src/online2bin/online2-wav-nnet3-latgen-faster.cc:160-176, online2-cli-nnet3-decode-faster.cc:97-111)
  * run CollapseModel on the network they read and, while computing the network's context and compiling its looped computation,
  * call glibc's rand() a model-dependent number of times -- which decides the noise Dither() adds to every frame afterwards
- * (kaldi/src/feat/feature-window.cc:90-98; the default mfcc configuration has --dither=1 and rhasspy starts one process per
+ * (kaldi/src/feat/feature-window.cc:90-98; the default mfcc and fbank configurations have --dither=1 and rhasspy starts one process per
  * utterance, so the noise of frame t is a constant of the model).  rs_model_load replays both; these two entry points expose
  * the replay for inspection and tests:
  *   rs_nnet3_setup: *rand_calls = number of rand() calls before the first frame for `final_mdl` under --frames-per-chunk;
  *     *certain = 0 when the count assumes a looped compilation the reference may have to retry (rs_model_load refuses such a
- *     model unless its mfcc.conf says --dither=0); collapsed_config (may be NULL) receives the config lines of the collapsed
+ *     model unless its mfcc.conf / fbank.conf says --dither=0); collapsed_config (may be NULL) receives the config lines of the collapsed
  *     network, '\n'-separated and NUL-terminated, truncated to buf_len.
  *   rs_dither_noise: out[(t - t0) * window + i] = the value Dither() adds, for --dither=1, to sample i of frame t in a process
  *     that called rand() `rand_calls` times before its first frame. */

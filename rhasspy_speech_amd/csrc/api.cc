@@ -148,7 +148,8 @@ int rs_model_check_sample_rate(const rs_model *model, float sample_rate) {
     if (sample_rate == o.samp_freq) return RS_OK;
     std::ostringstream e;
     if ((sample_rate > o.samp_freq && o.allow_downsample) || (sample_rate < o.samp_freq && o.allow_upsample)) {
-      e << "Sampling frequency mismatch, expected " << o.samp_freq << ", got " << sample_rate << ": the model's mfcc.conf sets --allow-"
+      e << "Sampling frequency mismatch, expected " << o.samp_freq << ", got " << sample_rate << ": the model's "
+        << (model->m->features().mfcc.fbank ? "fbank.conf" : "mfcc.conf") << " sets --allow-"
         << (sample_rate > o.samp_freq ? "downsample" : "upsample") << ", with which the reference resamples the waveform (LinearResample); "
         << "this library does not resample: convert the audio to " << o.samp_freq << " Hz first";
     } else {

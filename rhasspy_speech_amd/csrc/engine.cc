@@ -203,9 +203,10 @@ Model::Model(const std::string &final_mdl, const std::string &hclg, const std::s
   dither_rand_calls_ = am_.nnet.setup_rand_calls;
   if (const char *e = std::getenv("RS_DITHER_RAND_CALLS")) dither_rand_calls_ = std::atol(e);
   else if (fc_.mfcc.opts.dither != 0.0f && !am_.nnet.setup_rand_certain)
-    Fail("mfcc.conf has --dither=" + std::to_string(fc_.mfcc.opts.dither) + " and the reference seeds that noise from rand() after a model "
+    Fail(std::string(fc_.mfcc.fbank ? "fbank.conf" : "mfcc.conf") + " has --dither=" + std::to_string(fc_.mfcc.opts.dither) + " and the reference seeds that noise from rand() after a model "
          "set-up whose number of rand() calls cannot be derived for this network (" + am_.nnet.setup_rand_uncertain_why +
-         ": its looped compilation may need a second attempt, nnet-compile-looped.cc:326-345); set --dither=0 in the mfcc config, or "
+         ": its looped compilation may need a second attempt, nnet-compile-looped.cc:326-345); set --dither=0 in the " +
+         (fc_.mfcc.fbank ? "fbank" : "mfcc") + " config, or "
          "RS_DITHER_RAND_CALLS=<n> to the count `rs-dump randpos` reports for the reference");
   const Nnet &n = am_.nnet;
   if (n.input_dim != fc_.mfcc.nceps)
@@ -337,6 +338,12 @@ Model::~Model() {
     if (c->gemm_ovf) (void)hipHostFree(c->gemm_ovf);
   }
   if (stream_ctx_ && stream_ctx_->gemm_ovf) (void)hipHostFree(stream_ctx_->gemm_ovf);
+}
+
+void Model::LaunchBaseFeatures(int dither_frames, const BatchGeom &g, const int16_t *pcm, float *feats, int ld, hipStream_t s, bool exclusive,
+                               const int *out_rows) {
+  if (fc_.mfcc.fbank) LaunchFbank(MfccWithDither(dither_frames), fbank_dev_, g, pcm, feats, ld, s, exclusive, out_rows);
+  else LaunchMfcc(MfccWithDither(dither_frames), g, pcm, feats, ld, s, exclusive, out_rows);
 }
 
 MfccDev Model::MfccWithDither(int frames) {
@@ -565,6 +572,7 @@ void Model::ToDevice() {
   mfcc_dev_.win = t.win; mfcc_dev_.shift = t.shift; mfcc_dev_.padded = t.padded; mfcc_dev_.nbins = t.nbins; mfcc_dev_.nceps = t.nceps;
   mfcc_dev_.preemph = t.opts.preemph; mfcc_dev_.remove_dc = t.opts.remove_dc; mfcc_dev_.use_energy = t.opts.use_energy;
   mfcc_dev_.raw_energy = t.opts.raw_energy; mfcc_dev_.log_energy_floor = t.log_energy_floor;
+  fbank_dev_.use_log = t.use_log_fbank; fbank_dev_.use_power = t.use_power; fbank_dev_.energy_col = t.energy_col; fbank_dev_.mel_col0 = t.mel_col0;
   mfcc_dev_.window = Upload(t.window);
   mfcc_dev_.mel_offset = Upload(t.mel_offset); mfcc_dev_.mel_len = Upload(t.mel_len); mfcc_dev_.mel_start = Upload(t.mel_start);
   {
@@ -635,7 +643,7 @@ void Model::ToDevice() {
       mfcc_dev_.fft_post = static_cast<const float4 *>(UploadBytes(post.data(), post.size() * sizeof(float)));
     }
   }
-  if (t.nceps > 128) Fail("more than 128 cepstral coefficients are not supported");
+  if (t.nceps > 128) Fail("more than 128 feature columns are not supported");
   // ---- CMVN on the nnet input branch
   if (fc_.use_cmvn) {
     cmvn_nnet_dev_.dim = t.nceps; cmvn_nnet_dev_.cmn_window = fc_.cmvn.cmn_window;
@@ -849,8 +857,13 @@ void Model::ToDevice() {
 std::string Model::Describe() const {
   std::ostringstream os;
   const MfccTables &t = fc_.mfcc;
-  os << "mfcc: win=" << t.win << " shift=" << t.shift << " padded=" << t.padded << " mel_bins=" << t.nbins << " ceps=" << t.nceps
-     << " dither=" << t.opts.dither << "\n";
+  if (t.fbank)
+    os << "fbank: win=" << t.win << " shift=" << t.shift << " padded=" << t.padded << " mel_bins=" << t.nbins << " dim=" << t.nceps
+       << " use_energy=" << (t.opts.use_energy ? 1 : 0) << " htk_compat=" << (t.opts.htk_compat ? 1 : 0) << " use_log=" << (t.use_log_fbank ? 1 : 0)
+       << " use_power=" << (t.use_power ? 1 : 0) << " dither=" << t.opts.dither << "\n";
+  else
+    os << "mfcc: win=" << t.win << " shift=" << t.shift << " padded=" << t.padded << " mel_bins=" << t.nbins << " ceps=" << t.nceps
+       << " dither=" << t.opts.dither << "\n";
   os << "nnet_input_cmvn: " << (fc_.use_cmvn ? 1 : 0) << "\n";
   if (fc_.ie.present)
     os << "ivector: dim=" << fc_.ie.ivector_dim() << " gauss=" << fc_.ie.num_gauss() << " lda_dim=" << fc_.ie.feat_dim()
@@ -1811,12 +1824,12 @@ void Model::BatchFeatures(const int16_t *d_pcm, BatchCall *b) {
   if (fc_.use_cmvn) {
     b->raw = b->Rows(ld_c);
     LdsPoison(s);
-    LaunchMfcc(MfccWithDither(b->maxT), b->g, d_pcm, b->raw, ld_c, s, OthersInFlight());
+    LaunchBaseFeatures(b->maxT, b->g, d_pcm, b->raw, ld_c, s, OthersInFlight());
     LdsPoison(s);
     LaunchOnlineCmvn(cmvn_nnet_dev_, b->g, b->raw, b->bufp[nn.input_buf], in_ld, s);
   } else {
     LdsPoison(s);
-    LaunchMfcc(MfccWithDither(b->maxT), b->g, d_pcm, b->raw, in_ld, s, OthersInFlight());
+    LaunchBaseFeatures(b->maxT, b->g, d_pcm, b->raw, in_ld, s, OthersInFlight());
   }
   b->raw_ld = fc_.use_cmvn ? ld_c : in_ld;
 }

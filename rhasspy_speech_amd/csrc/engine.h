@@ -332,6 +332,10 @@ class Model {
   void PruneOutputLayer();
 
   MfccDev mfcc_dev_{};
+  FbankDev fbank_dev_{};           // --feature-type=fbank (fc_.mfcc.fbank): what the filterbank kernel reads beside mfcc_dev_
+  // the model's base-feature kernel (MFCC or log-mel filterbank) over the rows of g; arguments as LaunchMfcc's
+  void LaunchBaseFeatures(int dither_frames, const BatchGeom &g, const int16_t *pcm, float *feats, int ld, hipStream_t s, bool exclusive,
+                          const int *out_rows = nullptr);
   // Dither noise of frames [0, dither_frames_) on the device (nnet3_setup.h: the reference's draws for frame t are a constant of
   // the model).  Grows on demand by doubling; the table a growth step supersedes stays alive until the next step (launches in flight may still read it).
   MfccDev MfccWithDither(int frames);

@@ -70,6 +70,16 @@ struct MfccDev {
 // out_rows (null = the row itself): physical row of `feats` that receives dense row i (streams write into pool rows).
 void LaunchMfcc(const MfccDev &m, const BatchGeom &g, const int16_t *pcm, float *feats, int ld, hipStream_t s, bool exclusive = false,
                 const int *out_rows = nullptr);
+// Log-mel filterbank rows (feat/feature-fbank.cc:72-123) from the same front end: `m` as for LaunchMfcc (frame options, window, mel
+// filters -- up to 128 of them --, FFT plan, dither; dct, lifter and nceps are not read) plus what only this type has.  The row is
+// nbins (+ 1 with the energy) columns wide.  Same launch geometry, halo rows and out_rows as LaunchMfcc.
+struct FbankDev {
+  int use_log, use_power;    // --use-log-fbank, --use-power
+  int energy_col;            // column of the log energy (m.use_energy): 0, or nbins with --htk-compat; -1 without it
+  int mel_col0;              // column of mel bin 0: 1 when the energy is in column 0
+};
+void LaunchFbank(const MfccDev &m, const FbankDev &f, const BatchGeom &g, const int16_t *pcm, float *feats, int ld, hipStream_t s,
+                 bool exclusive = false, const int *out_rows = nullptr);
 // dst row dst_row[i] (null = i) <- src row src_row[i] (null = i), width_words 4-byte words, leading dimensions in words.
 // the same for up to four arrays that share the row lists and whose rows are as wide as their pitch (the per-stream estimator state)
 struct CopyRowsSet {

@@ -68,19 +68,16 @@ int NumFrames(long num_samples, const MfccOptions &o) {
 // mel-computations.h:81-87
 static inline float MelScale(float freq) { return 1127.0f * logf(1.0f + freq / 700.0f); }
 
-void BuildMfccTables(const MfccOptions &o, MfccTables *t) {
+// The window and the mel filters: what both feature types share (`what`: the type's name in the messages)
+static void BuildFrameAndMelTables(const MfccOptions &o, const std::string &what, MfccTables *t) {
   t->opts = o;
-  if (!o.snip_edges) Fail("mfcc: --snip-edges=false is not supported by the HIP feature kernel");
-  if (o.htk_compat) Fail("mfcc: --htk-compat=true is not supported by the HIP feature kernel");
-  if (o.num_ceps > o.num_bins) Fail("num-ceps cannot be larger than num-mel-bins.");
+  if (!o.snip_edges) Fail(what + ": --snip-edges=false is not supported by the HIP feature kernel");
   t->win = o.WindowSize();
   t->shift = o.WindowShift();
   t->padded = o.PaddedWindowSize();
   if (t->padded != 512 && t->padded != 2048)
-    Fail("mfcc: padded window size " + std::to_string(t->padded) + " unsupported by the HIP FFT (need 512 or 2048)");
-  if (o.num_bins > 64 || o.num_ceps > 64) Fail("mfcc: more than 64 mel bins / cepstra are not supported by the HIP kernel");
+    Fail(what + ": padded window size " + std::to_string(t->padded) + " unsupported by the HIP FFT (need 512 or 2048)");
   t->nbins = o.num_bins;
-  t->nceps = o.num_ceps;
   // window (feature-window.cc:113-125): computed in double, stored as float
   t->window.resize(t->win);
   double a = 2.0 * M_PI / (t->win - 1);
@@ -131,6 +128,15 @@ void BuildMfccTables(const MfccOptions &o, MfccTables *t) {
     t->mel_start[bin] = (int)t->mel_weights.size();
     t->mel_weights.insert(t->mel_weights.end(), this_bin.begin() + first, this_bin.begin() + last + 1);
   }
+  t->log_energy_floor = o.energy_floor > 0.0f ? logf(o.energy_floor) : -std::numeric_limits<float>::infinity();
+}
+
+void BuildMfccTables(const MfccOptions &o, MfccTables *t) {
+  if (o.htk_compat) Fail("mfcc: --htk-compat=true is not supported by the HIP feature kernel");
+  if (o.num_ceps > o.num_bins) Fail("num-ceps cannot be larger than num-mel-bins.");
+  if (o.num_bins > 64 || o.num_ceps > 64) Fail("mfcc: more than 64 mel bins / cepstra are not supported by the HIP kernel");
+  BuildFrameAndMelTables(o, "mfcc", t);
+  t->nceps = o.num_ceps;
   // DCT (matrix-functions.cc:592-608): rows k of an N x N type-II DCT, first num_ceps rows kept
   int N = o.num_bins;
   t->dct.assign((size_t)o.num_ceps * N, 0.0f);
@@ -145,7 +151,58 @@ void BuildMfccTables(const MfccOptions &o, MfccTables *t) {
   if (o.cepstral_lifter != 0.0f)
     for (int i = 0; i < o.num_ceps; i++)
       t->lifter[i] = (float)(1.0 + 0.5 * o.cepstral_lifter * sin(M_PI * i / o.cepstral_lifter));
-  t->log_energy_floor = o.energy_floor > 0.0f ? logf(o.energy_floor) : -std::numeric_limits<float>::infinity();
+}
+
+// feature-fbank.h:62-80 on top of the frame and mel options (feature-window.h:77-113, mel-computations.h:60-75).  The warping
+// factor is always 1, so --vtln-low / --vtln-high at their defaults change nothing; other values, and --debug-mel, are refused.
+void ReadFbankOptions(const std::string &conf_path, FbankOptions *o) {
+  for (auto &kv : ReadConfigFile(conf_path)) {
+    const std::string &k = kv.first, &v = kv.second;
+    if (k == "sample-frequency") o->samp_freq = std::stof(v);
+    else if (k == "frame-length") o->frame_length_ms = std::stof(v);
+    else if (k == "frame-shift") o->frame_shift_ms = std::stof(v);
+    else if (k == "preemphasis-coefficient") o->preemph = std::stof(v);
+    else if (k == "remove-dc-offset") o->remove_dc = ParseBool(v, k);
+    else if (k == "dither") o->dither = std::stof(v);
+    else if (k == "window-type") o->window_type = v;
+    else if (k == "blackman-coeff") o->blackman_coeff = std::stof(v);
+    else if (k == "round-to-power-of-two") o->round_pow2 = ParseBool(v, k);
+    else if (k == "snip-edges") o->snip_edges = ParseBool(v, k);
+    else if (k == "allow-downsample") o->allow_downsample = ParseBool(v, k);
+    else if (k == "allow-upsample") o->allow_upsample = ParseBool(v, k);
+    else if (k == "max-feature-vectors") {}
+    else if (k == "num-mel-bins") o->num_bins = std::stoi(v);
+    else if (k == "low-freq") o->low_freq = std::stof(v);
+    else if (k == "high-freq") o->high_freq = std::stof(v);
+    else if (k == "vtln-low" || k == "vtln-high") {
+      const float def = k == "vtln-low" ? o->vtln_low : o->vtln_high;
+      if (std::stof(v) != def) Fail("fbank: --" + k + "=" + v + " is not supported by the HIP feature kernel (no VTLN warping)");
+    }
+    else if (k == "debug-mel") { if (ParseBool(v, k)) Fail("fbank: --debug-mel=true is not supported by the HIP feature kernel"); }
+    else if (k == "use-energy") o->use_energy = ParseBool(v, k);
+    else if (k == "energy-floor") o->energy_floor = std::stof(v);
+    else if (k == "raw-energy") o->raw_energy = ParseBool(v, k);
+    else if (k == "htk-compat") o->htk_compat = ParseBool(v, k);
+    else if (k == "use-log-fbank") o->use_log_fbank = ParseBool(v, k);
+    else if (k == "use-power") o->use_power = ParseBool(v, k);
+    else Fail("Invalid option --" + k + "=" + v + " in config file " + conf_path);
+  }
+}
+
+void BuildFbankTables(const FbankOptions &o, MfccTables *t) {
+  if (o.num_bins < 3) Fail("Must have at least 3 mel bins");      // mel-computations.cc:39-40
+  BuildFrameAndMelTables(o, "fbank", t);      // (too many bins for the FFT's resolution fail here, in the reference's words)
+  if (o.Dim() > 128)
+    Fail("fbank: " + std::to_string(o.Dim()) + " feature columns (--num-mel-bins=" + std::to_string(o.num_bins) +
+         (o.use_energy ? " and the energy" : "") + ") are more than the 128 the HIP path supports");
+  t->fbank = true;
+  t->use_log_fbank = o.use_log_fbank;
+  t->use_power = o.use_power;
+  t->nceps = o.Dim();
+  t->energy_col = !o.use_energy ? -1 : o.htk_compat ? o.num_bins : 0;      // feature-fbank.cc:102,120
+  t->mel_col0 = (o.use_energy && !o.htk_compat) ? 1 : 0;
+  t->dct.assign(1, 0.0f);
+  t->lifter.assign(1, 1.0f);
 }
 
 static void ReadCmvnOptions(const std::string &path, CmvnOptions *c) {
@@ -319,7 +376,7 @@ static void ReadIvectorConfig(const std::string &path, IvectorExtractor *ie, int
 }
 
 void ReadFeatureConfig(const std::string &online_conf, FeatureConfig *fc) {
-  std::string mfcc_conf, ivec_conf, cmvn_conf, gstats;
+  std::string mfcc_conf, fbank_conf, ivec_conf, cmvn_conf, gstats;
   fc->conf_path = online_conf;
   for (auto &kv : ReadConfigFile(online_conf)) {
     const std::string &k = kv.first, &v = kv.second;
@@ -329,7 +386,8 @@ void ReadFeatureConfig(const std::string &online_conf, FeatureConfig *fc) {
     else if (k == "cmvn-config") cmvn_conf = v;
     else if (k == "global-cmvn-stats") gstats = v;
     else if (k == "add-pitch") { if (ParseBool(v, k)) Fail("--add-pitch=true is not supported"); }
-    else if (k == "plp-config" || k == "fbank-config" || k == "online-pitch-config") {}
+    else if (k == "fbank-config") fbank_conf = v;
+    else if (k == "plp-config" || k == "online-pitch-config") {}
     // OnlineEndpointConfig (online-endpoint.h:159-186): kept as written; parsed by the first endpoint call, so that a model that
     // loaded before still loads whatever these lines say (Model::EndpointOpts)
     else if (k.compare(0, 9, "endpoint.") == 0) fc->endpoint_conf.emplace_back(k, v);
@@ -346,22 +404,29 @@ void ReadFeatureConfig(const std::string &online_conf, FeatureConfig *fc) {
       fc->decoder_conf.emplace_back(k, v);
     else Fail("Invalid option --" + k + "=" + v + " in config file " + online_conf);
   }
-  if (fc->feature_type != "mfcc") {
-    if (fc->feature_type == "plp" || fc->feature_type == "fbank")
-      Fail("feature type " + fc->feature_type + " is not supported by the HIP path (mfcc only)");
+  if (fc->feature_type != "mfcc" && fc->feature_type != "fbank") {
+    if (fc->feature_type == "plp") Fail("feature type plp is not supported by the HIP path (supported: mfcc, fbank)");
     Fail("Invalid feature type: " + fc->feature_type + ". Supported feature types: mfcc, plp, fbank.");
   }
+  // online-nnet2-feature-pipeline.cc:36-55: only the selected type's options are used; no config file means its defaults
   MfccOptions mo;
-  if (!mfcc_conf.empty()) ReadMfccOptions(mfcc_conf, &mo);
-  BuildMfccTables(mo, &fc->mfcc);
+  if (!mfcc_conf.empty()) ReadMfccOptions(mfcc_conf, &mo);      // (read, and ignored, beside --feature-type=fbank too)
+  if (fc->feature_type == "fbank") {
+    FbankOptions fo;
+    if (!fbank_conf.empty()) ReadFbankOptions(fbank_conf, &fo);
+    BuildFbankTables(fo, &fc->mfcc);
+  } else {
+    BuildMfccTables(mo, &fc->mfcc);
+  }
+  const int feat_dim = fc->mfcc.nceps;
   fc->use_cmvn = !cmvn_conf.empty();
   if (fc->use_cmvn) {
     ReadCmvnOptions(cmvn_conf, &fc->cmvn);
     if (gstats.empty()) Fail("--global-cmvn-stats option is required  when --cmvn-config is specified.");
     ReadKaldiMatrixFileD(gstats, &fc->global_cmvn);
-    if (fc->global_cmvn.rows != 2 || fc->global_cmvn.cols != mo.num_ceps + 1) Fail("global cmvn stats have the wrong dimension");
+    if (fc->global_cmvn.rows != 2 || fc->global_cmvn.cols != feat_dim + 1) Fail("global cmvn stats have the wrong dimension");
   }
-  if (!ivec_conf.empty()) ReadIvectorConfig(ivec_conf, &fc->ie, mo.num_ceps);
+  if (!ivec_conf.empty()) ReadIvectorConfig(ivec_conf, &fc->ie, feat_dim);
 }
 
 // =============================================================================== transition model

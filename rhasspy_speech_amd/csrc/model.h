@@ -28,12 +28,23 @@ struct MfccOptions {
   int PaddedWindowSize() const;
 };
 
-// Tables the MFCC kernel needs, computed once on the host with the reference's float/double
+// feat/feature-fbank.h:41-81: the frame and mel options of MfccOptions (num_ceps and cepstral_lifter are not options here) with
+// this type's own defaults, and the two switches only it has
+struct FbankOptions : MfccOptions {
+  bool use_log_fbank = true, use_power = true;
+  FbankOptions() { use_energy = false; }
+  int Dim() const { return num_bins + (use_energy ? 1 : 0); }      // feature-fbank.h:93-95
+};
+
+// Tables the base-feature kernel needs, computed once on the host with the reference's float/double
 // expression order (feature-window.cc:113-125, mel-computations.cc:33-142,253-259,
-// matrix-functions.cc:592-608).
+// matrix-functions.cc:592-608).  For a log-mel filterbank model (fbank = true) nceps is the row's width, num-mel-bins (+ 1 with
+// the energy), opts holds the FbankOptions' shared part, and there is no DCT and no lifter.
 struct MfccTables {
   MfccOptions opts;
   int win = 0, shift = 0, padded = 0, nbins = 0, nceps = 0;
+  bool fbank = false, use_log_fbank = true, use_power = true;
+  int energy_col = -1, mel_col0 = 0;      // fbank: the energy's column (-1: none) and the first mel column
   std::vector<float> window;      // win
   std::vector<int> mel_offset;    // nbins: first FFT bin of each filter
   std::vector<int> mel_len;       // nbins
@@ -45,6 +56,8 @@ struct MfccTables {
 };
 void ReadMfccOptions(const std::string &conf_path, MfccOptions *o);
 void BuildMfccTables(const MfccOptions &o, MfccTables *t);
+void ReadFbankOptions(const std::string &conf_path, FbankOptions *o);
+void BuildFbankTables(const FbankOptions &o, MfccTables *t);
 int NumFrames(long num_samples, const MfccOptions &o);  // feature-window.cc:42-87 (snip_edges only)
 
 // feat/online-feature.h:200-260

@@ -734,7 +734,7 @@ void Model::AdvanceStageA(StreamPool *p, const AdvancePlan &plan, const AdvanceS
     int *ru = arena.AllocT<int>(rowsM), *rt = arena.AllocT<int>(rowsM);
     LaunchRowGeometry(nM, rowsM, 0, D(o.mrb), nullptr, ru, rt, nullptr, qa);
     g.d_row_utt = ru; g.d_row_t = rt;
-    LaunchMfcc(MfccWithDither(plan.max_feat_frames), g, set.d_pcm, p->raw, ld_c, qa, false, D(o.mout));
+    LaunchBaseFeatures(plan.max_feat_frames, g, set.d_pcm, p->raw, ld_c, qa, false, D(o.mout));
     BatchGeom gc;
     gc.n_utts = nM; gc.d_num_frames = D(o.cT); gc.d_row_base = D(o.crb);
     const bool spk_iv = plan.any_spk_iv, spk_nn = plan.any_spk_nn;

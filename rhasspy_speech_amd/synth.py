@@ -5,7 +5,7 @@ benchmark and the parity tests run on synthetic models written in exactly the la
 the reference's hot path reads:
 
     <model_dir>/model/model/final.mdl                         TransitionModel + nnet3 (binary or text)
-    <model_dir>/model/online/conf/{online,mfcc,ivector_extractor,splice,online_cmvn}.conf
+    <model_dir>/model/online/conf/{online,mfcc,ivector_extractor,splice,online_cmvn}.conf      (fbank.conf for mfcc.conf: ModelSpec.feature_type)
     <model_dir>/model/online/ivector_extractor/{final.mat,final.ie,final.dubm,global_cmvn.stats}
     <graph_dir>/{HCLG.fst,words.txt}
 
@@ -188,10 +188,32 @@ class ModelSpec:
     # to a fixed ABSOLUTE error only, a different one (tests: small activations and the split-fp16 layer GEMMs)
     gain_compensated: bool = False
     hmm_states: int = 1              # emitting states per phone (left-to-right; > 1 only with chain_topology = False, graphs by mkgraph)
+    # "fbank": log-mel filterbank rows (num_mel_bins bins, + 1 column with use-energy) are the base feature instead of MFCCs;
+    # conf/fbank.conf gets the lines the MFCC config would (bins, band, dither, frame length) with fbank_opts' --key=value on top
+    # (a key given there replaces the line of that name); fbank_config = False writes no --fbank-config line at all: the
+    # reference's defaults (23 bins, dither 1.0), which num_mel_bins then has to match
+    feature_type: str = "mfcc"
+    fbank_opts: Optional[Dict[str, object]] = None
+    fbank_config: bool = True
 
     @property
     def num_pdfs(self) -> int:
         return len(context_tuples(self)) * (2 if self.chain_topology else 1)
+
+    @property
+    def feat_dim(self) -> int:
+        """Width of a base-feature row: what the network's input, the extractor's LDA and global_cmvn.stats are sized from."""
+        if self.feature_type == "mfcc":
+            return self.num_ceps
+        if self.feature_type != "fbank":
+            raise ValueError(f"feature_type {self.feature_type!r}: mfcc or fbank")
+        o = {k: _conf_value(v) for k, v in (self.fbank_opts or {}).items()} if self.fbank_config else {}
+        bins = int(o.get("num-mel-bins", self.num_mel_bins)) if self.fbank_config else 23
+        return bins + (1 if o.get("use-energy", "false") == "true" else 0)
+
+
+def _conf_value(v: object) -> str:
+    return ("true" if v else "false") if isinstance(v, bool) else str(v)
 
 
 TINY = dict(name="tiny", ivector_dim=10, num_gauss=16, lda_dim=12, num_phones=24, hidden_dim=32,
@@ -441,7 +463,7 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
     """Returns (config_lines, [(name, writer_fn)], params dict for the numpy oracle)."""
     cfg: List[str] = []
     comps: List[Tuple[str, object]] = []
-    C, D = spec.num_ceps, spec.ivector_dim
+    C, D = spec.feat_dim, spec.ivector_dim
     cfg.append(f"input-node name=input dim={C}")
     if D > 0:
         cfg.append(f"input-node name=ivector dim={D}")
@@ -576,7 +598,7 @@ def write_final_mdl(path: Path, spec: ModelSpec) -> None:
 def write_ivector_extractor(ie_dir: Path, spec: ModelSpec) -> None:
     rng = np.random.default_rng(spec.seed + 7919)
     ie_dir.mkdir(parents=True, exist_ok=True)
-    C, Dl, G, Di = spec.num_ceps, spec.lda_dim, spec.num_gauss, spec.ivector_dim
+    C, Dl, G, Di = spec.feat_dim, spec.lda_dim, spec.num_gauss, spec.ivector_dim
     nsp = spec.splice_left + 1 + spec.splice_right
     # final.mat: affine LDA, D_lda x (C*nsp + 1); scaled so outputs are O(1) for MFCC-sized inputs
     lda = (rng.standard_normal((Dl, C * nsp + 1)) * (0.05 / math.sqrt(C * nsp))).astype(np.float32)
@@ -633,14 +655,27 @@ def write_model_dir(model_dir: Path, spec: ModelSpec) -> None:
     write_tree(model_dir / "model" / "model" / "tree", spec)
     conf = model_dir / "model" / "online" / "conf"
     conf.mkdir(parents=True, exist_ok=True)
-    mfcc = ["--use-energy=false", f"--num-mel-bins={spec.num_mel_bins}", f"--num-ceps={spec.num_ceps}",
-            "--low-freq=20", "--high-freq=-400", "--sample-frequency=16000"]
-    if spec.dither is not None:
-        mfcc.append(f"--dither={spec.dither}")
-    if spec.frame_length is not None:
-        mfcc.append(f"--frame-length={spec.frame_length}")
-    (conf / "mfcc.conf").write_text("# hires MFCC (egs/wsj/s5/conf/mfcc_hires.conf)\n" + "\n".join(mfcc) + "\n")
-    online = ["--feature-type=mfcc", f"--mfcc-config={conf / 'mfcc.conf'}"]
+    if spec.feature_type == "mfcc":
+        mfcc = ["--use-energy=false", f"--num-mel-bins={spec.num_mel_bins}", f"--num-ceps={spec.num_ceps}",
+                "--low-freq=20", "--high-freq=-400", "--sample-frequency=16000"]
+        if spec.dither is not None:
+            mfcc.append(f"--dither={spec.dither}")
+        if spec.frame_length is not None:
+            mfcc.append(f"--frame-length={spec.frame_length}")
+        (conf / "mfcc.conf").write_text("# hires MFCC (egs/wsj/s5/conf/mfcc_hires.conf)\n" + "\n".join(mfcc) + "\n")
+        online = ["--feature-type=mfcc", f"--mfcc-config={conf / 'mfcc.conf'}"]
+    else:
+        _ = spec.feat_dim      # (refuses a type other than fbank)
+        online = ["--feature-type=fbank"]
+        if spec.fbank_config:
+            fb: Dict[str, object] = {"num-mel-bins": spec.num_mel_bins, "low-freq": 20, "high-freq": -400, "sample-frequency": 16000}
+            if spec.dither is not None:
+                fb["dither"] = spec.dither
+            if spec.frame_length is not None:
+                fb["frame-length"] = spec.frame_length
+            fb.update(spec.fbank_opts or {})
+            (conf / "fbank.conf").write_text("".join(f"--{k}={_conf_value(v)}\n" for k, v in fb.items()))
+            online.append(f"--fbank-config={conf / 'fbank.conf'}")
     if spec.ivector_dim > 0:
         ie = model_dir / "model" / "online" / "ivector_extractor"
         write_ivector_extractor(ie, spec)
