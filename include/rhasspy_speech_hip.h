@@ -100,7 +100,10 @@ const char *rs_last_error(void);
  * TransitionModel + AmNnetSimple from final.mdl, ReadFstKaldiGeneric(HCLG.fst)).  The base feature is online.conf's
  * --feature-type: mfcc (--mfcc-config) or fbank (--fbank-config: log-mel filterbank rows, up to 128 columns); only the selected
  * type's file counts and none means the type's defaults (online-nnet2-feature-pipeline.cc:28-56).  plp, pitch and VTLN warping are
- * refused with a message.  Parses on the host only;
+ * refused with a message.  The network may start with TimeHeightConvolutionComponents (CNN-TDNN recipes) and a PermuteComponent;
+ * refused with a message are a convolution whose required time offsets are a proper subset of its time offsets (zero padding in
+ * time), one with more than 8 distinct time offsets or 128 output heights, one whose input rows of a frame exceed the kernel's 96 KiB
+ * of LDS, recurrent networks, and component types the HIP kernels do not implement.  Parses on the host only;
  * the device copy is made on first use or by rs_model_to_device().  Immutable afterwards, shareable
  * between threads. */
 int rs_model_load_files(const char *final_mdl, const char *hclg_fst, const char *online_conf,
@@ -113,7 +116,9 @@ void rs_model_free(rs_model *model);
 /* Writes a one-line-per-item description of the parsed model (dims, layer plan, graph size) into buf;
  * returns the number of bytes needed (like snprintf).  The first line is the base feature's: `mfcc: win= shift= padded= mel_bins=
  * ceps= dither=`, or for a filterbank model `fbank: win= shift= padded= mel_bins= dim= use_energy= htk_compat= use_log= use_power=
- * dither=` (dim = mel_bins + use_energy, the width of a feature row).  Two lines are state, not structure: `layer_gemm:` and
+ * dither=` (dim = mel_bins + use_energy, the width of a feature row).  After the `op:` lines comes one `conv:` line per convolution
+ * (none for a model without one): name, filters in->out, heights in->out, height subsampling, offsets, distinct time offsets, k, the
+ * kernel instantiation chosen at load, frames / pixel tiles / LDS bytes per workgroup, filter chunks, grid.  Two lines are state, not structure: `layer_gemm:` and
  *   arenas: device blocks=B bytes=N allocations=A; host blocks=B bytes=N allocations=A
  * summed over the model's decode contexts: the blocks and bytes their per-call arenas hold now, and the hipMalloc / hipHostMalloc
  * calls they have made since the model was loaded.  `allocations` stands still once every context has seen its largest call twice.
@@ -408,7 +413,8 @@ int rs_shard_gather(int32_t device_id, int32_t n_utts, int32_t rank, int32_t wor
 int rs_bind_host_thread(int32_t device_id);
 
 /* Parity taps (only with opts.keep_intermediates): kind 0 = nnet input features (T x C), 1 = iVector
- * (n x D_iv: one row offline, one row per nnet chunk for streams), 2 = log-likelihoods (T x P). */
+ * (n x D_iv: one row offline, one row per nnet chunk for streams), 2 = log-likelihoods (T x P); 3 + k = the output of the
+ * model's k-th convolution (T x heights * filters, ReLU and BatchNorm applied; batch calls only). */
 int rs_result_matrix(const rs_result *r, int32_t utt, int32_t kind, const float **data, int32_t *rows, int32_t *cols);
 /* Decoder work counters of one utterance, for the algorithmic-bytes figure of SURVEY.md section 8(d):
  * out[0] = tokens expanded, [1] = arcs examined, [2] = token insertions (FindOrAddToken calls),

@@ -268,7 +268,13 @@ Model::Model(const std::string &final_mdl, const std::string &hclg, const std::s
     if (op.kind == LayerOp::kGemm && (int)op.segs.size() > kMaxSegs) Fail("nnet3: layer " + op.name + " has too many input segments");
     if ((int)op.stages.size() > kMaxStages) Fail("nnet3: layer " + op.name + " has too many fused stages");
     if (op.kind == LayerOp::kEltwise && op.terms.size() > 8) Fail("nnet3: layer " + op.name + " sums too many terms");
+    if (op.kind == LayerOp::kGather && op.terms.size() > 8) Fail("nnet3: layer " + op.name + " gathers from too many Append() parts");
   }
+  // which convolution kernel runs each convolution, on what tile and with how much LDS: decided here, so that a geometry the
+  // kernels do not cover fails the load (conv_plan.h)
+  conv_plans_.assign(am_.nnet.ops.size(), ConvLaunchPlan());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++)
+    if (am_.nnet.ops[i].kind == LayerOp::kConv) conv_plans_[i] = PlanConv(am_.nnet.ops[i].conv, am_.nnet.ops[i].name);
 }
 
 // rs_decode_opts.prune_output_pdfs: the search looks log-likelihoods up by the pdf of the arc it crosses
@@ -410,6 +416,16 @@ template <typename T> T *Model::Upload(const std::vector<T> &v) { return static_
 
 void Model::BuildGemmPlan(const LayerOp &op, GemmPlan *plan) {
   plan->op = &op;
+  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather) {      // (their own operands: ToDevice; here the bias and the fused stages)
+    plan->d_bias = op.bias.empty() ? nullptr : Upload(op.bias);
+    plan->d_stage.clear();
+    for (auto &st : op.stages) {
+      float *s = nullptr, *o = nullptr;
+      if (st.kind == EltStage::kScaleOffset) { s = Upload(st.scale); o = Upload(st.offset); }
+      plan->d_stage.emplace_back(s, o);
+    }
+    return;
+  }
   int k = 0;
   plan->seg_k0.clear();
   for (auto &sg : op.segs) { plan->seg_k0.push_back(k); k += RoundUp(sg.ncols, kGemmBK); }
@@ -696,6 +712,20 @@ void Model::ToDevice() {
   // ---- nnet
   gemm_plans_.assign(am_.nnet.ops.size(), GemmPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++) BuildGemmPlan(am_.nnet.ops[i], &gemm_plans_[i]);
+  conv_dev_.assign(am_.nnet.ops.size(), ConvOperands());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++) {
+    const LayerOp &op = am_.nnet.ops[i];
+    if (op.kind == LayerOp::kConv) {
+      std::vector<float> wt;
+      std::vector<int> koff;
+      ConvWeightImage(op.conv, conv_plans_[i], op.W, &wt, &koff);
+      conv_dev_[i].wt = Upload(wt);
+      conv_dev_[i].tab0 = Upload(koff);
+    } else if (op.kind == LayerOp::kGather) {
+      conv_dev_[i].tab0 = Upload(op.gather_part);
+      conv_dev_[i].tab1 = Upload(op.gather_col);
+    }
+  }
   {
     // operand images: a buffer gets one when a split-bf16 layer reads it through GemmKernelB3I; it is still stored as plain
     // floats when anything else reads it (the nnet's input / output, an elementwise op, a layer on another kernel)
@@ -875,7 +905,8 @@ std::string Model::Describe() const {
      << " left_context=" << n.left_context << " right_context=" << n.right_context << " priors=" << n.priors.size()
      << " components=" << n.components.size() << " ops=" << n.ops.size() << "\n";
   for (auto &op : n.ops) {
-    os << "op: " << (op.kind == LayerOp::kGemm ? "gemm" : "eltwise") << " " << op.name << " out_dim=" << op.out_dim;
+    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather"};
+    os << "op: " << kinds[op.kind] << " " << op.name << " out_dim=" << op.out_dim;
     if (op.kind == LayerOp::kGemm) {
       os << " k=" << op.W.cols << " segs=";
       for (auto &s : op.segs) os << "[" << s.src_buf << ":" << s.offset << ":" << s.ncols << "]";
@@ -887,6 +918,8 @@ std::string Model::Describe() const {
     if (n.bufs[op.out_buf].stride > 1) os << " rows=every-" << n.bufs[op.out_buf].stride;      // (--frame-subsampling-factor: nothing reads the rows between)
     os << "\n";
   }
+  for (size_t i = 0; i < n.ops.size(); i++)      // (one line per convolution: its geometry and what the planner chose for it at load)
+    if (n.ops[i].kind == LayerOp::kConv) os << "conv: " << DescribeConv(n.ops[i].name, n.ops[i].conv, conv_plans_[i]) << "\n";
   os << "transition_model: tids=" << am_.trans.id2pdf.size() - 1 << " pdfs=" << am_.trans.num_pdfs << "\n";
   if (pruned_from_) os << "output layer: pruned to the " << am_.nnet.output_dim << " of " << pruned_from_ << " pdfs that occur on HCLG arcs\n";
   os << "hclg: states=" << hclg_.num_states() << " arcs=" << hclg_.arcs.size() << " start=" << hclg_.start << "\n";
@@ -1289,6 +1322,49 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
         conv_map = rm->rows; conv_rows = rm->count;
       } else {
         LaunchGemmRecorded(op.name, gd, rows, d_row_ivec, s, &sw);
+      }
+    } else if (op.kind == LayerOp::kConv) {
+      ConvDev d;
+      std::memset(&d, 0, sizeof(d));
+      d.src = bufp[op.terms[0].src_buf]; d.ld = buf_ld[op.terms[0].src_buf]; d.col0 = op.terms[0].src_col;
+      d.n_t = (int)op.terms.size();
+      for (int k = 0; k < d.n_t; k++) d.row_off[k] = op.terms[k].offset;
+      d.wt = conv_dev_[i].wt; d.koff = conv_dev_[i].tab0; d.bias = gemm_plans_[i].d_bias;
+      d.nstages = (int)op.stages.size();
+      for (int k = 0; k < d.nstages; k++) {
+        const EltStage &st = op.stages[k];
+        d.stages[k].kind = st.kind == EltStage::kRelu ? 0 : (st.kind == EltStage::kScaleOffset ? 1 : 4);
+        d.stages[k].scale = gemm_plans_[i].d_stage[k].first; d.stages[k].offset = gemm_plans_[i].d_stage[k].second; d.stages[k].alpha = st.alpha;
+      }
+      d.out = bufp[op.out_buf]; d.ldo = buf_ld[op.out_buf];
+      d.filters_in = op.conv.filters_in; d.filters_out = op.conv.filters_out; d.height_in = op.conv.height_in;
+      d.height_out = op.conv.height_out; d.height_sub = op.conv.height_sub;
+      d.plan = conv_plans_[i];
+      const BufferInfo &ob = nn.bufs[op.out_buf];
+      if (const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride)) {     // only the rows somebody reads
+        d.row_map = rm->rows;
+        LaunchConv(d, rm->count, s);
+        conv_map = rm->rows; conv_rows = rm->count;
+      } else {
+        LaunchConv(d, rows, s);
+      }
+    } else if (op.kind == LayerOp::kGather) {
+      GatherDev d;
+      std::memset(&d, 0, sizeof(d));
+      d.nparts = (int)op.terms.size();
+      for (int k = 0; k < d.nparts; k++) {
+        d.parts[k].src = bufp[op.terms[k].src_buf]; d.parts[k].ld = buf_ld[op.terms[k].src_buf];
+        d.parts[k].col0 = op.terms[k].src_col; d.parts[k].row_off = op.terms[k].offset;
+      }
+      d.part = conv_dev_[i].tab0; d.col = conv_dev_[i].tab1; d.dim = op.out_dim;
+      d.out = bufp[op.out_buf]; d.ldo = buf_ld[op.out_buf];
+      const BufferInfo &ob = nn.bufs[op.out_buf];
+      if (const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride)) {
+        d.row_map = rm->rows;
+        LaunchGather(d, rm->count, s);
+        conv_map = rm->rows; conv_rows = rm->count;
+      } else {
+        LaunchGather(d, rows, s);
       }
     } else {
       EltwiseDev d;
@@ -1936,6 +2012,16 @@ void Model::BatchIntermediates(const BatchCall &b, const float *ll, int ll_ld, U
     RS_HIP(hipMemcpy2D(ur.feats.data(), sizeof(float) * C, fin, sizeof(float) * in_ld, sizeof(float) * C, T, hipMemcpyDeviceToHost));
     const float *lin = ll + (fsf > 1 ? (size_t)b.dec_base[u] : (size_t)b.row_base[u] + L_) * ll_ld;
     RS_HIP(hipMemcpy2D(ur.loglikes.data(), sizeof(float) * P, lin, sizeof(float) * ll_ld, sizeof(float) * P, T_dec, hipMemcpyDeviceToHost));
+    ur.conv_out.clear();
+    ur.conv_dim.clear();
+    for (auto &op : nn.ops) {
+      if (op.kind != LayerOp::kConv) continue;
+      ur.conv_dim.push_back(op.out_dim);
+      ur.conv_out.emplace_back((size_t)T * op.out_dim);
+      const int ld = b.buf_ld[op.out_buf];
+      RS_HIP(hipMemcpy2D(ur.conv_out.back().data(), sizeof(float) * op.out_dim, b.bufp[op.out_buf] + ((size_t)b.row_base[u] + L_) * ld, sizeof(float) * ld,
+                         sizeof(float) * op.out_dim, T, hipMemcpyDeviceToHost));
+    }
     if (has_iv) {
       ur.ivector.resize((size_t)ur.ivec_rows * Di);
       RS_HIP(hipMemcpy2D(ur.ivector.data(), sizeof(float) * Di, b.d_ivec + (size_t)ivrow_base[u] * ld_i, sizeof(float) * ld_i,

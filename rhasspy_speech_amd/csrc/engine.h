@@ -63,6 +63,10 @@ struct UttResult {
   std::vector<Hypothesis> hyps;
   int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<float> feats, ivector, loglikes;   // keep_intermediates only
+  // keep_intermediates, batch calls: per convolution op, in op order, its output buffer's rows of the real frames (T x dim, the
+  // fused stages applied; under --frame-subsampling-factor only the rows the op was evaluated on hold anything)
+  std::vector<std::vector<float>> conv_out;
+  std::vector<int> conv_dim;
   int feat_dim = 0, ivec_rows = 0, ivec_dim = 0, num_pdfs = 0;
   std::shared_ptr<CompactLat> clat;              // emit_lattice only
 };
@@ -85,6 +89,11 @@ struct GemmPlan {        // one LayerOp of kind kGemm, uploaded
   bool interleave = false;        // W3 k-steps alternate between the segments (see GemmKernelB3)
   std::vector<int> seg_k0;
   std::vector<std::pair<float *, float *>> d_stage;   // scale/offset vectors per stage
+};
+
+struct ConvOperands {     // one LayerOp of kind kConv (W in the kernel's order, the k -> LDS offset table) or kGather (part, column per output column)
+  float *wt = nullptr;
+  int *tab0 = nullptr, *tab1 = nullptr;
 };
 
 struct LatArcBuffer { void *d = nullptr; size_t cap = 0; };      // capacity in LatArc records
@@ -355,6 +364,8 @@ class Model {
   GemmPlan lda_plan1_;
   const GemmPlan &LdaPlan(int ld) const { return (lda_plan1_.op && ld == fc_.mfcc.nceps) ? lda_plan1_ : lda_plan_; }
   std::vector<GemmPlan> gemm_plans_;  // indexed like am_.nnet.ops (unused entries for eltwise ops)
+  std::vector<ConvLaunchPlan> conv_plans_;   // indexed like am_.nnet.ops: what the planner chose at load for the convolutions
+  std::vector<ConvOperands> conv_dev_;       // indexed like am_.nnet.ops: the convolutions' and gathers' device operands
   float *d_log_priors_ = nullptr;
   HclgDev hclg_dev_{};
   RevGraphDev rev_dev_{};

@@ -188,6 +188,30 @@ void KaldiReader::ReadIntVector(std::vector<int32_t> *v) {
   }
 }
 
+// base/io-funcs-inl.h:131-196: binary = size byte, count, 2 * count raw values; text = "[ a,b c,d ]"
+void KaldiReader::ReadIntPairVector(std::vector<int32_t> *flat) {
+  flat->clear();
+  if (binary_) {
+    int sz = (signed char)Get();
+    if (sz != 4) Fail(name_ + ": integer pair vector with element size " + std::to_string(sz));
+    int32_t n;
+    ReadRaw(&n, 1);
+    if (n < 0) Fail(name_ + ": negative vector size");
+    flat->resize((size_t)n * 2);
+    if (n) ReadRaw(flat->data(), (size_t)n * 2);
+    return;
+  }
+  SkipSpace();
+  if (Get() != '[') Fail(name_ + ": expected '[' for integer pair vector");
+  while (true) {
+    SkipSpace();
+    if (PeekChar() == ']') { pos_++; break; }
+    flat->push_back((int32_t)ReadTextNumber());
+    if (Get() != ',') Fail(name_ + ": expected ',' inside an integer pair");
+    flat->push_back((int32_t)ReadTextNumber());
+  }
+}
+
 void KaldiReader::ReadTextMatrix(std::vector<double> *vals, int *rows, int *cols) {
   // matrix/kaldi-matrix.cc Matrix::Read text branch: '[' numbers, rows end at '\n' or ';', ']' ends.
   SkipSpace();

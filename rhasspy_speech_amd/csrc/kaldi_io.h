@@ -55,6 +55,7 @@ class KaldiReader {
   // A basic value whose type (int32/int64 vs float/double) is only known to the consumer: returns both readings.
   void ReadBasicAny(double *as_float, int64_t *as_int);
   void ReadIntVector(std::vector<int32_t> *v);
+  void ReadIntPairVector(std::vector<int32_t> *flat);   // ReadIntegerPairVector: (first, second) of every pair, one after the other
   void ReadVector(std::vector<float> *v);    // FV or DV (converted)
   void ReadVectorD(std::vector<double> *v);  // FV or DV
   void ReadMatrix(MatF *m);                  // FM or DM

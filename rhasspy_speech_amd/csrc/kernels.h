@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "conv_plan.h"
 #include "gemm_launch.h"
 #include "search_plan.h"
 
@@ -166,6 +167,10 @@ size_t ActImagePartBytes(int rows, int guard, int dim);      // bytes of one par
 // sw: the switches to plan with (null: read from the environment now); planned: where given, receives the plan that was launched
 void LaunchGemm(const GemmDev &d, int rows, const int *row_ivec, hipStream_t s, const GemmSwitches *sw = nullptr, GemmLaunch *planned = nullptr);
 int DeviceNumCu();      // compute units of the current device, asked once per process (what the launch planners are given)
+
+// TimeHeightConvolutionComponent / PermuteComponent (nnet_conv.hip; the descriptors and the load-time plan: conv_plan.h)
+void LaunchConv(const ConvDev &d, int rows, hipStream_t s);
+void LaunchGather(const GatherDev &d, int rows, hipStream_t s);
 
 struct SumTermDev { const float *src; int ld, col0, row_off; float scale; };
 struct EltwiseDev {

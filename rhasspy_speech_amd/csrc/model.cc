@@ -605,6 +605,11 @@ static Component ReadComponent(KaldiReader &r) {
     if (tok == close) break;
     if (tok.empty() || tok[0] != '<') Fail(r.name() + ": malformed component " + c.type + " near " + tok.substr(0, 40));
     if (kIntVectorFields.count(tok)) { r.ReadIntVector(&c.iv[tok]); continue; }
+    if (c.type == "TimeHeightConvolutionComponent") {
+      // ConvolutionModel::Read (convolution.cc:252-280): <Offsets> is a vector of (time, height) pairs, kept flat
+      if (tok == "<Offsets>") { r.ReadIntPairVector(&c.iv[tok]); continue; }
+      if (tok == "<RequiredTimeOffsets>") { r.ReadIntVector(&c.iv[tok]); continue; }
+    }
     c.b[tok] = true;   // present (bare flag unless values follow)
     while (true) {
       int ch = r.PeekChar();
@@ -635,6 +640,63 @@ static Component ReadComponent(KaldiReader &r) {
     }
   }
   return c;
+}
+
+// The <ConvolutionModel> of a TimeHeightConvolutionComponent with what ConvolutionModel::Check(false, true) (convolution.cc:
+// 130-209) and TimeHeightConvolutionComponent::Check ask of it and of the parameters.
+ConvGeom ReadConvGeom(const Component &c, const std::string &name) {
+  const std::string what = "nnet3: TimeHeightConvolutionComponent '" + name + "': ";
+  for (const char *k : {"<NumFiltersIn>", "<NumFiltersOut>", "<HeightIn>", "<HeightOut>", "<HeightSubsampleOut>"})
+    if (!c.i.count(k)) Fail(what + "no " + k);
+  ConvGeom g;
+  g.filters_in = c.Int("<NumFiltersIn>"); g.filters_out = c.Int("<NumFiltersOut>");
+  g.height_in = c.Int("<HeightIn>"); g.height_out = c.Int("<HeightOut>"); g.height_sub = c.Int("<HeightSubsampleOut>");
+  auto oit = c.iv.find("<Offsets>"), rit = c.iv.find("<RequiredTimeOffsets>");
+  if (oit == c.iv.end() || rit == c.iv.end()) Fail(what + "no <Offsets> or <RequiredTimeOffsets>");
+  for (size_t i = 0; i + 1 < oit->second.size(); i += 2) g.offsets.emplace_back(oit->second[i], oit->second[i + 1]);
+  const std::set<int> required(rit->second.begin(), rit->second.end());
+  if (g.filters_in <= 0 || g.filters_out <= 0 || g.height_in <= 0 || g.height_out <= 0 || g.height_sub <= 0 || g.offsets.empty() ||
+      required.empty())
+    Fail(what + "Convolution model fails basic check.");
+  if (g.filters_in > 4096 || g.filters_out > 4096 || g.height_in > 4096 || g.height_out > 4096 || g.height_sub > 4096 || g.offsets.size() > 4096)
+    Fail(what + "a dimension above 4096 is not supported by the HIP convolution kernel");
+  for (size_t i = 0; i + 1 < g.offsets.size(); i++)
+    if (!(g.offsets[i] < g.offsets[i + 1])) Fail(what + "the (time, height) offsets are not sorted and unique");
+  std::set<int> all;
+  for (auto &o : g.offsets) {
+    if (std::abs(o.first) > 4096 || std::abs(o.second) > 4096) Fail(what + "an offset beyond +-4096 is not supported");
+    all.insert(o.first);
+  }
+  for (int t : required)
+    if (!all.count(t)) Fail(what + "Required time offsets not a subset of all_time_offsets.");
+  std::vector<char> used(g.offsets.size(), 0);
+  for (int h = 0; h < g.height_out; h++) {
+    bool some = false;
+    for (size_t i = 0; i < g.offsets.size(); i++) {
+      const int h_in = h * g.height_sub + g.offsets[i].second;
+      if (h_in < 0 || h_in >= g.height_in) continue;
+      used[i] = 1;
+      if (required.count(g.offsets[i].first)) some = true;
+    }
+    if (!some) Fail(what + "for the " + std::to_string(h) + "'th output height, no input is available, if only required time-indexes are available.");
+  }
+  for (size_t i = 0; i < used.size(); i++)
+    if (!used[i])
+      Fail(what + "(time,height) offset (" + std::to_string(g.offsets[i].first) + "," + std::to_string(g.offsets[i].second) + ") of this computation is never used.");
+  // Zero padding in time: a frame whose optional offsets fall outside the chunk's input gets zeros for them, so the result
+  // depends on where the chunk boundaries lie.  Never approximated.
+  if (required.size() != all.size())
+    Fail(what + "its required time offsets are a proper subset of its time offsets (zero padding in time, whose result depends on the frames "
+                "a chunk holds): not supported by the HIP acoustic-model kernels");
+  g.time_offsets.assign(all.begin(), all.end());
+  auto wit = c.m.find("<LinearParams>");
+  auto bit = c.v.find("<BiasParams>");
+  if (wit == c.m.end() || bit == c.v.end()) Fail(what + "no <LinearParams> or <BiasParams>");
+  if (wit->second.rows != g.filters_out || wit->second.cols != g.K())
+    Fail(what + "<LinearParams> is " + std::to_string(wit->second.rows) + " x " + std::to_string(wit->second.cols) + ", the model needs " +
+         std::to_string(g.filters_out) + " x " + std::to_string(g.K()));
+  if ((int)bit->second.size() != g.filters_out) Fail(what + "<BiasParams> has " + std::to_string(bit->second.size()) + " elements, not " + std::to_string(g.filters_out));
+  return g;
 }
 
 // ---- descriptor parser (nnet3/nnet-descriptor.cc grammar subset) ----
@@ -770,6 +832,12 @@ int ComponentOutputDim(const Component &c, const std::string &name) {
       c.type == "TdnnComponent")
     return rows("<LinearParams>");
   if (c.type == "LinearComponent") return rows("<Params>");
+  if (c.type == "TimeHeightConvolutionComponent") { const ConvGeom g = ReadConvGeom(c, name); return g.filters_out * g.height_out; }
+  if (c.type == "PermuteComponent") {
+    auto it = c.iv.find("<ColumnMap>");
+    if (it == c.iv.end() || it->second.empty()) Fail("nnet3: PermuteComponent '" + name + "' has no <ColumnMap>");
+    return (int)it->second.size();
+  }
   if (c.type == "NormalizeComponent") {
     int d = c.i.count("<InputDim>") ? c.Int("<InputDim>") : c.Int("<Dim>");
     bool add = c.f.count("<AddLogStddev>") && c.f.at("<AddLogStddev>")[0] != 0.0;
@@ -818,6 +886,8 @@ void Nnet::Read(KaldiReader &r, int frames_per_chunk, int extra_left_context_ini
     cfg.push_back(line);
   }
   ReadNnetComponents(r, &component_names, &components);
+  for (size_t c = 0; c < components.size(); c++)      // (checked before the set-up walks the network with their offsets)
+    if (components[c].type == "TimeHeightConvolutionComponent") (void)ReadConvGeom(components[c], component_names[c]);
   {
     // CollapseModel + the rand() calls of the reference's set-up (nnet3_setup.h); RS_NO_COLLAPSE=1 keeps the layers as
     // written (A/B of the rounding difference; the rand() count is that of the reference either way)
@@ -1000,6 +1070,8 @@ void Nnet::Compile() {
       if (it == c.iv.end() || it->second.empty()) Fail("nnet3: TdnnComponent without <TimeOffsets>");
       return std::vector<int>(it->second.begin(), it->second.end());
     }
+    if (nd.kind == NnetNode::kComponent && components[nd.component].type == "TimeHeightConvolutionComponent")
+      return ReadConvGeom(components[nd.component], component_names[nd.component]).time_offsets;
     return {0};
   };
   // required extension per node: rows t in [-lext, T+rext)
@@ -1055,9 +1127,10 @@ void Nnet::Compile() {
     }
     const Component *comp = nd.kind == NnetNode::kComponent ? &components[nd.component] : nullptr;
     bool affine = comp && IsAffineLike(comp->type);
+    const bool conv = comp && comp->type == "TimeHeightConvolutionComponent", permute = comp && comp->type == "PermuteComponent";
     std::vector<EltStage> stages;
-    bool elt = !affine && (comp == nullptr || EltStagesFor(*comp, nd.name, &stages));
-    if (!affine && !elt)
+    bool elt = !affine && !conv && !permute && (comp == nullptr || EltStagesFor(*comp, nd.name, &stages));
+    if (!affine && !elt && !conv && !permute)
       Fail("nnet3: component type " + comp->type + " (node " + nd.name + ") is not supported by the HIP acoustic-model kernels");
 
     // ---- fuse an elementwise node into its producer when it is the only consumer of a plain reference
@@ -1070,6 +1143,7 @@ void Nnet::Compile() {
         bool ok = true;
         // a row-wise reduction can only be fused when the op's tile covers the whole row; keep those standalone
         for (auto &s : stages) if (s.kind == EltStage::kLogSoftmax || s.kind == EltStage::kNormalize) ok = false;
+        if (op.kind == LayerOp::kGather) ok = false;      // (a column gather has no epilogue)
         if (ok) {
           op.stages.insert(op.stages.end(), stages.begin(), stages.end());
           op.name += "+" + nd.name;
@@ -1130,6 +1204,47 @@ void Nnet::Compile() {
       }
       if (wcol != W.cols) Fail("nnet3: component of node " + nd.name + " expects input dim " + std::to_string(W.cols) + " but its descriptor provides " + std::to_string(wcol));
       if (!op.bias.empty() && (int)op.bias.size() != W.rows) Fail("nnet3: bias dim mismatch in node " + nd.name);
+    } else if (conv) {
+      op.kind = LayerOp::kConv;
+      op.conv = ReadConvGeom(*comp, component_names[nd.component]);
+      op.W = comp->m.at("<LinearParams>");
+      op.bias = comp->v.at("<BiasParams>");
+      if (nd.input.parts.size() != 1 || nd.input.parts[0].terms.size() != 1 || nd.input.parts[0].terms[0].scale != 1.0f)
+        Fail("nnet3: the input of convolution node " + nd.name + " must be one node or an Offset() of one");
+      const DescTerm &t = nd.input.parts[0].terms[0];
+      int b, c;
+      term_src(t, &b, &c);
+      if (b == -2 || t.const_t) Fail("nnet3: a convolution over the iVector input is not supported (node " + nd.name + ")");
+      if (nd.input.dim != op.conv.filters_in * op.conv.height_in)
+        Fail("nnet3: convolution node " + nd.name + " expects input dim " + std::to_string(op.conv.filters_in * op.conv.height_in) +
+             " but its descriptor provides " + std::to_string(nd.input.dim));
+      for (int dt : op.conv.time_offsets) op.terms.push_back({b, c, t.offset + dt, 1.0f});
+    } else if (permute) {
+      // out[:, i] = in[:, column_map[i]] (CopyCols, nnet-simple-component.cc:3990-3995) over the parts of an Append
+      op.kind = LayerOp::kGather;
+      const std::vector<int32_t> &cm = comp->iv.at("<ColumnMap>");
+      if ((int)cm.size() != nd.input.dim)
+        Fail("nnet3: PermuteComponent node " + nd.name + " has a column map of " + std::to_string(cm.size()) + " entries but its descriptor provides " +
+             std::to_string(nd.input.dim));
+      std::vector<int> part_col0;
+      int col0 = 0;
+      for (auto &p : nd.input.parts) {
+        if (p.terms.size() != 1 || p.terms[0].scale != 1.0f) Fail("nnet3: a Sum() or Scale() feeding PermuteComponent node " + nd.name + " is not supported");
+        int b, c;
+        term_src(p.terms[0], &b, &c);
+        if (b == -2 || p.terms[0].const_t) Fail("nnet3: PermuteComponent node " + nd.name + " reads the iVector input directly: not supported");
+        op.terms.push_back({b, c, p.terms[0].offset, 1.0f});
+        part_col0.push_back(col0);
+        col0 += p.dim;
+      }
+      std::vector<char> seen(cm.size(), 0);
+      for (int32_t src : cm) {
+        if (src < 0 || src >= (int)cm.size() || seen[src]) Fail("nnet3: PermuteComponent node " + nd.name + ": Column map does not represent a permutation.");
+        seen[src] = 1;
+        int part = (int)(std::upper_bound(part_col0.begin(), part_col0.end(), (int)src) - part_col0.begin()) - 1;
+        op.gather_part.push_back(part);
+        op.gather_col.push_back(src - part_col0[part]);
+      }
     } else {
       op.kind = LayerOp::kEltwise;
       if (nd.input.parts.size() != 1) {

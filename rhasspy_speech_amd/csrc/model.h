@@ -190,8 +190,17 @@ struct EltStage {
   float alpha = 1.0f;                 // kScale / kNormalize target_rms
 };
 struct SumTerm { int src_buf; int src_col; int offset; float scale; };
+// TimeHeightConvolutionComponent (nnet3/convolution.h:125-208): rows are frames, columns (height, filter) with the filter
+// fastest; weight column = offset index * filters_in + filter, offsets in (time, height) order.
+struct ConvGeom {
+  int filters_in = 0, filters_out = 0, height_in = 0, height_out = 0, height_sub = 1;
+  std::vector<std::pair<int, int>> offsets;   // (time, height), sorted
+  std::vector<int> time_offsets;              // the distinct time offsets, ascending: LayerOp::terms[i] reads the rows of time_offsets[i]
+  int K() const { return (int)offsets.size() * filters_in; }
+};
 struct LayerOp {
-  enum Kind { kGemm, kEltwise } kind = kGemm;
+  // kConv: out = stages(bias + conv(terms)); kGather: out[:, i] = part(gather_part[i])[:, gather_col[i]] (PermuteComponent over an Append)
+  enum Kind { kGemm, kEltwise, kConv, kGather } kind = kGemm;
   std::string name;
   int out_buf = -1, out_dim = 0;
   // kGemm
@@ -203,8 +212,12 @@ struct LayerOp {
   int res_buf = -1;
   float res_scale = 1.0f;
   // kEltwise: out = stages(sum_i scale_i * src_i[t+o_i])
+  // kConv: one term per distinct time offset (the same source, offset = descriptor offset + time offset; scale 1), W and bias as
+  // for kGemm.  kGather: one term per Append part, in order.
   std::vector<SumTerm> terms;
   std::vector<EltStage> stages; // applied after the gemm/sum, in order
+  ConvGeom conv;                           // kConv
+  std::vector<int> gather_part, gather_col;   // kGather, per output column: the term and the column inside it
 };
 struct BufferInfo {
   int dim = 0, lext = 0, rext = 0;   // rows cover t in [-lext, T + rext)
@@ -233,6 +246,10 @@ struct Nnet {
   void SetSubsampling(int factor);   // fills BufferInfo::stride for outputs wanted at t = 0, factor, 2 factor, ...
   int FindNode(const std::string &name) const;
 };
+
+// The geometry of a parsed TimeHeightConvolutionComponent, checked as the reference checks it at load (and refused where its
+// required time offsets are fewer than its time offsets)
+ConvGeom ReadConvGeom(const Component &c, const std::string &name);
 
 // <NumComponents> ... </Nnet3> (nnet-nnet.cc:608-621)
 void ReadNnetComponents(KaldiReader &r, std::vector<std::string> *names, std::vector<Component> *comps);

@@ -510,6 +510,7 @@ struct Net {
   std::vector<Node> nodes;
   std::vector<std::string> *comp_names;
   std::vector<Component> *comps;
+  mutable std::map<int, std::vector<int32_t>> conv_offsets;   // per convolution component: its distinct time offsets
 
   std::vector<std::string> Names() const {
     std::vector<std::string> n;
@@ -529,6 +530,19 @@ struct Net {
   const std::string &CType(int c) const { return (*comps)[c].type; }
   const std::vector<int32_t> *TimeOffsets(int c) const {
     const Component &k = (*comps)[c];
+    if (k.type == "TimeHeightConvolutionComponent") {
+      // all_time_offsets (convolution.cc:109-115): GetInputIndexes asks for every one of them, and IsComputable needs the
+      // required ones -- the same set in every model that loads (model.cc: ReadConvGeom)
+      auto have = conv_offsets.find(c);
+      if (have != conv_offsets.end()) return &have->second;
+      auto it = k.iv.find("<Offsets>");
+      if (it == k.iv.end() || it->second.empty()) Fail("nnet3: TimeHeightConvolutionComponent without <Offsets>");
+      std::vector<int32_t> t;
+      for (size_t i = 0; i + 1 < it->second.size(); i += 2) t.push_back(it->second[i]);
+      std::sort(t.begin(), t.end());
+      t.erase(std::unique(t.begin(), t.end()), t.end());
+      return &(conv_offsets[c] = t);
+    }
     if (k.type != "TdnnComponent") return nullptr;
     auto it = k.iv.find("<TimeOffsets>");
     if (it == k.iv.end()) Fail("nnet3: TdnnComponent without <TimeOffsets>");
@@ -1119,6 +1133,26 @@ Nnet3SetupResult Nnet3Setup(const std::vector<std::string> &config_lines, std::v
     std::sort(tdnn.begin(), tdnn.end());
     tdnn.erase(std::unique(tdnn.begin(), tdnn.end()), tdnn.end());
     for (size_t i = 0; i < tdnn.size(); i++) rng.Rand();
+    // A convolution step compiles its ConvolutionComputation twice -- ReorderIndexes (Compiler::CreateStepInfo) and
+    // PrecomputeIndexes (nnet-convolutional-component.cc:408-422,560-579) -- and CompileConvolutionComputation checks the model
+    // against the step's times at four stages (convolution.cc:1380-1401); each check draws min(5, num_t_out) output times
+    // (:1345-1347) unless the step has a single one (RandInt over an empty range draws nothing).  num_t_out: the step's output
+    // times on their regular grid (RegularizeTList, :1431-1446), which none of the four stages changes.
+    std::map<int, std::vector<int>> conv_t;
+    for (int c = begin; c < end; c++) {
+      const Node &n = net.nodes[b.cindexes[c].node];
+      if (n.type == Node::kComponent && net.CType(n.comp) == "TimeHeightConvolutionComponent") conv_t[b.cindexes[c].node].push_back(b.cindexes[c].i.t);
+    }
+    for (auto &kv : conv_t) {
+      std::vector<int> &t = kv.second;
+      std::sort(t.begin(), t.end());
+      t.erase(std::unique(t.begin(), t.end()), t.end());
+      int step = 0;
+      for (size_t i = 0; i + 1 < t.size(); i++) step = std::gcd(step, t[i + 1] - t[i]);
+      const int num_t_out = step == 0 ? 1 : 1 + (t.back() - t.front()) / step;
+      if (num_t_out > 1)
+        for (int i = 0; i < 2 * 4 * std::min(5, num_t_out); i++) rng.Rand();
+    }
     begin = end;
   }
   // Optimize -> SplitRowOps -> InsertCommands (nnet-optimize-utils.cc:2883-2892,4654): the rows a chunk reads from the

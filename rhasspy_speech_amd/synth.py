@@ -88,6 +88,15 @@ class KaldiWriter:
             self.buf.write(("[ " + " ".join(str(int(x)) for x in v) + " ]\n").encode())
         return self
 
+    def int_pair_vector(self, v: Sequence[Tuple[int, int]]) -> "KaldiWriter":
+        """WriteIntegerPairVector (base/io-funcs-inl.h:93-127)."""
+        if self.binary:
+            self.buf.write(b"\x04" + struct.pack("<i", len(v)))
+            self.buf.write(np.asarray(v, dtype="<i4").reshape(-1).tobytes())
+        else:
+            self.buf.write(("[ " + "".join(f"{int(a)},{int(b)} " for a, b in v) + "]\n").encode())
+        return self
+
     def vector(self, v: np.ndarray, double: bool = False) -> "KaldiWriter":
         v = np.asarray(v)
         if self.binary:
@@ -195,6 +204,16 @@ class ModelSpec:
     feature_type: str = "mfcc"
     fbank_opts: Optional[Dict[str, object]] = None
     fbank_config: bool = True
+    # A convolutional front end between the input and the first affine (nnet3's CNN-TDNN recipes: conv-relu-batchnorm-layer).
+    # One dict per layer: filters, height_out, sub (height subsampling, default 1) and either time_offsets + height_offsets (the
+    # rectangle of both) or offsets (explicit (time, height) pairs); required_time_offsets (default: all of them); gain (default
+    # 1: a factor on the layer's weights).  The first layer sees the input as one filter of feat_dim heights, or, with
+    # conv_ivector_maps, 1 + conv_ivector_maps filters.  Behind the stack the "lda" FixedAffine maps to hidden_dim.
+    conv_layers: Tuple[Dict[str, object], ...] = ()
+    conv_idct: bool = False          # idct-layer in front: FixedAffine (feat_dim x feat_dim) + BatchNorm
+    # > 0: the iVector goes through a LinearComponent to that many feature maps + BatchNorm, and a PermuteComponent interleaves
+    # them with the features (combine-feature-maps-layer) instead of being appended to the first affine's input
+    conv_ivector_maps: int = 0
 
     @property
     def num_pdfs(self) -> int:
@@ -414,9 +433,12 @@ def _w_nonlinear(w: KaldiWriter, typ: str, dim: int) -> None:
     w.token(f"</{typ}>")
 
 
-def _w_batchnorm(w: KaldiWriter, mean: np.ndarray, var: np.ndarray, eps: float = 1e-3, target_rms: float = 1.0) -> None:
-    dim = mean.shape[0]
-    w.token("<BatchNormComponent>").token("<Dim>").i32(dim).token("<BlockDim>").i32(dim)
+def _w_batchnorm(w: KaldiWriter, mean: np.ndarray, var: np.ndarray, eps: float = 1e-3, target_rms: float = 1.0,
+                 dim: Optional[int] = None) -> None:
+    """dim: the component's width where it is a multiple of the statistics' (block-dim = their length: one per filter)."""
+    block = mean.shape[0]
+    dim = block if dim is None else dim
+    w.token("<BatchNormComponent>").token("<Dim>").i32(dim).token("<BlockDim>").i32(block)
     w.token("<Epsilon>").f32(eps).token("<TargetRms>").f32(target_rms).token("<TestMode>").boolean(False)
     w.token("<Count>").f32(1000.0).token("<StatsMean>").vector(mean).token("<StatsVar>").vector(var)
     w.token("</BatchNormComponent>")
@@ -431,6 +453,45 @@ def _w_tdnn(w: KaldiWriter, offsets: Sequence[int], W: np.ndarray, b: Optional[n
     w.token("<NumSamplesHistory>").f32(2000.0).token("<AlphaInOut>").f32(4.0).f32(4.0)
     w.token("<RankInOut>").i32(20).i32(80)
     w.token("</TdnnComponent>")
+
+
+def conv_layer_offsets(layer: Dict[str, object]) -> List[Tuple[int, int]]:
+    """The sorted (time, height) offset pairs of a ModelSpec.conv_layers entry."""
+    if "offsets" in layer:
+        return sorted((int(t), int(h)) for t, h in layer["offsets"])
+    return sorted((int(t), int(h)) for t in layer["time_offsets"] for h in layer["height_offsets"])
+
+
+def _w_conv(w: KaldiWriter, filters_in: int, filters_out: int, height_in: int, height_out: int, sub: int,
+            offsets: Sequence[Tuple[int, int]], required: Sequence[int], W: np.ndarray, b: np.ndarray) -> None:
+    # nnet-convolutional-component.cc:424-450 with ConvolutionModel::Write (convolution.cc:225-249)
+    _updatable_open(w, "TimeHeightConvolutionComponent")
+    w.token("<Model>").token("<ConvolutionModel>")
+    w.token("<NumFiltersIn>").i32(filters_in).token("<NumFiltersOut>").i32(filters_out)
+    w.token("<HeightIn>").i32(height_in).token("<HeightOut>").i32(height_out).token("<HeightSubsampleOut>").i32(sub)
+    w.token("<Offsets>").int_pair_vector(list(offsets))
+    w.token("<RequiredTimeOffsets>").int_vector(list(required))
+    w.token("</ConvolutionModel>")
+    w.token("<LinearParams>").matrix(W).token("<BiasParams>").vector(b)
+    w.token("<MaxMemoryMb>").f32(200.0).token("<UseNaturalGradient>").boolean(True)
+    w.token("<NumMinibatchesHistory>").f32(4.0).token("<AlphaInOut>").f32(4.0).f32(4.0)
+    w.token("<RankInOut>").i32(80).i32(80)
+    w.token("</TimeHeightConvolutionComponent>")
+
+
+def _w_permute(w: KaldiWriter, column_map: Sequence[int]) -> None:
+    # nnet-simple-component.cc:4056-4064
+    w.token("<PermuteComponent>").token("<ColumnMap>").int_vector(list(column_map)).token("</PermuteComponent>")
+
+
+def combine_feature_maps(height: int, filters1: int, filters2: int) -> List[int]:
+    """combine-feature-maps-layer's column map: the input is Append(a, b), a = height x filters1 and b = height x filters2 (filter
+    fastest); output column h * (filters1 + filters2) + f takes a's filter f, or b's filter f - filters1, of height h."""
+    out = []
+    for h in range(height):
+        out += [h * filters1 + f for f in range(filters1)]
+        out += [height * filters1 + h * filters2 + f for f in range(filters2)]
+    return out
 
 
 def _w_linear(w: KaldiWriter, W: np.ndarray) -> None:
@@ -476,14 +537,59 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
     def randb(o, s=0.1):
         return (rng.standard_normal(o) * s).astype(np.float32)
 
+    # the convolutional front end, if any: [idct + batchnorm] [iVector maps, combined] conv-relu-batchnorm layers
+    front, front_dim, scaled, iv_direct = "input", C, False, D > 0
+    if spec.conv_layers:
+        height, filters = C, 1
+        if spec.conv_idct:
+            Wi = randw(C, C) * np.float32(spec.input_scale)
+            comps.append(("idct", lambda w, W=Wi, b=np.zeros(C, np.float32): _w_fixed_affine(w, W, b)))
+            cfg.append("component-node name=idct component=idct input=input")
+            mean, var = (0.1 * rng.standard_normal(C)).astype(np.float32), rng.uniform(0.5, 1.5, C).astype(np.float32)
+            comps.append(("idct.batchnorm", lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+            cfg.append("component-node name=idct.batchnorm component=idct.batchnorm input=idct")
+            front, scaled = "idct.batchnorm", True
+        if spec.conv_ivector_maps > 0:
+            if D <= 0:
+                raise ValueError("conv_ivector_maps needs an iVector extractor")
+            M = spec.conv_ivector_maps
+            comps.append(("ivector-linear", lambda w, W=randw(M * height, D): _w_linear(w, W)))
+            cfg.append("component-node name=ivector-linear component=ivector-linear input=ReplaceIndex(ivector, t, 0)")
+            mean, var = (0.1 * rng.standard_normal(M * height)).astype(np.float32), rng.uniform(0.5, 1.5, M * height).astype(np.float32)
+            comps.append(("ivector-batchnorm", lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+            cfg.append("component-node name=ivector-batchnorm component=ivector-batchnorm input=ivector-linear")
+            comps.append(("combine-inputs", lambda w, cm=combine_feature_maps(height, filters, M): _w_permute(w, cm)))
+            cfg.append(f"component-node name=combine-inputs component=combine-inputs input=Append({front}, ivector-batchnorm)")
+            front, filters, iv_direct = "combine-inputs", filters + M, False
+        for ci, layer in enumerate(spec.conv_layers, start=1):
+            offs = conv_layer_offsets(layer)
+            f_out, h_out, sub = int(layer["filters"]), int(layer["height_out"]), int(layer.get("sub", 1))
+            required = sorted(set(int(t) for t in layer.get("required_time_offsets", [t for t, _ in offs])))
+            Wc, bc = randw(f_out, len(offs) * filters) * np.float32(layer.get("gain", 1.0)), randb(f_out)
+            if not scaled:
+                Wc, scaled = Wc * np.float32(spec.input_scale), True
+            comps.append((f"cnn{ci}.conv", lambda w, a=(filters, f_out, height, h_out, sub, offs, required, Wc, bc): _w_conv(w, *a)))
+            cfg.append(f"component-node name=cnn{ci}.conv component=cnn{ci}.conv input={front}")
+            comps.append((f"cnn{ci}.relu", lambda w, d=f_out * h_out: _w_nonlinear(w, "RectifiedLinearComponent", d)))
+            cfg.append(f"component-node name=cnn{ci}.relu component=cnn{ci}.relu input=cnn{ci}.conv")
+            mean, var = (0.4 + 0.1 * rng.standard_normal(f_out)).astype(np.float32), rng.uniform(0.5, 1.5, f_out).astype(np.float32)
+            comps.append((f"cnn{ci}.batchnorm", lambda w, m=mean, v=var, d=f_out * h_out: _w_batchnorm(w, m, v, dim=d)))
+            cfg.append(f"component-node name=cnn{ci}.batchnorm component=cnn{ci}.batchnorm input=cnn{ci}.relu")
+            front, filters, height = f"cnn{ci}.batchnorm", f_out, h_out
+        front_dim = filters * height
+
     # lda
-    lda_in = C * len(spec.lda_offsets) + D
-    parts = [("input" if o == 0 else f"Offset(input, {o})") for o in spec.lda_offsets]
-    if D > 0:
+    lda_in = front_dim * len(spec.lda_offsets) + (D if iv_direct else 0)
+    parts = [(front if o == 0 else f"Offset({front}, {o})") for o in spec.lda_offsets]
+    if iv_direct:
         parts.append("ReplaceIndex(ivector, t, 0)")
     lda_desc = "Append(" + ", ".join(parts) + ")" if len(parts) > 1 else parts[0]
-    Wl, bl = randw(lda_in, lda_in), randb(lda_in)
-    Wl[:, :C * len(spec.lda_offsets)] *= np.float32(spec.input_scale)
+    if spec.conv_layers:      # (not square: the stack's output can be thousands of columns wide)
+        Wl, bl = randw(spec.hidden_dim, lda_in), randb(spec.hidden_dim)
+        lda_in = spec.hidden_dim
+    else:
+        Wl, bl = randw(lda_in, lda_in), randb(lda_in)
+        Wl[:, :C * len(spec.lda_offsets)] *= np.float32(spec.input_scale)
     comps.append(("lda", lambda w, W=Wl, b=bl: _w_fixed_affine(w, W, b)))
     cfg.append(f"component-node name=lda component=lda input={lda_desc}")
     prev, prev_dim = "lda", lda_in
