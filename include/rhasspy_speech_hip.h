@@ -103,7 +103,16 @@ const char *rs_last_error(void);
  * refused with a message.  The network may start with TimeHeightConvolutionComponents (CNN-TDNN recipes) and a PermuteComponent;
  * refused with a message are a convolution whose required time offsets are a proper subset of its time offsets (zero padding in
  * time), one with more than 8 distinct time offsets or 128 output heights, one whose input rows of a frame exceed the kernel's 96 KiB
- * of LDS, recurrent networks, and component types the HIP kernels do not implement.  Parses on the host only;
+ * of LDS, and component types the HIP kernels do not implement.  The network may be recurrent where every cycle is what nnet3's
+ * fast-lstmp-layer / fast-lstm-layer emit (TDNN-LSTM recipes): an affine W_all over Append(x, IfDefined(Offset(r_trunc, -d))), an
+ * LstmNonlinearityComponent over Append(W_all, IfDefined(Offset(c_trunc, -d)) [, a 3-column DropoutMaskComponent node: all ones]),
+ * optionally the projection W_rp over m, and one BackpropTruncationComponent (its <Scale> is honoured, here and anywhere else) whose
+ * dim-ranges are the state; one delay d for both connections, 1 <= d <= 8, towards the past.  Limits: cell dim <= 2048, recurrent +
+ * non-recurrent projection dim <= 4096, and 64 * (2 * recurrent input dim + cell dim [with a projection] + 12) bytes <= 144 KiB of
+ * LDS.  Any other cycle -- lstmp-layer's Sigmoid / Tanh / ElementwiseProduct cell, lstmb-layer, GRU layers, a positive delay, two
+ * delays in one block, a block that reads another block's state at a future time -- is refused with the node and the reason.  The
+ * rand() calls of a recurrent compilation are not replayed, so such a model loads only with --dither=0 in its mfcc.conf / fbank.conf
+ * (rs_nnet3_setup below: certain = 0).  Parses on the host only;
  * the device copy is made on first use or by rs_model_to_device().  Immutable afterwards, shareable
  * between threads. */
 int rs_model_load_files(const char *final_mdl, const char *hclg_fst, const char *online_conf,
@@ -118,7 +127,10 @@ void rs_model_free(rs_model *model);
  * ceps= dither=`, or for a filterbank model `fbank: win= shift= padded= mel_bins= dim= use_energy= htk_compat= use_log= use_power=
  * dither=` (dim = mel_bins + use_energy, the width of a feature row).  After the `op:` lines comes one `conv:` line per convolution
  * (none for a model without one): name, filters in->out, heights in->out, height subsampling, offsets, distinct time offsets, k, the
- * kernel instantiation chosen at load, frames / pixel tiles / LDS bytes per workgroup, filter chunks, grid.  Two lines are state, not structure: `layer_gemm:` and
+ * kernel instantiation chosen at load, frames / pixel tiles / LDS bytes per workgroup, filter chunks, grid.  Then one `lstm:` line per
+ * recurrent block: name, input dim, cell / recurrent / non-recurrent dims (0 / 0: no projection), delay, the truncation component's
+ * scale, dropout_mask=0|1, the kernel instantiation, chains (rows) per workgroup, LDS bytes, the split of W_all's columns into
+ * feed-forward + recurrent, cell and projection tiles, the grid rule.  Two lines are state, not structure: `layer_gemm:` and
  *   arenas: device blocks=B bytes=N allocations=A; host blocks=B bytes=N allocations=A
  * summed over the model's decode contexts: the blocks and bytes their per-call arenas hold now, and the hipMalloc / hipHostMalloc
  * calls they have made since the model was loaded.  `allocations` stands still once every context has seen its largest call twice.
@@ -414,7 +426,10 @@ int rs_bind_host_thread(int32_t device_id);
 
 /* Parity taps (only with opts.keep_intermediates): kind 0 = nnet input features (T x C), 1 = iVector
  * (n x D_iv: one row offline, one row per nnet chunk for streams), 2 = log-likelihoods (T x P); 3 + k = the output of the
- * model's k-th convolution (T x heights * filters, ReLU and BatchNorm applied; batch calls only). */
+ * model's k-th convolution (T x heights * filters, ReLU and BatchNorm applied; batch calls only); 64 + k = the output rows of the
+ * model's k-th recurrent block, what the layers above it read (T x (recurrent + non-recurrent) dim: rp, before any BatchNorm; or
+ * T x cell dim: m, without a projection; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
+ * hold anything). */
 int rs_result_matrix(const rs_result *r, int32_t utt, int32_t kind, const float **data, int32_t *rows, int32_t *cols);
 /* Decoder work counters of one utterance, for the algorithmic-bytes figure of SURVEY.md section 8(d):
  * out[0] = tokens expanded, [1] = arcs examined, [2] = token insertions (FindOrAddToken calls),
@@ -474,7 +489,9 @@ int rs_fst_tool(const char *tool, const char *in1, const char *in2, const char *
  * utterance, so the noise of frame t is a constant of the model).  rs_model_load replays both; these two entry points expose
  * the replay for inspection and tests:
  *   rs_nnet3_setup: *rand_calls = number of rand() calls before the first frame for `final_mdl` under --frames-per-chunk;
- *     *certain = 0 when the count assumes a looped compilation the reference may have to retry (rs_model_load refuses such a
+ *     *certain = 0 when the count assumes a looped compilation the reference may have to retry, and for every recurrent network
+ *     (its compilation has another step structure, whose draws are not replayed; the context search, the collapser and the
+ *     five-request walk run all the same and give the reference's context and collapsed network) (rs_model_load refuses such a
  *     model unless its mfcc.conf / fbank.conf says --dither=0); collapsed_config (may be NULL) receives the config lines of the collapsed
  *     network, '\n'-separated and NUL-terminated, truncated to buf_len.
  *   rs_dither_noise: out[(t - t0) * window + i] = the value Dither() adds, for --dither=1, to sample i of frame t in a process

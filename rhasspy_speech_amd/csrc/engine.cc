@@ -275,6 +275,10 @@ Model::Model(const std::string &final_mdl, const std::string &hclg, const std::s
   conv_plans_.assign(am_.nnet.ops.size(), ConvLaunchPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++)
     if (am_.nnet.ops[i].kind == LayerOp::kConv) conv_plans_[i] = PlanConv(am_.nnet.ops[i].conv, am_.nnet.ops[i].name);
+  // ... and the recurrent blocks: a cell or projection dim beyond the kernel's limits fails the load (lstm_plan.h)
+  lstm_plans_.assign(am_.nnet.ops.size(), LstmLaunchPlan());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++)
+    if (am_.nnet.ops[i].kind == LayerOp::kLstm) lstm_plans_[i] = PlanLstm(am_.nnet.ops[i].lstm, am_.nnet.ops[i].name);
 }
 
 // rs_decode_opts.prune_output_pdfs: the search looks log-likelihoods up by the pdf of the arc it crosses
@@ -416,7 +420,7 @@ template <typename T> T *Model::Upload(const std::vector<T> &v) { return static_
 
 void Model::BuildGemmPlan(const LayerOp &op, GemmPlan *plan) {
   plan->op = &op;
-  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather) {      // (their own operands: ToDevice; here the bias and the fused stages)
+  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm) {      // (their own operands: ToDevice; here the bias and the fused stages)
     plan->d_bias = op.bias.empty() ? nullptr : Upload(op.bias);
     plan->d_stage.clear();
     for (auto &st : op.stages) {
@@ -726,6 +730,17 @@ void Model::ToDevice() {
       conv_dev_[i].tab1 = Upload(op.gather_col);
     }
   }
+  lstm_dev_.assign(am_.nnet.ops.size(), LstmOperands());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++) {
+    const LayerOp &op = am_.nnet.ops[i];
+    if (op.kind != LayerOp::kLstm) continue;
+    std::vector<float> wr_t, wrp_t;
+    LstmWeightImages(op.lstm, lstm_plans_[i], &wr_t, &wrp_t);
+    lstm_dev_[i].wr_t = Upload(wr_t);
+    lstm_dev_[i].wrp_t = Upload(wrp_t);
+    lstm_dev_[i].b_rp = Upload(op.lstm.b_rp);
+    lstm_dev_[i].params = Upload(op.lstm.params.d);
+  }
   {
     // operand images: a buffer gets one when a split-bf16 layer reads it through GemmKernelB3I; it is still stored as plain
     // floats when anything else reads it (the nnet's input / output, an elementwise op, a layer on another kernel)
@@ -905,7 +920,7 @@ std::string Model::Describe() const {
      << " left_context=" << n.left_context << " right_context=" << n.right_context << " priors=" << n.priors.size()
      << " components=" << n.components.size() << " ops=" << n.ops.size() << "\n";
   for (auto &op : n.ops) {
-    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather"};
+    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm"};
     os << "op: " << kinds[op.kind] << " " << op.name << " out_dim=" << op.out_dim;
     if (op.kind == LayerOp::kGemm) {
       os << " k=" << op.W.cols << " segs=";
@@ -920,6 +935,8 @@ std::string Model::Describe() const {
   }
   for (size_t i = 0; i < n.ops.size(); i++)      // (one line per convolution: its geometry and what the planner chose for it at load)
     if (n.ops[i].kind == LayerOp::kConv) os << "conv: " << DescribeConv(n.ops[i].name, n.ops[i].conv, conv_plans_[i]) << "\n";
+  for (size_t i = 0; i < n.ops.size(); i++)      // (one line per recurrent block)
+    if (n.ops[i].kind == LayerOp::kLstm) os << "lstm: " << DescribeLstm(n.ops[i].name, n.ops[i].lstm, lstm_plans_[i]) << "\n";
   os << "transition_model: tids=" << am_.trans.id2pdf.size() - 1 << " pdfs=" << am_.trans.num_pdfs << "\n";
   if (pruned_from_) os << "output layer: pruned to the " << am_.nnet.output_dim << " of " << pruned_from_ << " pdfs that occur on HCLG arcs\n";
   os << "hclg: states=" << hclg_.num_states() << " arcs=" << hclg_.arcs.size() << " start=" << hclg_.start << "\n";
@@ -1298,7 +1315,7 @@ GemmDev Model::MakeGemm(const GemmPlan &pl, const std::vector<float *> &src, con
 // caller supplies that row list (row_maps), else on all rows.
 void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &buf_ld, float *d_ivec, int ld_i, const int *d_row_ivec, int rows,
                     const RowMaps &row_maps, int share, size_t op_begin, size_t op_end, hipStream_t s,
-                    const std::vector<ActImage> *imgs) const {
+                    const std::vector<ActImage> *imgs, const LstmCall *lstm) const {
   const Nnet &nn = am_.nnet;
   const bool images_on = imgs != nullptr && GemmImagesEnabled() && !tls_exact_gemm && tls_gemm_ovf_dev != nullptr;
   if (op_begin == 0 && !tls_exact_gemm) ZeroGuards(bufp, buf_ld, rows, images_on ? imgs : nullptr, s);
@@ -1348,6 +1365,39 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       } else {
         LaunchConv(d, rows, s);
       }
+    } else if (op.kind == LayerOp::kLstm) {
+      if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
+      const LstmBlock &k = op.lstm;
+      const BufferInfo &ob = nn.bufs[op.out_buf];
+      const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride);
+      const int outs[3] = {k.cm_buf, k.st_buf, k.rp_buf};
+      // (a stream advance evaluates the layers above on all rows of its segments: the rows the walk does not reach -- before the
+      // re-entry point, behind the last row its readers need -- hold zeros, not what the arena held)
+      if (!rm)
+        for (int b : outs)
+          if (b >= 0) RS_HIP(hipMemsetAsync(bufp[b], 0, sizeof(float) * (size_t)rows * buf_ld[b], s));
+      LstmDev d;
+      std::memset(&d, 0, sizeof(d));
+      d.pre = bufp[k.pre_buf]; d.ld_pre = buf_ld[k.pre_buf];
+      d.cm = bufp[k.cm_buf]; d.ld_cm = buf_ld[k.cm_buf];
+      d.st = bufp[k.st_buf]; d.ld_st = buf_ld[k.st_buf];
+      if (k.rp_buf >= 0) { d.rp = bufp[k.rp_buf]; d.ld_rp = buf_ld[k.rp_buf]; }
+      d.wr_t = lstm_dev_[i].wr_t; d.wrp_t = lstm_dev_[i].wrp_t; d.b_rp = lstm_dev_[i].b_rp; d.params = lstm_dev_[i].params;
+      d.cell = k.cell; d.rec_dim = k.RecDim(); d.out_dim = k.proj() ? k.rec + k.nonrec : 0; d.rec = k.rec;
+      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale;
+      d.n_utts = lstm->n_utts; d.L = L_; d.lext = ob.lext; d.rext = ob.rext;
+      d.num_frames = lstm->num_frames; d.row_base = lstm->row_base;
+      d.t0 = lstm->t0; d.slot = lstm->slot; d.lext_cont = k.need_lext;
+      d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
+      if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
+      d.plan = lstm_plans_[i];
+      LaunchLstm(d, s);
+      // operand images of what the split-fp16 layers above read: the rows the walk wrote
+      if (images_on)
+        for (int b : outs)
+          if (b >= 0 && (*imgs)[b].base)
+            LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
+      continue;
     } else if (op.kind == LayerOp::kGather) {
       GatherDev d;
       std::memset(&d, 0, sizeof(d));
@@ -2022,6 +2072,17 @@ void Model::BatchIntermediates(const BatchCall &b, const float *ll, int ll_ld, U
       RS_HIP(hipMemcpy2D(ur.conv_out.back().data(), sizeof(float) * op.out_dim, b.bufp[op.out_buf] + ((size_t)b.row_base[u] + L_) * ld, sizeof(float) * ld,
                          sizeof(float) * op.out_dim, T, hipMemcpyDeviceToHost));
     }
+    ur.lstm_out.clear();
+    ur.lstm_dim.clear();
+    for (auto &op : nn.ops) {
+      if (op.kind != LayerOp::kLstm) continue;
+      const LstmBlock &k = op.lstm;
+      const int buf = k.proj() ? k.rp_buf : k.cm_buf, col = k.proj() ? 0 : k.cell, dim = k.OutDim(), ld = b.buf_ld[buf];
+      ur.lstm_dim.push_back(dim);
+      ur.lstm_out.emplace_back((size_t)T * dim);
+      RS_HIP(hipMemcpy2D(ur.lstm_out.back().data(), sizeof(float) * dim, b.bufp[buf] + ((size_t)b.row_base[u] + L_) * ld + col, sizeof(float) * ld,
+                         sizeof(float) * dim, T, hipMemcpyDeviceToHost));
+    }
     if (has_iv) {
       ur.ivector.resize((size_t)ur.ivec_rows * Di);
       RS_HIP(hipMemcpy2D(ur.ivector.data(), sizeof(float) * Di, b.d_ivec + (size_t)ivrow_base[u] * ld_i, sizeof(float) * ld_i,
@@ -2091,9 +2152,11 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
   const int ld_i = RoundUp(std::max(fc_.ie.present ? fc_.ie.ivector_dim() : 0, 1), 4);
   tm.Mark();
   // ---- acoustic model
+  LstmCall lstm_call;
+  lstm_call.n_utts = n_utts; lstm_call.num_frames = b.g.d_num_frames; lstm_call.row_base = b.g.d_row_base;
   stage_begin(1);
   if (pipelined) {
-    RunNnet(b.bufp, b.buf_ld, b.d_ivec, ld_i, b.d_row_ivec, b.rows, b.row_maps, cx.active_groups, 0, nn.ops.size() - 1, s, &b.imgs);
+    RunNnet(b.bufp, b.buf_ld, b.d_ivec, ld_i, b.d_row_ivec, b.rows, b.row_maps, cx.active_groups, 0, nn.ops.size() - 1, s, &b.imgs, &lstm_call);
     // slab k: output layer on the main stream, then the search of that slab on the decode stream
     const size_t i = nn.ops.size() - 1;
     GemmDev gd = MakeGemm(gemm_plans_[i], b.bufp, b.buf_ld, b.d_ivec, ld_i, b.bufp[nn.ops[i].out_buf], b.buf_ld[nn.ops[i].out_buf], cx.active_groups, &b.imgs,
@@ -2110,7 +2173,7 @@ void Model::DecodeGroup(DecodeContext &cx, int gi, const int16_t *d_pcm, const i
     RS_HIP(hipEventRecord(cx.slab_ev[8], cx.stream_dec));
   } else {
     LdsPoison(s);
-    RunNnet(b.bufp, b.buf_ld, b.d_ivec, ld_i, b.d_row_ivec, b.rows, b.row_maps, cx.active_groups, 0, nn.ops.size(), s, &b.imgs);
+    RunNnet(b.bufp, b.buf_ld, b.d_ivec, ld_i, b.d_row_ivec, b.rows, b.row_maps, cx.active_groups, 0, nn.ops.size(), s, &b.imgs, &lstm_call);
   }
   stage_end(1);
   float *ll = b.bufp[nn.output_buf];

@@ -67,6 +67,9 @@ struct UttResult {
   // fused stages applied; under --frame-subsampling-factor only the rows the op was evaluated on hold anything)
   std::vector<std::vector<float>> conv_out;
   std::vector<int> conv_dim;
+  // ... per recurrent block, in op order, the rows the layers above read (rp, or m without a projection: T x dim)
+  std::vector<std::vector<float>> lstm_out;
+  std::vector<int> lstm_dim;
   int feat_dim = 0, ivec_rows = 0, ivec_dim = 0, num_pdfs = 0;
   std::shared_ptr<CompactLat> clat;              // emit_lattice only
 };
@@ -94,6 +97,18 @@ struct GemmPlan {        // one LayerOp of kind kGemm, uploaded
 struct ConvOperands {     // one LayerOp of kind kConv (W in the kernel's order, the k -> LDS offset table) or kGather (part, column per output column)
   float *wt = nullptr;
   int *tab0 = nullptr, *tab1 = nullptr;
+};
+
+struct LstmOperands {     // one LayerOp of kind kLstm: LstmWeightImages' two matrices, the projection's bias, the nonlinearity's <Params>
+  float *wr_t = nullptr, *wrp_t = nullptr, *b_rp = nullptr, *params = nullptr;
+};
+// The utterances of the call a recurrent block is walked for (RunNnet): frames and first row of each, in the layout of kernels.h;
+// for a stream advance also the frames each stream had before it and its slot, and the pool's parked state per kLstm op
+struct LstmCall {
+  int n_utts = 0;
+  const int *num_frames = nullptr, *row_base = nullptr;
+  const int *t0 = nullptr, *slot = nullptr;
+  const std::vector<float *> *rings = nullptr;      // indexed like am_.nnet.ops
 };
 
 struct LatArcBuffer { void *d = nullptr; size_t cap = 0; };      // capacity in LatArc records
@@ -228,7 +243,7 @@ class Model {
                       float lat_scale, hipStream_t s, UttResult *out_utts, float *timings);
   void RunNnet(const std::vector<float *> &bufp, const std::vector<int> &buf_ld, float *d_ivec, int ld_i, const int *d_row_ivec, int rows,
                const RowMaps &row_maps, int share, size_t op_begin, size_t op_end, hipStream_t s,
-               const std::vector<ActImage> *imgs = nullptr) const;
+               const std::vector<ActImage> *imgs = nullptr, const LstmCall *lstm = nullptr) const;
 
   // keep_intermediates only: the layer GEMMs the most recent decode call or stream advance launched, one line per distinct launch
   // (Describe: "gemm_launch:").  A call opens a generation (GemmRecordBegin) and every thread that enqueues for it carries the
@@ -366,6 +381,8 @@ class Model {
   std::vector<GemmPlan> gemm_plans_;  // indexed like am_.nnet.ops (unused entries for eltwise ops)
   std::vector<ConvLaunchPlan> conv_plans_;   // indexed like am_.nnet.ops: what the planner chose at load for the convolutions
   std::vector<ConvOperands> conv_dev_;       // indexed like am_.nnet.ops: the convolutions' and gathers' device operands
+  std::vector<LstmLaunchPlan> lstm_plans_;   // indexed like am_.nnet.ops: what the planner chose at load for the recurrent blocks
+  std::vector<LstmOperands> lstm_dev_;       // indexed like am_.nnet.ops: their device operands
   float *d_log_priors_ = nullptr;
   HclgDev hclg_dev_{};
   RevGraphDev rev_dev_{};

@@ -9,6 +9,7 @@
 
 #include "conv_plan.h"
 #include "gemm_launch.h"
+#include "lstm_plan.h"
 #include "search_plan.h"
 
 namespace rs {
@@ -171,6 +172,8 @@ int DeviceNumCu();      // compute units of the current device, asked once per p
 // TimeHeightConvolutionComponent / PermuteComponent (nnet_conv.hip; the descriptors and the load-time plan: conv_plan.h)
 void LaunchConv(const ConvDev &d, int rows, hipStream_t s);
 void LaunchGather(const GatherDev &d, int rows, hipStream_t s);
+// The walk of a recurrent block over the chains of a call (nnet_lstm.hip; the descriptor and the load-time plan: lstm_plan.h)
+void LaunchLstm(const LstmDev &d, hipStream_t s);
 
 struct SumTermDev { const float *src; int ld, col0, row_off; float scale; };
 struct EltwiseDev {

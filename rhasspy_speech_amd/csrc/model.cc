@@ -781,6 +781,7 @@ struct DescParser {
         for (auto &pt : out) for (auto &tm : pt.terms) { tm.const_t = true; tm.offset = 0; }
       } else if (id == "IfDefined") {
         out = Parse();
+        for (auto &pt : out) for (auto &tm : pt.terms) tm.optional = true;
       } else {
         Fail("nnet3 descriptor: unsupported expression '" + id + "' in: " + s);
       }
@@ -832,6 +833,12 @@ int ComponentOutputDim(const Component &c, const std::string &name) {
       c.type == "TdnnComponent")
     return rows("<LinearParams>");
   if (c.type == "LinearComponent") return rows("<Params>");
+  if (c.type == "LstmNonlinearityComponent") {      // (nnet-combined-component.cc:973-977: [c | m])
+    auto it = c.m.find("<Params>");
+    if (it == c.m.end() || it->second.rows != 3 || it->second.cols <= 0) Fail("nnet3: LstmNonlinearityComponent '" + name + "' needs a 3-row <Params> matrix");
+    return 2 * it->second.cols;
+  }
+  if ((c.type == "DropoutMaskComponent" || c.type == "ElementwiseProductComponent") && c.i.count("<OutputDim>")) return c.Int("<OutputDim>");
   if (c.type == "TimeHeightConvolutionComponent") { const ConvGeom g = ReadConvGeom(c, name); return g.filters_out * g.height_out; }
   if (c.type == "PermuteComponent") {
     auto it = c.iv.find("<ColumnMap>");
@@ -874,6 +881,8 @@ void ReadNnetComponents(KaldiReader &r, std::vector<std::string> *names, std::ve
   r.ExpectToken("</Nnet3>");
 }
 
+namespace { void CheckRecurrence(const Nnet &net); }
+
 void Nnet::Read(KaldiReader &r, int frames_per_chunk, int extra_left_context_initial, int frame_subsampling_factor) {
   r.ExpectToken("<Nnet3>");
   std::string line = r.ReadLine();
@@ -888,6 +897,12 @@ void Nnet::Read(KaldiReader &r, int frames_per_chunk, int extra_left_context_ini
   ReadNnetComponents(r, &component_names, &components);
   for (size_t c = 0; c < components.size(); c++)      // (checked before the set-up walks the network with their offsets)
     if (components[c].type == "TimeHeightConvolutionComponent") (void)ReadConvGeom(components[c], component_names[c]);
+  // The network as written, and its cycles: a recurrence that is not a fast-lstm(p) block is refused here, with its node and the
+  // reason, before the set-up below walks the network.  (Lines this parser does not take may belong to orphan nodes the set-up
+  // drops: then the check waits for Compile, which sees the network the set-up leaves.)
+  bool parsed = true;
+  try { ParseNodes(cfg); } catch (const Error &) { parsed = false; }
+  if (parsed) CheckRecurrence(*this);
   {
     // CollapseModel + the rand() calls of the reference's set-up (nnet3_setup.h); RS_NO_COLLAPSE=1 keeps the layers as
     // written (A/B of the rounding difference; the rand() count is that of the reference either way)
@@ -902,6 +917,11 @@ void Nnet::Read(KaldiReader &r, int frames_per_chunk, int extra_left_context_ini
     setup_rand_uncertain_why = su.uncertain_why;
     if (!keep_layers) cfg = su.config;
   }
+  ParseNodes(cfg);
+}
+
+void Nnet::ParseNodes(const std::vector<std::string> &cfg) {
+  nodes.clear();
   // first pass: create nodes (names + dims), second pass: descriptors
   std::vector<std::map<std::string, std::string>> kvs;
   std::vector<std::string> firsts;
@@ -963,14 +983,23 @@ bool IsAffineLike(const std::string &t) {
 }
 bool IsIdentity(const Component &c) {
   return c.type == "NoOpComponent" || c.type == "DropoutComponent" || c.type == "GeneralDropoutComponent" ||
-         c.type == "DropoutMaskComponent" || c.type == "SpecAugmentTimeMaskComponent" || c.type == "ClipGradientComponent" ||
-         c.type == "BackpropTruncationComponent";
+         c.type == "SpecAugmentTimeMaskComponent" || c.type == "ClipGradientComponent";
+}
+// BackpropTruncationComponent::Propagate (nnet-general-component.cc:1094-1102): out = in, then Scale(scale_) unless it is 1
+float TruncationScale(const Component &c) {
+  auto it = c.f.find("<Scale>");
+  return it == c.f.end() || it->second.empty() ? 1.0f : (float)it->second[0];
 }
 
 // Elementwise component -> stages (empty = identity).  false if the type is not elementwise.
 bool EltStagesFor(const Component &c, const std::string &name, std::vector<EltStage> *st) {
   st->clear();
   if (IsIdentity(c)) return true;
+  if (c.type == "BackpropTruncationComponent") {
+    const float scale = TruncationScale(c);
+    if (scale != 1.0f) { EltStage s; s.kind = EltStage::kScale; s.alpha = scale; st->push_back(s); }
+    return true;
+  }
   if (c.type == "RectifiedLinearComponent") { EltStage s; s.kind = EltStage::kRelu; st->push_back(s); return true; }
   if (c.type == "LogSoftmaxComponent") { EltStage s; s.kind = EltStage::kLogSoftmax; st->push_back(s); return true; }
   if (c.type == "BatchNormComponent") {
@@ -1036,19 +1065,215 @@ bool EltStagesFor(const Component &c, const std::string &name, std::vector<EltSt
   }
   return false;
 }
+
+// The nodes of one recurrent block (xconfig/lstm.py: XconfigFastLstmpLayer :1120-1198, XconfigFastLstmLayer :706-753)
+struct BlockNodes {
+  int wa = -1, nl = -1, tr = -1, sc = -1, sr = -1;   // W_all, lstm_nonlin, cr_trunc / cm_trunc, c_trunc, r_trunc / m_trunc
+  int c = -1, m = -1, rp = -1, r = -1;               // with a projection: the dim-ranges c and m, the affine rp, the dim-range r
+  int dm = -1;                                       // the DropoutMaskComponent node (use-dropout=true); not part of the cycle
+  int delay = 0, cell = 0, rec_dim = 0;              // rec_dim: width of the recurrent input (r, or m without a projection)
+  int need_lext = 0;
+  std::vector<int> members;                          // the cycle's nodes
+  std::vector<DescPart> x_parts;                     // W_all's input without its recurrent part
+};
+
+// Every cycle of the nodes `out_node` depends on has to be such a block, and nothing else: anything else is refused with the
+// node and the reason.
+void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, std::vector<int> *block_of) {
+  const std::vector<NnetNode> &nodes = net.nodes;
+  const int N = (int)nodes.size();
+  auto comp_type = [&](int n) -> std::string { return nodes[n].kind == NnetNode::kComponent ? net.components[nodes[n].component].type : std::string(); };
+  auto deps = [&](int n, std::vector<int> *out) {
+    out->clear();
+    const NnetNode &nd = nodes[n];
+    if (comp_type(n) == "DropoutMaskComponent") return;      // (its input is a don't-care: GetInputIndexes asks for nothing)
+    if (nd.kind == NnetNode::kDimRange) out->push_back(nd.range_node);
+    for (auto &p : nd.input.parts) for (auto &t : p.terms) out->push_back(t.node);
+  };
+  // strongly connected components (Tarjan, iterative over an explicit stack) of what the output depends on
+  std::vector<int> index(N, -1), low(N, 0), comp(N, -1), stack;
+  std::vector<char> on_stack(N, 0);
+  int counter = 0, ncomp = 0;
+  std::vector<std::vector<int>> sccs;
+  struct Frame { int n; std::vector<int> d; size_t i; };
+  std::vector<Frame> call;
+  auto push = [&](int n) {
+    index[n] = low[n] = counter++;
+    stack.push_back(n);
+    on_stack[n] = 1;
+    Frame f{n, {}, 0};
+    deps(n, &f.d);
+    call.push_back(std::move(f));
+  };
+  push(out_node);
+  while (!call.empty()) {
+    Frame &f = call.back();
+    if (f.i < f.d.size()) {
+      const int m = f.d[f.i++];
+      if (index[m] < 0) push(m);
+      else if (on_stack[m]) low[f.n] = std::min(low[f.n], index[m]);
+      continue;
+    }
+    const int n = f.n;
+    if (low[n] == index[n]) {
+      std::vector<int> scc;
+      for (;;) {
+        const int m = stack.back();
+        stack.pop_back();
+        on_stack[m] = 0;
+        comp[m] = ncomp;
+        scc.push_back(m);
+        if (m == n) break;
+      }
+      ncomp++;
+      std::sort(scc.begin(), scc.end());
+      sccs.push_back(std::move(scc));
+    }
+    call.pop_back();
+    if (!call.empty()) low[call.back().n] = std::min(low[call.back().n], low[n]);
+  }
+  block_of->assign(N, -1);
+  for (const std::vector<int> &scc : sccs) {
+    if (scc.size() == 1) {
+      std::vector<int> d;
+      deps(scc[0], &d);
+      if (std::find(d.begin(), d.end(), scc[0]) == d.end()) continue;
+    }
+    auto in_scc = [&](int n) { return std::binary_search(scc.begin(), scc.end(), n); };
+    auto refuse = [&](int n, const std::string &why) {
+      Fail("nnet3: recurrent networks are supported only as fast-lstmp-layer / fast-lstm-layer blocks (cycle at node " + nodes[n].name + ": " + why + ")");
+    };
+    BlockNodes b;
+    for (int n : scc)
+      if (comp_type(n) == "LstmNonlinearityComponent") {
+        if (b.nl >= 0) refuse(n, "a second LstmNonlinearityComponent in one cycle");
+        b.nl = n;
+      }
+    if (b.nl < 0)
+      refuse(scc[0], "the cycle has no LstmNonlinearityComponent; lstmp-layer (Sigmoid / Tanh / ElementwiseProduct components), lstmb-layer and GRU layers are not supported");
+    // a recurrent part: one optional term, Offset(x, -d) with 1 <= d <= kLstmMaxDelay
+    auto recurrent_part = [&](int at, const DescPart &p, int *node) {
+      if (p.terms.size() != 1 || p.terms[0].const_t || p.terms[0].scale != 1.0f) refuse(at, "its recurrent input is not IfDefined(Offset(node, -delay))");
+      const DescTerm &t = p.terms[0];
+      if (!t.optional) refuse(at, "its recurrent input " + nodes[t.node].name + " is not inside IfDefined()");
+      if (t.offset > 0) refuse(at, "a positive delay, Offset(" + nodes[t.node].name + ", " + std::to_string(t.offset) + "): a recurrence towards the future is not supported");
+      if (t.offset == 0 || -t.offset > kLstmMaxDelay)
+        refuse(at, "a delay of " + std::to_string(-t.offset) + " frames; the HIP kernel takes 1 to " + std::to_string(kLstmMaxDelay));
+      *node = t.node;
+      return -t.offset;
+    };
+    auto plain_part = [&](const DescPart &p) { return p.terms.size() == 1 && !p.terms[0].const_t && !p.terms[0].optional && p.terms[0].offset == 0 && p.terms[0].scale == 1.0f; };
+    auto range_of = [&](int n, int src, int off, int dim) { return nodes[n].kind == NnetNode::kDimRange && nodes[n].range_node == src && nodes[n].range_offset == off && nodes[n].dim == dim; };
+    // the nonlinearity: Append(W_all, IfDefined(Offset(c_trunc, -d)) [, dropout_mask])
+    const NnetNode &nl = nodes[b.nl];
+    const int C = b.cell = nl.dim / 2;
+    if (nl.input.parts.size() != 2 && nl.input.parts.size() != 3) refuse(b.nl, "its input is not Append(W_all, IfDefined(Offset(c_trunc, -delay)) [, dropout_mask])");
+    if (!plain_part(nl.input.parts[0]) || nl.input.parts[0].dim != 4 * C) refuse(b.nl, "its first input is not a node of dim 4 x cell-dim");
+    b.wa = nl.input.parts[0].terms[0].node;
+    if (nl.input.parts[1].dim != C) refuse(b.nl, "its second input is not of the cell's dim");
+    b.delay = recurrent_part(b.nl, nl.input.parts[1], &b.sc);
+    if (nl.input.parts.size() == 3) {
+      if (!plain_part(nl.input.parts[2]) || nl.input.parts[2].dim != 3 || comp_type(nl.input.parts[2].terms[0].node) != "DropoutMaskComponent")
+        refuse(b.nl, "its third input is not a 3-column DropoutMaskComponent node");
+      b.dm = nl.input.parts[2].terms[0].node;
+      const Component &dm = net.components[nodes[b.dm].component];
+      // test mode (the binaries set it): ones with dropout-proportion 0 or <Continuous>, else 1 - proportion (nnet-general-component.cc:1429-1449)
+      const bool continuous = dm.b.count("<Continuous>") != 0;
+      if (!continuous && dm.f.count("<DropoutProportion>") && dm.f.at("<DropoutProportion>")[0] != 0.0)
+        refuse(b.dm, "a non-continuous dropout mask with dropout-proportion " + std::to_string(dm.f.at("<DropoutProportion>")[0]) + " is not all ones in test mode");
+    }
+    // W_all: Append(x ..., IfDefined(Offset(r_trunc, -d)))
+    const std::string wt = comp_type(b.wa);
+    if (!in_scc(b.wa) || (wt != "AffineComponent" && wt != "NaturalGradientAffineComponent")) refuse(b.wa, "the nonlinearity's first input is not an affine component node of the cycle");
+    const NnetNode &wa = nodes[b.wa];
+    if (wa.input.parts.size() < 2) refuse(b.wa, "its input is not Append(x, IfDefined(Offset(r_trunc, -delay)))");
+    const int d2 = recurrent_part(b.wa, wa.input.parts.back(), &b.sr);
+    if (d2 != b.delay) refuse(b.wa, "two different delays in one block, " + std::to_string(d2) + " and " + std::to_string(b.delay));
+    b.rec_dim = wa.input.parts.back().dim;
+    b.x_parts.assign(wa.input.parts.begin(), wa.input.parts.end() - 1);
+    for (auto &p : b.x_parts) for (auto &t : p.terms) if (in_scc(t.node)) refuse(b.wa, "its feed-forward input reads " + nodes[t.node].name + ", a node of the cycle");
+    // the state: dim-ranges of one BackpropTruncationComponent node
+    if (nodes[b.sc].kind != NnetNode::kDimRange) refuse(b.sc, "the cell state is not a dim-range of a BackpropTruncationComponent node");
+    b.tr = nodes[b.sc].range_node;
+    if (comp_type(b.tr) != "BackpropTruncationComponent") refuse(b.tr, "the state does not come through a BackpropTruncationComponent");
+    if (!range_of(b.sc, b.tr, 0, C) || !range_of(b.sr, b.tr, C, b.rec_dim) || nodes[b.tr].dim != C + b.rec_dim)
+      refuse(b.tr, "c_trunc and r_trunc / m_trunc are not the two column ranges of one BackpropTruncationComponent node");
+    const NnetNode &tr = nodes[b.tr];
+    if (tr.input.parts.size() == 1 && plain_part(tr.input.parts[0]) && tr.input.parts[0].terms[0].node == b.nl) {
+      if (b.rec_dim != C) refuse(b.tr, "without a projection the recurrent input is m, of the cell's dim");
+      b.members = {b.wa, b.nl, b.tr, b.sc, b.sr};
+    } else {
+      if (tr.input.parts.size() != 2 || !plain_part(tr.input.parts[0]) || !plain_part(tr.input.parts[1])) refuse(b.tr, "its input is neither the nonlinearity nor Append(c, r)");
+      b.c = tr.input.parts[0].terms[0].node;
+      b.r = tr.input.parts[1].terms[0].node;
+      if (!range_of(b.c, b.nl, 0, C)) refuse(b.c, "not the first cell-dim columns of the nonlinearity");
+      if (nodes[b.r].kind != NnetNode::kDimRange) refuse(b.r, "not a dim-range of the projection");
+      b.rp = nodes[b.r].range_node;
+      const std::string rt = comp_type(b.rp);
+      if ((rt != "AffineComponent" && rt != "NaturalGradientAffineComponent") || !range_of(b.r, b.rp, 0, b.rec_dim) || nodes[b.rp].dim < b.rec_dim)
+        refuse(b.rp, "r is not the first columns of an affine projection");
+      const NnetNode &rp = nodes[b.rp];
+      if (rp.input.parts.size() != 1 || !plain_part(rp.input.parts[0])) refuse(b.rp, "the projection's input is not m");
+      b.m = rp.input.parts[0].terms[0].node;
+      if (!range_of(b.m, b.nl, C, C)) refuse(b.m, "not the second cell-dim columns of the nonlinearity");
+      if (net.components[rp.component].m.at("<LinearParams>").cols != C) refuse(b.rp, "the projection's input dim is not the cell's");
+      b.members = {b.wa, b.nl, b.tr, b.sc, b.sr, b.c, b.m, b.rp, b.r};
+    }
+    std::sort(b.members.begin(), b.members.end());
+    if (std::adjacent_find(b.members.begin(), b.members.end()) != b.members.end()) refuse(b.nl, "a node has two roles in the block");
+    for (int n : scc) if (!std::binary_search(b.members.begin(), b.members.end(), n)) refuse(n, "the node is part of the cycle but not of such a block");
+    for (int n : b.members) if (!in_scc(n)) refuse(n, "the node is not part of the cycle");
+    const MatF &W = net.components[wa.component].m.at("<LinearParams>");
+    if (W.rows != 4 * C || W.cols <= b.rec_dim) refuse(b.wa, "W_all is " + std::to_string(W.rows) + " x " + std::to_string(W.cols) + ", the block needs 4 x cell-dim rows and more columns than the recurrent input has");
+    if (nl.input.dim != 5 * C + (b.dm >= 0 ? 3 : 0)) refuse(b.nl, "its input dim is not 5 x cell-dim (+ 3 with a dropout mask)");
+    for (int n : b.members) (*block_of)[n] = (int)blocks->size();
+    blocks->push_back(std::move(b));
+  }
+  // a block whose feed-forward input reads another block's state at a future time would need that block's rows before they exist
+  for (const BlockNodes &b : *blocks)
+    for (auto &p : b.x_parts)
+      for (auto &t : p.terms)
+        for (const BlockNodes &o : *blocks)
+          if ((t.node == o.tr || t.node == o.sc || t.node == o.sr) && t.offset > 0)
+            Fail("nnet3: recurrent networks are supported only as fast-lstmp-layer / fast-lstm-layer blocks (cycle at node " + nodes[b.wa].name + ": it reads the state " +
+                 nodes[t.node].name + " of another block at a future time, offset " + std::to_string(t.offset) + ")");
+}
+
+void CheckRecurrence(const Nnet &net) {
+  std::vector<BlockNodes> blocks;
+  std::vector<int> block_of;
+  const int out = net.FindNode("output");
+  if (out >= 0) FindBlocks(net, out, &blocks, &block_of);
+}
 }  // namespace
 
 void Nnet::Compile() {
   int out_node = FindNode("output");
   int in_node = FindNode("input"), iv_node = FindNode("ivector");
   const int N = (int)nodes.size();
-  // reachable set + topological order (DFS post-order)
+  // recurrent blocks: the cycles of the node graph, each of which has to be what fast-lstmp-layer / fast-lstm-layer emit
+  std::vector<BlockNodes> blocks;
+  std::vector<int> block_of(N, -1);
+  FindBlocks(*this, out_node, &blocks, &block_of);
+  recurrent = !blocks.empty();
+  // reachable set + topological order (DFS post-order); a block is one unit, placed where its affine node W_all would be
   std::vector<int> order, state(N, 0);
   std::function<void(int)> visit = [&](int n) {
     if (state[n] == 2) return;
-    if (state[n] == 1) Fail("nnet3: recurrent networks are not supported (cycle at node " + nodes[n].name + ")");
+    if (state[n] == 1) Fail("nnet3: internal error, a cycle outside the recurrent blocks (node " + nodes[n].name + ")");
+    if (block_of[n] >= 0) {
+      const BlockNodes &b = blocks[block_of[n]];
+      for (int m : b.members) state[m] = 1;
+      for (auto &p : b.x_parts) for (auto &t : p.terms) visit(t.node);
+      for (int m : b.members) state[m] = 2;
+      if (b.dm >= 0) state[b.dm] = 2;
+      order.push_back(b.wa);
+      return;
+    }
     state[n] = 1;
     const NnetNode &nd = nodes[n];
+    if (nd.kind == NnetNode::kComponent && components[nd.component].type == "DropoutMaskComponent")
+      Fail("nnet3: DropoutMaskComponent node " + nd.name + " is supported only as the dropout mask of an LstmNonlinearityComponent inside a recurrent block");
     if (nd.kind == NnetNode::kDimRange) visit(nd.range_node);
     for (auto &p : nd.input.parts) for (auto &t : p.terms) visit(t.node);
     state[n] = 2;
@@ -1075,28 +1300,78 @@ void Nnet::Compile() {
     return {0};
   };
   // required extension per node: rows t in [-lext, T+rext)
-  std::vector<int> lext(N, 0), rext(N, 0);
-  for (auto it = order.rbegin(); it != order.rend(); ++it) {
-    int n = *it;
-    const NnetNode &nd = nodes[n];
-    if (nd.kind == NnetNode::kDimRange) {
-      lext[nd.range_node] = std::max(lext[nd.range_node], lext[n]);
-      rext[nd.range_node] = std::max(rext[nd.range_node], rext[n]);
-      continue;
-    }
-    std::vector<int> toffs = tdnn_offsets(nd);
-    for (auto &p : nd.input.parts)
-      for (auto &t : p.terms) {
-        if (t.const_t) continue;
-        for (int o2 : toffs) {
-          int o = t.offset + o2;
-          lext[t.node] = std::max(lext[t.node], lext[n] - o);
-          rext[t.node] = std::max(rext[t.node], rext[n] + o);
-        }
+  // A recurrent block's rows: to the right what its readers need; to the left, where `avail` is given, every row that is
+  // computable from the input the first chunk requests (t >= -left_context) -- the computation graph builder computes every
+  // cell that is computable and reachable, so a chain t, t - d, ... starts at the first t' of its residue class at which the
+  // block's feed-forward input exists, and IfDefined supplies zeros before that.  The recurrent connection itself asks for
+  // nothing (ComputeSimpleNnetContext ignores the optional dependency).
+  std::vector<int> lext, rext;
+  auto extents = [&](const std::vector<int> *avail) {
+    lext.assign(N, 0);
+    rext.assign(N, 0);
+    for (auto it = order.rbegin(); it != order.rend(); ++it) {
+      int n = *it;
+      const NnetNode &nd = nodes[n];
+      if (nd.kind == NnetNode::kDimRange) {
+        lext[nd.range_node] = std::max(lext[nd.range_node], lext[n]);
+        rext[nd.range_node] = std::max(rext[nd.range_node], rext[n]);
+        continue;
       }
-  }
+      if (block_of[n] >= 0) {
+        BlockNodes &b = blocks[block_of[n]];
+        int l = 0, r = 0;
+        for (int m : b.members) { l = std::max(l, lext[m]); r = std::max(r, rext[m]); }
+        b.need_lext = l;
+        if (avail) l = std::max(l, (*avail)[b.wa]);
+        for (int m : b.members) { lext[m] = l; rext[m] = r; }
+        for (auto &p : b.x_parts)
+          for (auto &t : p.terms) {
+            if (t.const_t) continue;
+            lext[t.node] = std::max(lext[t.node], l - t.offset);
+            rext[t.node] = std::max(rext[t.node], r + t.offset);
+          }
+        continue;
+      }
+      std::vector<int> toffs = tdnn_offsets(nd);
+      for (auto &p : nd.input.parts)
+        for (auto &t : p.terms) {
+          if (t.const_t) continue;
+          for (int o2 : toffs) {
+            int o = t.offset + o2;
+            lext[t.node] = std::max(lext[t.node], lext[n] - o);
+            rext[t.node] = std::max(rext[t.node], rext[n] + o);
+          }
+        }
+    }
+  };
+  extents(nullptr);
   left_context = lext[in_node];
   right_context = rext[in_node];
+  if (recurrent) {
+    // avail[n]: node n is computable for t >= -avail[n] when the input is there for t >= -left_context
+    const int kFree = 1 << 28;
+    std::vector<int> avail(N, kFree);
+    avail[in_node] = left_context;
+    for (int n : order) {
+      const NnetNode &nd = nodes[n];
+      if (nd.kind == NnetNode::kInput) continue;
+      if (nd.kind == NnetNode::kDimRange) { avail[n] = avail[nd.range_node]; continue; }
+      int a = kFree;
+      if (block_of[n] >= 0) {
+        const BlockNodes &b = blocks[block_of[n]];
+        for (auto &p : b.x_parts) for (auto &t : p.terms) if (!t.const_t) a = std::min(a, avail[t.node] + t.offset);
+        if (a >= kFree / 2) Fail("nnet3: recurrent block at node " + nd.name + " has no input that depends on time");
+        for (int m : b.members) avail[m] = a;
+        continue;
+      }
+      for (int o2 : tdnn_offsets(nd))
+        for (auto &p : nd.input.parts) for (auto &t : p.terms) if (!t.const_t) a = std::min(a, avail[t.node] + t.offset + o2);
+      avail[n] = a;
+    }
+    extents(&avail);
+    if (lext[in_node] != left_context || rext[in_node] != right_context)
+      Fail("nnet3: internal error, the rows of the recurrent blocks reach beyond the network's context");
+  }
 
   // buffer assignment
   std::vector<int> node_buf(N, -1), node_col(N, 0);
@@ -1116,9 +1391,111 @@ void Nnet::Compile() {
     *col = node_col[t.node];
   };
 
+  // the segments of an affine layer over the parts of an Append (for every time offset of a TdnnComponent); a part that is a Sum
+  // is materialised first.  Returns the number of weight columns the parts cover.
+  auto add_gemm_segs = [&](LayerOp *op, const std::vector<DescPart> &parts, int n, const std::vector<int> &toffs) {
+    const NnetNode &nd = nodes[n];
+    int wcol = 0;
+    for (int o2 : toffs) {
+      for (auto &p : parts) {
+        int sbuf, scol, soff;
+        if (p.terms.size() == 1 && p.terms[0].scale == 1.0f) {
+          const DescTerm &t = p.terms[0];
+          term_src(t, &sbuf, &scol);
+          soff = t.const_t ? 0 : t.offset;
+          if (sbuf == -2) { sbuf = -1; soff = 0; }
+          else if (t.const_t) Fail("nnet3: ReplaceIndex on a non-iVector node is not supported (node " + nd.name + ")");
+        } else {
+          // materialise the sum
+          LayerOp sop;
+          sop.kind = LayerOp::kEltwise;
+          sop.name = nd.name + ".sum";
+          sop.out_dim = p.dim;
+          int l = 0, r = 0;
+          for (int oo : toffs) { l = std::max(l, lext[n] - oo); r = std::max(r, rext[n] + oo); }
+          sop.out_buf = new_buf(p.dim, std::max(l, 0), std::max(r, 0));
+          for (auto &t : p.terms) {
+            int b, c;
+            term_src(t, &b, &c);
+            if (b == -2 || t.const_t) Fail("nnet3: Sum() over the iVector input is not supported");
+            sop.terms.push_back({b, c, t.offset, t.scale});
+          }
+          ops.push_back(sop);
+          sbuf = sop.out_buf; scol = 0; soff = 0;
+        }
+        GemmSegment sg;
+        sg.src_buf = sbuf; sg.src_col = scol; sg.ncols = p.dim; sg.offset = soff + (sbuf == -1 ? 0 : o2); sg.w_col = wcol;
+        op->segs.push_back(sg);
+        wcol += p.dim;
+      }
+    }
+    return wcol;
+  };
+
   for (int n : order) {
     NnetNode &nd = nodes[n];
     if (nd.kind == NnetNode::kInput) continue;
+    if (block_of[n] >= 0) {
+      // ---- a recurrent block: the feed-forward columns of W_all as a layer GEMM over all rows (bias included), then the walk
+      const BlockNodes &b = blocks[block_of[n]];
+      const Component &wa = components[nodes[b.wa].component];
+      const MatF &W = wa.m.at("<LinearParams>");
+      const int C = b.cell, rec = b.rec_dim, in_dim = W.cols - rec, l = lext[b.wa], r = rext[b.wa];
+      LayerOp g;
+      g.kind = LayerOp::kGemm;
+      g.name = nodes[b.wa].name + ".x";
+      g.out_dim = 4 * C;
+      g.W.Resize(4 * C, in_dim);
+      LayerOp w;
+      w.kind = LayerOp::kLstm;
+      w.name = nodes[b.nl].name;
+      w.out_dim = 2 * C;
+      LstmBlock &k = w.lstm;
+      k.W_r.Resize(4 * C, rec);
+      for (int row = 0; row < 4 * C; row++) {
+        for (int c = 0; c < in_dim; c++) g.W(row, c) = W(row, c);
+        for (int c = 0; c < rec; c++) k.W_r(row, c) = W(row, in_dim + c);
+      }
+      auto bit = wa.v.find("<BiasParams>");
+      if (bit != wa.v.end() && !bit->second.empty()) {
+        if ((int)bit->second.size() != 4 * C) Fail("nnet3: bias dim mismatch in node " + nodes[b.wa].name);
+        g.bias = bit->second;
+      }
+      const int wcol = add_gemm_segs(&g, b.x_parts, b.wa, {0});
+      if (wcol != in_dim)
+        Fail("nnet3: component of node " + nodes[b.wa].name + " expects input dim " + std::to_string(W.cols) + " but its descriptor provides " +
+             std::to_string(wcol + rec));
+      g.out_buf = new_buf(4 * C, l, r);
+      ops.push_back(g);
+      k.in_dim = in_dim; k.cell = C; k.rec = b.rp >= 0 ? nodes[b.r].dim : 0; k.nonrec = b.rp >= 0 ? nodes[b.rp].dim - nodes[b.r].dim : 0;
+      k.delay = b.delay;
+      k.scale = TruncationScale(components[nodes[b.tr].component]);
+      k.dropout_mask = b.dm >= 0;
+      k.params = components[nodes[b.nl].component].m.at("<Params>");
+      k.need_lext = b.need_lext;
+      k.pre_buf = g.out_buf;
+      k.cm_buf = new_buf(2 * C, l, r);
+      k.st_buf = new_buf(C + rec, l, r);
+      node_buf[b.wa] = k.pre_buf;
+      node_buf[b.nl] = k.cm_buf;
+      node_buf[b.tr] = node_buf[b.sc] = node_buf[b.sr] = k.st_buf;
+      node_col[b.sr] = C;
+      if (b.rp >= 0) {
+        const Component &rp = components[nodes[b.rp].component];
+        k.W_rp = rp.m.at("<LinearParams>");
+        auto rb = rp.v.find("<BiasParams>");
+        k.b_rp = rb != rp.v.end() && !rb->second.empty() ? rb->second : std::vector<float>(k.W_rp.rows, 0.0f);
+        if ((int)k.b_rp.size() != k.W_rp.rows) Fail("nnet3: bias dim mismatch in node " + nodes[b.rp].name);
+        k.rp_buf = new_buf(k.rec + k.nonrec, l, r);
+        node_buf[b.c] = node_buf[b.m] = k.cm_buf;
+        node_col[b.m] = C;
+        node_buf[b.rp] = node_buf[b.r] = k.rp_buf;
+      }
+      w.out_buf = k.cm_buf;
+      w.terms.push_back({k.pre_buf, 0, 0, 1.0f});
+      ops.push_back(w);
+      continue;
+    }
     if (nd.kind == NnetNode::kDimRange) {
       if (node_buf[nd.range_node] == -2) Fail("nnet3: dim-range-node over the iVector input is not supported");
       node_buf[n] = node_buf[nd.range_node];
@@ -1168,40 +1545,7 @@ void Nnet::Compile() {
       auto bit = comp->v.find("<BiasParams>");
       if (bit != comp->v.end() && !bit->second.empty()) op.bias = bit->second;
       std::vector<int> toffs = tdnn_offsets(nd);
-      int wcol = 0;
-      for (int o2 : toffs) {
-        for (auto &p : nd.input.parts) {
-          int sbuf, scol, soff;
-          if (p.terms.size() == 1 && p.terms[0].scale == 1.0f) {
-            const DescTerm &t = p.terms[0];
-            term_src(t, &sbuf, &scol);
-            soff = t.const_t ? 0 : t.offset;
-            if (sbuf == -2) { sbuf = -1; soff = 0; }
-            else if (t.const_t) Fail("nnet3: ReplaceIndex on a non-iVector node is not supported (node " + nd.name + ")");
-          } else {
-            // materialise the sum
-            LayerOp sop;
-            sop.kind = LayerOp::kEltwise;
-            sop.name = nd.name + ".sum";
-            sop.out_dim = p.dim;
-            int l = 0, r = 0;
-            for (int oo : toffs) { l = std::max(l, lext[n] - oo); r = std::max(r, rext[n] + oo); }
-            sop.out_buf = new_buf(p.dim, std::max(l, 0), std::max(r, 0));
-            for (auto &t : p.terms) {
-              int b, c;
-              term_src(t, &b, &c);
-              if (b == -2 || t.const_t) Fail("nnet3: Sum() over the iVector input is not supported");
-              sop.terms.push_back({b, c, t.offset, t.scale});
-            }
-            ops.push_back(sop);
-            sbuf = sop.out_buf; scol = 0; soff = 0;
-          }
-          GemmSegment sg;
-          sg.src_buf = sbuf; sg.src_col = scol; sg.ncols = p.dim; sg.offset = soff + (sbuf == -1 ? 0 : o2); sg.w_col = wcol;
-          op.segs.push_back(sg);
-          wcol += p.dim;
-        }
-      }
+      const int wcol = add_gemm_segs(&op, nd.input.parts, n, toffs);
       if (wcol != W.cols) Fail("nnet3: component of node " + nd.name + " expects input dim " + std::to_string(W.cols) + " but its descriptor provides " + std::to_string(wcol));
       if (!op.bias.empty() && (int)op.bias.size() != W.rows) Fail("nnet3: bias dim mismatch in node " + nd.name);
     } else if (conv) {
@@ -1347,6 +1691,16 @@ void Nnet::SetSubsampling(int factor) {
   // a layer X that feeds a Sum dense while its own input W stayed strided: X's GEMM ran over all rows and read rows of W nobody
   // had written in that call.)
   for (auto it = ops.rbegin(); it != ops.rend(); ++it) {
+    if (it->kind == LayerOp::kLstm) {
+      // a block's buffers hold the same rows: every residue one of them is read at, and every residue the chains of those rows
+      // pass through (delay 3 under factor 3 stays in its class; delay 2 visits all three)
+      const LstmBlock &k = it->lstm;
+      unsigned all = need[k.cm_buf] | need[k.st_buf] | (k.rp_buf >= 0 ? need[k.rp_buf] : 0u);
+      for (int round = 0; round < factor; round++)
+        for (int r = 0; r < factor; r++) if (all >> r & 1u) all |= 1u << mod(r - k.delay);
+      need[k.cm_buf] = need[k.st_buf] = all;
+      if (k.rp_buf >= 0) need[k.rp_buf] = all;
+    }
     const unsigned out = need[it->out_buf];
     auto reads = [&](int src, int off) {
       if (src < 0) return;

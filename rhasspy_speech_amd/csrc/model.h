@@ -156,6 +156,7 @@ struct DescTerm {
   int offset = 0;
   float scale = 1.0f;
   bool const_t = false;
+  bool optional = false;   // inside IfDefined(): the recurrent connections of a block are written that way
 };
 // Append(part0, part1, ...) where each part is a Sum of terms of equal dim.
 struct DescPart {
@@ -198,9 +199,36 @@ struct ConvGeom {
   std::vector<int> time_offsets;              // the distinct time offsets, ascending: LayerOp::terms[i] reads the rows of time_offsets[i]
   int K() const { return (int)offsets.size() * filters_in; }
 };
+// A recurrent block: what nnet3's fast-lstmp-layer / fast-lstm-layer emit (xconfig/lstm.py), recognised as a unit (Nnet::Compile).
+// With s_c, s_r the state rows (zero where the chain has not started), d the delay, per row t:
+//   gates = pre[t] + W_r s_r[t - d]                                   pre = W_x x + b, a kGemm op over all rows
+//   (c, m) = LstmNonlinearity(gates, s_c[t - d]; params)              cu-math.cc:445-486
+//   rp = W_rp m + b_rp                                                with a projection
+//   s_c[t] = scale c,  s_r[t] = scale rp[0:rec] (or scale m)          BackpropTruncationComponent::Propagate
+struct LstmBlock {
+  int in_dim = 0, cell = 0, rec = 0, nonrec = 0;   // rec / nonrec: the projection's dims, 0 / 0 without one (the recurrent input is then m)
+  int delay = 0;                  // frames towards the past, 1 .. kLstmMaxDelay
+  float scale = 1.0f;
+  bool dropout_mask = false;      // use-dropout=true with its DropoutMaskComponent node: all ones in test mode
+  MatF W_r;                       // 4 cell x RecDim(): W_all's recurrent columns
+  MatF params;                    // 3 x cell: w_ic, w_fc, w_oc
+  MatF W_rp;                      // (rec + nonrec) x cell
+  std::vector<float> b_rp;
+  // buffers: pre-activations (4 cell), the nonlinearity's output [c | m], rp (-1 without a projection), the state [s_c | s_r]
+  int pre_buf = -1, cm_buf = -1, rp_buf = -1, st_buf = -1;
+  // rows: a call that starts an utterance walks t from -lext of these buffers (the first t at which x is computable from the input
+  // the first chunk requests); an advance that continues a stream re-enters at t0 - need_lext with the state it parked
+  int need_lext = 0;
+  bool proj() const { return rec > 0; }
+  int RecDim() const { return rec > 0 ? rec : cell; }
+  int OutDim() const { return rec > 0 ? rec + nonrec : cell; }
+};
+constexpr int kLstmMaxDelay = 8;
+
 struct LayerOp {
   // kConv: out = stages(bias + conv(terms)); kGather: out[:, i] = part(gather_part[i])[:, gather_col[i]] (PermuteComponent over an Append)
-  enum Kind { kGemm, kEltwise, kConv, kGather } kind = kGemm;
+  // kLstm: the serial part of a recurrent block (lstm); out_buf = lstm.cm_buf
+  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm } kind = kGemm;
   std::string name;
   int out_buf = -1, out_dim = 0;
   // kGemm
@@ -218,6 +246,7 @@ struct LayerOp {
   std::vector<EltStage> stages; // applied after the gemm/sum, in order
   ConvGeom conv;                           // kConv
   std::vector<int> gather_part, gather_col;   // kGather, per output column: the term and the column inside it
+  LstmBlock lstm;                             // kLstm
 };
 struct BufferInfo {
   int dim = 0, lext = 0, rext = 0;   // rows cover t in [-lext, T + rext)
@@ -236,12 +265,14 @@ struct Nnet {
   std::vector<BufferInfo> bufs;
   int input_buf = -1, output_buf = -1;
   int left_context = 0, right_context = 0;
+  bool recurrent = false;      // has at least one recurrent block (kLstm op)
   // What the reference's binaries do to the network before the first frame (nnet3_setup.h): the network is the one
   // CollapseModel leaves behind, and rand() has been called `setup_rand_calls` times (the dither seeds follow from that).
   long setup_rand_calls = 0;
   bool setup_rand_certain = true;
   std::string setup_rand_uncertain_why;
   void Read(KaldiReader &r, int frames_per_chunk = 24, int extra_left_context_initial = 0, int frame_subsampling_factor = 1);
+  void ParseNodes(const std::vector<std::string> &config_lines);   // nodes (and the dims) from config lines and the components read
   void Compile();   // builds ops/bufs for the "output" node
   void SetSubsampling(int factor);   // fills BufferInfo::stride for outputs wanted at t = 0, factor, 2 factor, ...
   int FindNode(const std::string &name) const;

@@ -737,6 +737,31 @@ std::vector<bool> ReachableFromOutputs(const Net &net) {
   return seen;
 }
 
+// The name of a kept node that depends on itself ("" in a feed-forward network); a DropoutMaskComponent's own input is no dependency
+std::string NodeOnCycle(const Net &net, const std::vector<bool> &keep) {
+  const int N = (int)net.nodes.size();
+  std::vector<char> state(N, 0);
+  std::string found;
+  std::function<void(int)> visit = [&](int i) {
+    if (!found.empty() || state[i] == 2) return;
+    if (state[i] == 1) { found = net.nodes[i].component_input ? net.nodes[i + 1].name : net.nodes[i].name; return; }
+    state[i] = 1;
+    const Node &n = net.nodes[i];
+    if (n.type == Node::kDescriptor) {
+      std::function<void(const G &)> walk = [&](const G &g) {
+        if (g.kind == kNode) visit(g.v1);
+        for (auto &c : g.ch) walk(c);
+      };
+      walk(n.desc.g);
+    } else if (n.type == Node::kComponent) {
+      if (net.CType(n.comp) != "DropoutMaskComponent") visit(i - 1);
+    } else if (n.type == Node::kDimRange) visit(n.src);
+    state[i] = 2;
+  };
+  for (int i = 0; i < N && found.empty(); i++) if (keep[i]) visit(i);
+  return found;
+}
+
 // =============================================================================== computation graph (nnet-computation-graph.cc)
 
 enum { kUnknown = 0, kComputable = 1, kNotComputable = 2 };
@@ -838,6 +863,7 @@ struct GraphBuilder {
     out->clear();
     if (node.type == Node::kDescriptor) node.desc.Deps(c.i, out);
     else if (node.type == Node::kComponent) {
+      if (net.CType(node.comp) == "DropoutMaskComponent") return;      // GetInputIndexes asks for nothing (nnet-general-component.h:768-783)
       const std::vector<int32_t> *offs = net.TimeOffsets(node.comp);
       if (!offs) out->push_back(Cindex{c.node - 1, c.i});
       else for (int o : *offs) out->push_back(Cindex{c.node - 1, Index{c.i.n, c.i.t + o, c.i.x}});
@@ -889,6 +915,7 @@ struct GraphBuilder {
   bool ComponentComputable(int node_i, const Index &ind, const CSet &cs, std::vector<Cindex> *used) const {
     const std::vector<int32_t> *offs = net.TimeOffsets(net.nodes[node_i].comp);
     if (used) used->clear();
+    if (net.CType(net.nodes[node_i].comp) == "DropoutMaskComponent") return true;      // IsComputable: always (its input is a don't-care)
     auto one = [&](const Cindex &c) {
       if (!cs(c)) return false;
       if (used) used->push_back(c);
@@ -1175,6 +1202,13 @@ Nnet3SetupResult Nnet3Setup(const std::vector<std::string> &config_lines, std::v
     if (max_offset > chunk) {
       res.rand_calls_certain = false;
       res.uncertain_why = "a time offset of " + std::to_string(max_offset) + " frames exceeds --frames-per-chunk=" + std::to_string(chunk);
+    }
+    // A recurrent network compiles to steps of another structure (one per node and time of a cycle, nnet-compile.cc:50-62 with
+    // ComputeComputationPhases) and the number of looped-compilation attempts is not known: the count above does not cover it.
+    const std::string cyc = NodeOnCycle(net, keep);
+    if (!cyc.empty()) {
+      res.rand_calls_certain = false;
+      res.uncertain_why = "the network is recurrent (a cycle through node " + cyc + "): the rand() calls of a recurrent compilation are not replayed";
     }
   }
   return res;

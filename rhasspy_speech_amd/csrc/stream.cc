@@ -159,6 +159,12 @@ struct StreamPool {
   // still be taken, until they are freed or an open / a growing stream needs the room (oldest first)
   std::vector<rs_stream *> ended;
   long long *dec_ctr = nullptr;
+  // Recurrent blocks: per kLstm op (indexed like the network's ops, null elsewhere) and slot, the `delay` state rows [s_c | s_r] the
+  // stream's next advance re-enters the block behind -- row (t mod delay) holds the state of the one t in
+  // [ll_done - need_lext - delay, ll_done - need_lext) of that class (lstm_plan.h: LstmDev::ring).  Written by the advance that
+  // computes those rows, read by the next one; a stream's first advance reads nothing (it starts from zeros), so opening, growing,
+  // reclaiming and ending a stream have nothing to do here: the state goes with the slot.
+  std::vector<float *> lstm_ring;
   // rs_streams_partial on register-resident streams (decode_partial.hip): the previous call's best path per row, its length and
   // words per slot
   static constexpr int kPartialWords = 1024;          // = SearchPlan::max_words: a partial result holds as many words as a final one
@@ -278,6 +284,12 @@ StreamPool *Model::Pool() {
     p->anchor_words = static_cast<int *>(dalloc((size_t)p->max_slots * StreamPool::kPartialWords * 4));
   }
   p->dec_ctr = static_cast<long long *>(dalloc((size_t)p->max_slots * 64));
+  p->lstm_ring.assign(nn.ops.size(), nullptr);
+  for (size_t i = 0; i < nn.ops.size(); i++)
+    if (nn.ops[i].kind == LayerOp::kLstm) {
+      const LstmBlock &k = nn.ops[i].lstm;
+      p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * (k.cell + k.RecDim()) * 4));
+    }
   if (fc_.ie.present) {
     const int Di = fc_.ie.ivector_dim(), usz = Di * (Di + 1) / 2;
     p->ld_i = RoundUp(Di, 4);
@@ -606,6 +618,9 @@ struct StagesBC {
   int nI = 0, nN = 0, rowsN = 0, framesN = 0, maxTn = 1, n = 0, n_sub = 0;
   bool have_sub = false;
   const int *d_nsrc = nullptr, *d_nfb = nullptr, *d_nrb = nullptr, *d_nriv = nullptr, *d_nll = nullptr, *d_nlls = nullptr, *d_slots = nullptr;
+  // recurrent networks: per nnet segment its frames; the stream's frames before it and its slot (h_lstm: both, staged on the host)
+  const int *d_nT = nullptr, *h_lstm = nullptr;
+  int *d_lstm_t0 = nullptr, *d_lstm_slot = nullptr;
   std::vector<float *> bufp;
   std::vector<int> buf_ld;
   std::vector<ActImage> imgs;
@@ -834,6 +849,13 @@ void Model::AdvanceStagesBC(StreamPool *p, const AdvancePlan &plan, const Advanc
     for (size_t b = 0; b < nn.bufs.size(); b++) job.bufp[b] = AllocGuarded(arena, plan.rowsN, job.buf_ld[b], set.guard);
     job.imgs = AllocImages(arena, plan.rowsN);
     job.frame_rows = arena.AllocT<int>(plan.framesN + 8);
+    if (nn.recurrent) {
+      // where each segment's stream stands (its log-likelihood frames so far: the segment covers [t0, t1)) and its slot
+      const int nN = plan.nN;
+      int *h = set.harena->AllocT<int>(2 * (size_t)nN + 8), *dv = arena.AllocT<int>(2 * (size_t)nN + 8);
+      for (int k = 0; k < nN; k++) { h[k] = plan.pl[plan.N_idx[k]].t0; h[nN + k] = plan.slots[plan.N_idx[k]]; }
+      job.d_nT = D(o.nT); job.h_lstm = h; job.d_lstm_t0 = dv; job.d_lstm_slot = dv + nN;      // (copied on q, in front of the acoustic model)
+    }
   }
   job.gd = SearchGeom(plan, set.d_is);
   DenseWork &dw = job.dw;
@@ -865,7 +887,11 @@ void Model::IssueStagesBC(const StagesBC &j) {
     RowMaps row_maps;
     row_maps.maps.push_back({0, 0, j.frame_rows, j.framesN});
     if (fsf > 1 && j.have_sub) row_maps.maps.push_back({0, 0, j.d_nlls, j.n_sub, 0, fsf});      // the layers only the decoder's frames read
-    RunNnet(j.bufp, j.buf_ld, p->ivec, p->ld_i, j.d_nriv, j.rowsN, row_maps, 1, 0, nn.ops.size(), q, &j.imgs);
+    LstmCall lstm_call;
+    if (j.h_lstm) RS_HIP(hipMemcpyAsync(j.d_lstm_t0, j.h_lstm, sizeof(int) * 2 * (size_t)j.nN, hipMemcpyHostToDevice, q));
+    lstm_call.n_utts = j.nN; lstm_call.num_frames = j.d_nT; lstm_call.row_base = j.d_nrb;
+    lstm_call.t0 = j.d_lstm_t0; lstm_call.slot = j.d_lstm_slot; lstm_call.rings = &p->lstm_ring;
+    RunNnet(j.bufp, j.buf_ld, p->ivec, p->ld_i, j.d_nriv, j.rowsN, row_maps, 1, 0, nn.ops.size(), q, &j.imgs, &lstm_call);
     if (fsf == 1) LaunchCopyRows(j.bufp[nn.output_buf], j.buf_ld[nn.output_buf], j.frame_rows, p->ll, p->ld_ll, j.d_nll, j.framesN, P, q);
     else if (j.n_sub > 0) LaunchCopyRows(j.bufp[nn.output_buf], j.buf_ld[nn.output_buf], j.d_nlls, p->ll, p->ld_ll, j.d_nll, j.n_sub, P, q);
   }

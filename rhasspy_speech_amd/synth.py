@@ -214,6 +214,12 @@ class ModelSpec:
     # > 0: the iVector goes through a LinearComponent to that many feature maps + BatchNorm, and a PermuteComponent interleaves
     # them with the features (combine-feature-maps-layer) instead of being appended to the first affine's input
     conv_ivector_maps: int = 0
+    # Recurrent blocks between the TDNN layers (nnet3's fast-lstmp-layer / fast-lstm-layer, xconfig/lstm.py).  One dict per block:
+    # after (the block follows that many of layer_offsets' layers, >= 1), cell, rec and nonrec (the recurrent and non-recurrent
+    # projection dims; 0 and 0: no projection, fast-lstm-layer), delay (frames towards the past, default 3), scale (the
+    # BackpropTruncationComponent's <Scale>, 1 - delay / decay-time in a recipe; default 1), dropout (use-dropout=true with its
+    # DropoutMaskComponent node, default False), batchnorm (a BatchNorm on the block's output, default False).
+    lstm_layers: Tuple[Dict[str, object], ...] = ()
 
     @property
     def num_pdfs(self) -> int:
@@ -515,6 +521,103 @@ def _w_noop(w: KaldiWriter, dim: int) -> None:
     w.token("<NoOpComponent>").token("<Dim>").i32(dim).token("<BackpropScale>").f32(1.0).token("</NoOpComponent>")
 
 
+def _w_lstm_nonlinearity(w: KaldiWriter, params: np.ndarray, use_dropout: bool) -> None:
+    # nnet-combined-component.cc:1019-1057 (LstmNonlinearityComponent::Write), behind WriteUpdatableCommon
+    cell = params.shape[1]
+    _updatable_open(w, "LstmNonlinearityComponent")
+    w.token("<Params>").matrix(params)
+    w.token("<ValueAvg>").matrix(np.zeros((5, cell), np.float32)).token("<DerivAvg>").matrix(np.zeros((5, cell), np.float32))
+    w.token("<SelfRepairConfig>").vector(np.array([0.05, 0.05, 0.2, 0.05, 0.2] + [1e-5] * 5, np.float32))
+    w.token("<SelfRepairProb>").vector(np.zeros(5, np.float32))
+    if use_dropout:
+        w.token("<UseDropout>").boolean(True)
+    w.token("<Count>").f64(0.0)
+    w.token("</LstmNonlinearityComponent>")
+
+
+def _w_backprop_truncation(w: KaldiWriter, dim: int, scale: float, recurrence_interval: int) -> None:
+    # nnet-general-component.cc:932-955
+    w.token("<BackpropTruncationComponent>").token("<Dim>").i32(dim).token("<Scale>").f32(scale)
+    w.token("<ClippingThreshold>").f32(30.0).token("<ZeroingThreshold>").f32(15.0).token("<ZeroingInterval>").i32(20)
+    w.token("<RecurrenceInterval>").i32(recurrence_interval)
+    w.token("<NumElementsClipped>").f64(0.0).token("<NumElementsZeroed>").f64(0.0)
+    w.token("<NumElementsProcessed>").f64(0.0).token("<NumZeroingBoundaries>").f64(0.0)
+    w.token("</BackpropTruncationComponent>")
+
+
+def _w_dropout_mask(w: KaldiWriter, output_dim: int, proportion: float = 0.0) -> None:
+    # nnet-general-component.cc:1499-1510 (<Continuous> would be a bare flag token)
+    w.token("<DropoutMaskComponent>").token("<OutputDim>").i32(output_dim).token("<DropoutProportion>").f32(proportion)
+    w.token("<TestMode>").boolean(False)
+    w.token("</DropoutMaskComponent>")
+
+
+def lstm_layer_dims(layer: Dict[str, object]) -> Tuple[int, int, int, int]:
+    """(cell, recurrent, non-recurrent, output) dims of a ModelSpec.lstm_layers entry; without a projection the recurrent
+    input and the output are the cell-wide m."""
+    C, R, P = int(layer["cell"]), int(layer.get("rec", 0)), int(layer.get("nonrec", 0))
+    if (R == 0) != (P == 0):
+        raise ValueError("lstm layer: rec and nonrec are both 0 (no projection) or both positive")
+    return C, R, P, (R + P if R else C)
+
+
+def _lstm_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.Generator, name: str, layer: Dict[str, object],
+                prev: str, prev_dim: int) -> Tuple[str, int]:
+    """The components and nodes XconfigFastLstmpLayer / XconfigFastLstmLayer emit (xconfig/lstm.py:1120-1198, 706-753), in their
+    order.  Returns the node the next layer reads and its dim."""
+    C, R, P, out_dim = lstm_layer_dims(layer)
+    d, scale = int(layer.get("delay", 3)), float(layer.get("scale", 1.0))
+    dropout, proj = bool(layer.get("dropout", False)), R > 0
+    rec_dim = R if proj else C
+
+    def randn(o, i):
+        return (rng.standard_normal((o, i)) / math.sqrt(i)).astype(np.float32)
+
+    W_all = np.concatenate([randn(4 * C, prev_dim), randn(4 * C, rec_dim)], axis=1)
+    b_all = (rng.standard_normal(4 * C) * 0.1).astype(np.float32)
+    params = (rng.standard_normal((3, C)) * 0.1).astype(np.float32)
+    trunc = "cr_trunc" if proj else "cm_trunc"
+    comps.append((f"{name}.W_all", lambda w, W=W_all, b=b_all: _w_affine(w, "NaturalGradientAffineComponent", W, b)))
+    comps.append((f"{name}.lstm_nonlin", lambda w, p=params, u=dropout: _w_lstm_nonlinearity(w, p, u)))
+    comps.append((f"{name}.{trunc}", lambda w, n=C + rec_dim, s=scale, i=d: _w_backprop_truncation(w, n, s, i)))
+    if dropout:
+        comps.append((f"{name}.dropout_mask", lambda w: _w_dropout_mask(w, 3)))
+    if proj:
+        W_rp, b_rp = randn(R + P, C), (rng.standard_normal(R + P) * 0.1).astype(np.float32)
+        comps.append((f"{name}.W_rp", lambda w, W=W_rp, b=b_rp: _w_affine(w, "NaturalGradientAffineComponent", W, b)))
+    s_r = f"{name}.r_trunc" if proj else f"{name}.m_trunc"
+    cfg.append(f"component-node name={name}.W_all component={name}.W_all input=Append({prev}, IfDefined(Offset({s_r}, {-d})))")
+    if dropout:
+        cfg.append(f"component-node name={name}.dropout_mask component={name}.dropout_mask input={name}.dropout_mask")
+        cfg.append(f"component-node name={name}.lstm_nonlin component={name}.lstm_nonlin "
+                   f"input=Append({name}.W_all, IfDefined(Offset({name}.c_trunc, {-d})), {name}.dropout_mask)")
+    else:
+        cfg.append(f"component-node name={name}.lstm_nonlin component={name}.lstm_nonlin "
+                   f"input=Append({name}.W_all, IfDefined(Offset({name}.c_trunc, {-d})))")
+    if proj:
+        cfg.append(f"dim-range-node name={name}.c input-node={name}.lstm_nonlin dim-offset=0 dim={C}")
+    cfg.append(f"dim-range-node name={name}.m input-node={name}.lstm_nonlin dim-offset={C} dim={C}")
+    if proj:
+        cfg.append(f"component-node name={name}.rp component={name}.W_rp input={name}.m")
+        cfg.append(f"dim-range-node name={name}.r input-node={name}.rp dim-offset=0 dim={R}")
+        cfg.append(f"component-node name={name}.cr_trunc component={name}.cr_trunc input=Append({name}.c, {name}.r)")
+        cfg.append(f"dim-range-node name={name}.c_trunc input-node={name}.cr_trunc dim-offset=0 dim={C}")
+        cfg.append(f"dim-range-node name={name}.r_trunc input-node={name}.cr_trunc dim-offset={C} dim={R}")
+        out = f"{name}.rp"
+    else:
+        cfg.append(f"component-node name={name}.cm_trunc component={name}.cm_trunc input={name}.lstm_nonlin")
+        cfg.append(f"dim-range-node name={name}.c_trunc input-node={name}.cm_trunc dim-offset=0 dim={C}")
+        cfg.append(f"dim-range-node name={name}.m_trunc input-node={name}.cm_trunc dim-offset={C} dim={C}")
+        out = f"{name}.m"
+    if layer.get("batchnorm", False):
+        bn = out + "_batchnorm"
+        mean, var = (0.1 * rng.standard_normal(out_dim)).astype(np.float32), rng.uniform(0.05, 0.2, out_dim).astype(np.float32)
+        comps.append((bn, lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+        cfg.append(f"component-node name={bn} component={bn} input={out}")
+        out = bn
+    return out, out_dim
+
+
 def _append_desc(src: str, offsets: Sequence[int]) -> str:
     parts = [src if o == 0 else f"Offset({src}, {o})" for o in offsets]
     return parts[0] if len(parts) == 1 else "Append(" + ", ".join(parts) + ")"
@@ -594,8 +697,18 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
     cfg.append(f"component-node name=lda component=lda input={lda_desc}")
     prev, prev_dim = "lda", lda_in
 
+    def lstm_blocks_after(n_layers, prev, prev_dim):
+        for k, layer in enumerate(spec.lstm_layers, start=1):
+            if int(layer["after"]) == n_layers:
+                prev, prev_dim = _lstm_block(cfg, comps, rng, f"lstm{k}", layer, prev, prev_dim)
+        return prev, prev_dim
+
+    for layer in spec.lstm_layers:
+        if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
+            raise ValueError("lstm layer: 'after' counts the TDNN layers in front of the block, 1 .. len(layer_offsets)")
     for li, offs in enumerate(spec.layer_offsets, start=1):
         H = spec.hidden_dim
+        prev, prev_dim = lstm_blocks_after(li - 1, prev, prev_dim)
         if spec.tdnnf and li > 1:
             # factorized layer: linear bottleneck (TdnnComponent w/o bias) -> affine (TdnnComponent) -> relu -> bn
             # -> dropout(test: identity) -> Sum(Scale(0.66, prev), this) residual through NoOp
@@ -642,6 +755,7 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
         cfg.append(f"component-node name=tdnn{li}.batchnorm component=tdnn{li}.batchnorm input=tdnn{li}.relu")
         prev, prev_dim = f"tdnn{li}.batchnorm", H
 
+    prev, prev_dim = lstm_blocks_after(len(spec.layer_offsets), prev, prev_dim)
     # prefinal-chain: affine -> relu -> batchnorm
     Pd = spec.prefinal_dim
     W, b = randw(Pd, prev_dim), randb(Pd)
