@@ -109,8 +109,19 @@ const char *rs_last_error(void);
  * optionally the projection W_rp over m, and one BackpropTruncationComponent (its <Scale> is honoured, here and anywhere else) whose
  * dim-ranges are the state; one delay d for both connections, 1 <= d <= 8, towards the past.  Limits: cell dim <= 2048, recurrent +
  * non-recurrent projection dim <= 4096, and 64 * (2 * recurrent input dim + cell dim [with a projection] + 12) bytes <= 144 KiB of
- * LDS.  Any other cycle -- lstmp-layer's Sigmoid / Tanh / ElementwiseProduct cell, lstmb-layer, GRU layers, a positive delay, two
- * delays in one block, a block that reads another block's state at a future time -- is refused with the node and the reason.  The
+ * LDS.  Any other cycle -- lstmp-layer's Sigmoid / Tanh / ElementwiseProduct cell, lstmb-layer, a positive delay, two
+ * delays in one block, a block that reads another block's state at a future time -- is refused with the node and the reason.  A
+ * cycle may instead be what fast-opgru-layer / fast-norm-opgru-layer emit (TDNN-OPGRU recipes, the output-gate projected GRU): two
+ * affines W_z, W_o of cell-dim rows over Append(x, IfDefined(Offset(s_t, -d))), each behind a SigmoidComponent [and one shared
+ * DropoutComponent, a copy in test mode], an affine W_hpart over the same x, an OutputGruNonlinearityComponent over Append(z_t,
+ * hpart_t, IfDefined(Offset(c_t, -d))) with c_t its second cell-dim columns, an ElementwiseProductComponent over Append(c_t, o_t),
+ * the affine W_y, the dim-range [0, R) of W_y's node, optionally a NormalizeComponent (no add-log-stddev, no block-dim), and one
+ * BackpropTruncationComponent whose node is s_t; a BatchNorm on W_y's node is an ordinary layer.  The same delays and the limits
+ * cell dim <= 2048, R + P <= 4096, 64 * (2 * R + cell dim + 12) bytes <= 144 KiB of LDS (dims rounded up to 16).  Refused, in a
+ * sentence of their own that names the node and the reason: anything else in a cycle that holds an OutputGruNonlinearityComponent,
+ * and every cycle that holds a GruNonlinearityComponent (fast-gru-layer, fast-pgru-layer, fast-norm-pgru-layer); the non-fast
+ * gru-layer / pgru-layer / opgru-layer and their norm forms (cells of Sigmoid / Tanh / ElementwiseProduct components without either
+ * nonlinearity) are refused like lstmp-layer.  The
  * rand() calls of a recurrent compilation are not replayed, so such a model loads only with --dither=0 in its mfcc.conf / fbank.conf
  * (rs_nnet3_setup below: certain = 0).  Parses on the host only;
  * the device copy is made on first use or by rs_model_to_device().  Immutable afterwards, shareable
@@ -130,7 +141,10 @@ void rs_model_free(rs_model *model);
  * kernel instantiation chosen at load, frames / pixel tiles / LDS bytes per workgroup, filter chunks, grid.  Then one `lstm:` line per
  * recurrent block: name, input dim, cell / recurrent / non-recurrent dims (0 / 0: no projection), delay, the truncation component's
  * scale, dropout_mask=0|1, the kernel instantiation, chains (rows) per workgroup, LDS bytes, the split of W_all's columns into
- * feed-forward + recurrent, cell and projection tiles, the grid rule.  Two lines are state, not structure: `layer_gemm:` and
+ * feed-forward + recurrent, cell and projection tiles, the grid rule.  Then one `gru:` line per GRU block: name, input dim, cell /
+ * recurrent / non-recurrent dims, delay, the truncation component's scale, norm=0|1 (a NormalizeComponent in the recurrence),
+ * dropout=0|1, the kernel instantiation, chains per workgroup, LDS bytes, the split of W_z's and W_o's columns, cell and output tiles,
+ * the grid rule; its `op: gru` line follows the `op: gemm` of the stacked feed-forward columns (3 x cell dim rows).  Two lines are state, not structure: `layer_gemm:` and
  *   arenas: device blocks=B bytes=N allocations=A; host blocks=B bytes=N allocations=A
  * summed over the model's decode contexts: the blocks and bytes their per-call arenas hold now, and the hipMalloc / hipHostMalloc
  * calls they have made since the model was loaded.  `allocations` stands still once every context has seen its largest call twice.
@@ -427,8 +441,9 @@ int rs_bind_host_thread(int32_t device_id);
 /* Parity taps (only with opts.keep_intermediates): kind 0 = nnet input features (T x C), 1 = iVector
  * (n x D_iv: one row offline, one row per nnet chunk for streams), 2 = log-likelihoods (T x P); 3 + k = the output of the
  * model's k-th convolution (T x heights * filters, ReLU and BatchNorm applied; batch calls only); 64 + k = the output rows of the
- * model's k-th recurrent block, what the layers above it read (T x (recurrent + non-recurrent) dim: rp, before any BatchNorm; or
- * T x cell dim: m, without a projection; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
+ * model's k-th recurrent block of either kind, in network order, what the layers above it read (an LSTM block: T x (recurrent +
+ * non-recurrent) dim: rp, before any BatchNorm; or T x cell dim: m, without a projection; a GRU block: T x (recurrent +
+ * non-recurrent) dim: W_y's rows, before any BatchNorm; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
  * hold anything). */
 int rs_result_matrix(const rs_result *r, int32_t utt, int32_t kind, const float **data, int32_t *rows, int32_t *cols);
 /* Decoder work counters of one utterance, for the algorithmic-bytes figure of SURVEY.md section 8(d):

@@ -279,6 +279,9 @@ Model::Model(const std::string &final_mdl, const std::string &hclg, const std::s
   lstm_plans_.assign(am_.nnet.ops.size(), LstmLaunchPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++)
     if (am_.nnet.ops[i].kind == LayerOp::kLstm) lstm_plans_[i] = PlanLstm(am_.nnet.ops[i].lstm, am_.nnet.ops[i].name);
+  gru_plans_.assign(am_.nnet.ops.size(), GruLaunchPlan());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++)
+    if (am_.nnet.ops[i].kind == LayerOp::kGru) gru_plans_[i] = PlanGru(am_.nnet.ops[i].gru, am_.nnet.ops[i].name);
 }
 
 // rs_decode_opts.prune_output_pdfs: the search looks log-likelihoods up by the pdf of the arc it crosses
@@ -420,7 +423,7 @@ template <typename T> T *Model::Upload(const std::vector<T> &v) { return static_
 
 void Model::BuildGemmPlan(const LayerOp &op, GemmPlan *plan) {
   plan->op = &op;
-  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm) {      // (their own operands: ToDevice; here the bias and the fused stages)
+  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm || op.kind == LayerOp::kGru) {      // (their own operands: ToDevice; here the bias and the fused stages)
     plan->d_bias = op.bias.empty() ? nullptr : Upload(op.bias);
     plan->d_stage.clear();
     for (auto &st : op.stages) {
@@ -741,6 +744,17 @@ void Model::ToDevice() {
     lstm_dev_[i].b_rp = Upload(op.lstm.b_rp);
     lstm_dev_[i].params = Upload(op.lstm.params.d);
   }
+  gru_dev_.assign(am_.nnet.ops.size(), GruOperands());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++) {
+    const LayerOp &op = am_.nnet.ops[i];
+    if (op.kind != LayerOp::kGru) continue;
+    std::vector<float> ws_t, wy_t;
+    GruWeightImages(op.gru, gru_plans_[i], &ws_t, &wy_t);
+    gru_dev_[i].ws_t = Upload(ws_t);
+    gru_dev_[i].wy_t = Upload(wy_t);
+    gru_dev_[i].b_y = Upload(op.gru.b_y);
+    gru_dev_[i].w_h = Upload(op.gru.w_h);
+  }
   {
     // operand images: a buffer gets one when a split-bf16 layer reads it through GemmKernelB3I; it is still stored as plain
     // floats when anything else reads it (the nnet's input / output, an elementwise op, a layer on another kernel)
@@ -920,7 +934,7 @@ std::string Model::Describe() const {
      << " left_context=" << n.left_context << " right_context=" << n.right_context << " priors=" << n.priors.size()
      << " components=" << n.components.size() << " ops=" << n.ops.size() << "\n";
   for (auto &op : n.ops) {
-    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm"};
+    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm", "gru"};
     os << "op: " << kinds[op.kind] << " " << op.name << " out_dim=" << op.out_dim;
     if (op.kind == LayerOp::kGemm) {
       os << " k=" << op.W.cols << " segs=";
@@ -937,6 +951,8 @@ std::string Model::Describe() const {
     if (n.ops[i].kind == LayerOp::kConv) os << "conv: " << DescribeConv(n.ops[i].name, n.ops[i].conv, conv_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)      // (one line per recurrent block)
     if (n.ops[i].kind == LayerOp::kLstm) os << "lstm: " << DescribeLstm(n.ops[i].name, n.ops[i].lstm, lstm_plans_[i]) << "\n";
+  for (size_t i = 0; i < n.ops.size(); i++)
+    if (n.ops[i].kind == LayerOp::kGru) os << "gru: " << DescribeGru(n.ops[i].name, n.ops[i].gru, gru_plans_[i]) << "\n";
   os << "transition_model: tids=" << am_.trans.id2pdf.size() - 1 << " pdfs=" << am_.trans.num_pdfs << "\n";
   if (pruned_from_) os << "output layer: pruned to the " << am_.nnet.output_dim << " of " << pruned_from_ << " pdfs that occur on HCLG arcs\n";
   os << "hclg: states=" << hclg_.num_states() << " arcs=" << hclg_.arcs.size() << " start=" << hclg_.start << "\n";
@@ -1396,6 +1412,37 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       if (images_on)
         for (int b : outs)
           if (b >= 0 && (*imgs)[b].base)
+            LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
+      continue;
+    } else if (op.kind == LayerOp::kGru) {
+      if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
+      const GruBlock &k = op.gru;
+      const BufferInfo &ob = nn.bufs[op.out_buf];
+      const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride);
+      const int outs[3] = {k.hc_buf, k.s_buf, k.y_buf};
+      // (as for an LSTM block: the rows of a stream advance the walk does not reach hold zeros, not what the arena held)
+      if (!rm)
+        for (int b : outs) RS_HIP(hipMemsetAsync(bufp[b], 0, sizeof(float) * (size_t)rows * buf_ld[b], s));
+      GruDev d;
+      std::memset(&d, 0, sizeof(d));
+      d.pre = bufp[k.pre_buf]; d.ld_pre = buf_ld[k.pre_buf];
+      d.hc = bufp[k.hc_buf]; d.ld_hc = buf_ld[k.hc_buf];
+      d.y = bufp[k.y_buf]; d.ld_y = buf_ld[k.y_buf];
+      d.st = bufp[k.s_buf]; d.ld_st = buf_ld[k.s_buf];
+      d.ws_t = gru_dev_[i].ws_t; d.wy_t = gru_dev_[i].wy_t; d.b_y = gru_dev_[i].b_y; d.w_h = gru_dev_[i].w_h;
+      d.cell = k.cell; d.rec = k.rec; d.out_dim = k.rec + k.nonrec;
+      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale;
+      d.norm = k.norm ? 1 : 0; d.norm_alpha = 1.0f / ((float)k.rec * k.target_rms * k.target_rms);
+      d.n_utts = lstm->n_utts; d.L = L_; d.lext = ob.lext; d.rext = ob.rext;
+      d.num_frames = lstm->num_frames; d.row_base = lstm->row_base;
+      d.t0 = lstm->t0; d.slot = lstm->slot; d.lext_cont = k.need_lext;
+      d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
+      if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
+      d.plan = gru_plans_[i];
+      LaunchGru(d, s);
+      if (images_on)
+        for (int b : outs)
+          if ((*imgs)[b].base)
             LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
       continue;
     } else if (op.kind == LayerOp::kGather) {
@@ -2075,9 +2122,11 @@ void Model::BatchIntermediates(const BatchCall &b, const float *ll, int ll_ld, U
     ur.lstm_out.clear();
     ur.lstm_dim.clear();
     for (auto &op : nn.ops) {
-      if (op.kind != LayerOp::kLstm) continue;
+      if (op.kind != LayerOp::kLstm && op.kind != LayerOp::kGru) continue;
       const LstmBlock &k = op.lstm;
-      const int buf = k.proj() ? k.rp_buf : k.cm_buf, col = k.proj() ? 0 : k.cell, dim = k.OutDim(), ld = b.buf_ld[buf];
+      const bool gru = op.kind == LayerOp::kGru;
+      const int buf = gru ? op.gru.y_buf : k.proj() ? k.rp_buf : k.cm_buf, col = gru || k.proj() ? 0 : k.cell;
+      const int dim = gru ? op.gru.rec + op.gru.nonrec : k.OutDim(), ld = b.buf_ld[buf];
       ur.lstm_dim.push_back(dim);
       ur.lstm_out.emplace_back((size_t)T * dim);
       RS_HIP(hipMemcpy2D(ur.lstm_out.back().data(), sizeof(float) * dim, b.bufp[buf] + ((size_t)b.row_base[u] + L_) * ld + col, sizeof(float) * ld,

@@ -67,7 +67,8 @@ struct UttResult {
   // fused stages applied; under --frame-subsampling-factor only the rows the op was evaluated on hold anything)
   std::vector<std::vector<float>> conv_out;
   std::vector<int> conv_dim;
-  // ... per recurrent block, in op order, the rows the layers above read (rp, or m without a projection: T x dim)
+  // ... per recurrent block of either kind, in op order, the rows the layers above read (LSTM: rp, or m without a projection; GRU: y,
+  // before any BatchNorm: T x dim)
   std::vector<std::vector<float>> lstm_out;
   std::vector<int> lstm_dim;
   int feat_dim = 0, ivec_rows = 0, ivec_dim = 0, num_pdfs = 0;
@@ -102,13 +103,16 @@ struct ConvOperands {     // one LayerOp of kind kConv (W in the kernel's order,
 struct LstmOperands {     // one LayerOp of kind kLstm: LstmWeightImages' two matrices, the projection's bias, the nonlinearity's <Params>
   float *wr_t = nullptr, *wrp_t = nullptr, *b_rp = nullptr, *params = nullptr;
 };
+struct GruOperands {      // one LayerOp of kind kGru: GruWeightImages' two matrices, W_y's bias, the nonlinearity's <w_h>
+  float *ws_t = nullptr, *wy_t = nullptr, *b_y = nullptr, *w_h = nullptr;
+};
 // The utterances of the call a recurrent block is walked for (RunNnet): frames and first row of each, in the layout of kernels.h;
 // for a stream advance also the frames each stream had before it and its slot, and the pool's parked state per kLstm op
 struct LstmCall {
   int n_utts = 0;
   const int *num_frames = nullptr, *row_base = nullptr;
   const int *t0 = nullptr, *slot = nullptr;
-  const std::vector<float *> *rings = nullptr;      // indexed like am_.nnet.ops
+  const std::vector<float *> *rings = nullptr;      // indexed like am_.nnet.ops (kLstm and kGru ops)
 };
 
 struct LatArcBuffer { void *d = nullptr; size_t cap = 0; };      // capacity in LatArc records
@@ -383,6 +387,8 @@ class Model {
   std::vector<ConvOperands> conv_dev_;       // indexed like am_.nnet.ops: the convolutions' and gathers' device operands
   std::vector<LstmLaunchPlan> lstm_plans_;   // indexed like am_.nnet.ops: what the planner chose at load for the recurrent blocks
   std::vector<LstmOperands> lstm_dev_;       // indexed like am_.nnet.ops: their device operands
+  std::vector<GruLaunchPlan> gru_plans_;     // the same for the GRU blocks
+  std::vector<GruOperands> gru_dev_;
   float *d_log_priors_ = nullptr;
   HclgDev hclg_dev_{};
   RevGraphDev rev_dev_{};

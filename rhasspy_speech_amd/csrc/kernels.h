@@ -9,6 +9,7 @@
 
 #include "conv_plan.h"
 #include "gemm_launch.h"
+#include "gru_plan.h"
 #include "lstm_plan.h"
 #include "search_plan.h"
 
@@ -174,6 +175,8 @@ void LaunchConv(const ConvDev &d, int rows, hipStream_t s);
 void LaunchGather(const GatherDev &d, int rows, hipStream_t s);
 // The walk of a recurrent block over the chains of a call (nnet_lstm.hip; the descriptor and the load-time plan: lstm_plan.h)
 void LaunchLstm(const LstmDev &d, hipStream_t s);
+// ... of a GRU block (nnet_gru.hip; gru_plan.h)
+void LaunchGru(const GruDev &d, hipStream_t s);
 
 struct SumTermDev { const float *src; int ld, col0, row_off; float scale; };
 struct EltwiseDev {

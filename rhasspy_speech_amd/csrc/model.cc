@@ -838,6 +838,12 @@ int ComponentOutputDim(const Component &c, const std::string &name) {
     if (it == c.m.end() || it->second.rows != 3 || it->second.cols <= 0) Fail("nnet3: LstmNonlinearityComponent '" + name + "' needs a 3-row <Params> matrix");
     return 2 * it->second.cols;
   }
+  if (c.type == "OutputGruNonlinearityComponent" || c.type == "GruNonlinearityComponent") {      // (nnet-combined-component.h: [h | c])
+    if (!c.i.count("<CellDim>") || c.Int("<CellDim>") <= 0) Fail("nnet3: " + c.type + " '" + name + "' has no <CellDim>");
+    if (c.type == "OutputGruNonlinearityComponent" && (!c.v.count("<w_h>") || (int)c.v.at("<w_h>").size() != c.Int("<CellDim>")))
+      Fail("nnet3: OutputGruNonlinearityComponent '" + name + "' needs a <w_h> vector of <CellDim> elements");
+    return 2 * c.Int("<CellDim>");
+  }
   if ((c.type == "DropoutMaskComponent" || c.type == "ElementwiseProductComponent") && c.i.count("<OutputDim>")) return c.Int("<OutputDim>");
   if (c.type == "TimeHeightConvolutionComponent") { const ConvGeom g = ReadConvGeom(c, name); return g.filters_out * g.height_out; }
   if (c.type == "PermuteComponent") {
@@ -897,7 +903,7 @@ void Nnet::Read(KaldiReader &r, int frames_per_chunk, int extra_left_context_ini
   ReadNnetComponents(r, &component_names, &components);
   for (size_t c = 0; c < components.size(); c++)      // (checked before the set-up walks the network with their offsets)
     if (components[c].type == "TimeHeightConvolutionComponent") (void)ReadConvGeom(components[c], component_names[c]);
-  // The network as written, and its cycles: a recurrence that is not a fast-lstm(p) block is refused here, with its node and the
+  // The network as written, and its cycles: a recurrence that is not a fast-lstm(p) or fast-(norm-)opgru block is refused here, with its node and the
   // reason, before the set-up below walks the network.  (Lines this parser does not take may belong to orphan nodes the set-up
   // drops: then the check waits for Compile, which sees the network the set-up leaves.)
   bool parsed = true;
@@ -1073,7 +1079,12 @@ struct BlockNodes {
   int dm = -1;                                       // the DropoutMaskComponent node (use-dropout=true); not part of the cycle
   int delay = 0, cell = 0, rec_dim = 0;              // rec_dim: width of the recurrent input (r, or m without a projection)
   int need_lext = 0;
-  std::vector<int> members;                          // the cycle's nodes
+  // a GRU block (xconfig/gru.py: XconfigFastOpgruLayer :1771-1866, XconfigFastNormOpgruLayer :1994-2111): wa = z_t_pre, nl = gru_nonlin_t,
+  // sc = c_t (a dim-range of nl, read back unscaled), tr = sr = s_t; and
+  bool gru = false;
+  int wo = -1, zs = -1, os = -1, zd = -1, od = -1;   // o_t_pre, the two SigmoidComponent nodes, with dropout the two DropoutComponent nodes
+  int hp = -1, cd = -1, wy = -1, sp = -1, nm = -1;   // hpart_t (not part of the cycle), cdoto, y_t / y_t_tmp, its dim-range, s_t_renorm (norm variant)
+  std::vector<int> members;                          // the cycle's nodes (a GRU block: and hpart_t)
   std::vector<DescPart> x_parts;                     // W_all's input without its recurrent part
 };
 
@@ -1140,7 +1151,12 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
       if (std::find(d.begin(), d.end(), scc[0]) == d.end()) continue;
     }
     auto in_scc = [&](int n) { return std::binary_search(scc.begin(), scc.end(), n); };
+    // (a cycle that holds one of the two GRU nonlinearities is the GRU recogniser's, with wording of its own)
+    bool gru_cycle = false;
+    for (int n : scc) gru_cycle = gru_cycle || comp_type(n) == "OutputGruNonlinearityComponent" || comp_type(n) == "GruNonlinearityComponent";
     auto refuse = [&](int n, const std::string &why) {
+      if (gru_cycle)
+        Fail("nnet3: recurrent GRU networks are supported only as fast-opgru-layer / fast-norm-opgru-layer blocks (cycle at node " + nodes[n].name + ": " + why + ")");
       Fail("nnet3: recurrent networks are supported only as fast-lstmp-layer / fast-lstm-layer blocks (cycle at node " + nodes[n].name + ": " + why + ")");
     };
     BlockNodes b;
@@ -1149,7 +1165,7 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
         if (b.nl >= 0) refuse(n, "a second LstmNonlinearityComponent in one cycle");
         b.nl = n;
       }
-    if (b.nl < 0)
+    if (b.nl < 0 && !gru_cycle)
       refuse(scc[0], "the cycle has no LstmNonlinearityComponent; lstmp-layer (Sigmoid / Tanh / ElementwiseProduct components), lstmb-layer and GRU layers are not supported");
     // a recurrent part: one optional term, Offset(x, -d) with 1 <= d <= kLstmMaxDelay
     auto recurrent_part = [&](int at, const DescPart &p, int *node) {
@@ -1164,6 +1180,133 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
     };
     auto plain_part = [&](const DescPart &p) { return p.terms.size() == 1 && !p.terms[0].const_t && !p.terms[0].optional && p.terms[0].offset == 0 && p.terms[0].scale == 1.0f; };
     auto range_of = [&](int n, int src, int off, int dim) { return nodes[n].kind == NnetNode::kDimRange && nodes[n].range_node == src && nodes[n].range_offset == off && nodes[n].dim == dim; };
+    if (gru_cycle) {
+      b.gru = true;
+      b.nl = -1;
+      for (int n : scc) {
+        if (comp_type(n) == "GruNonlinearityComponent")
+          refuse(n, "a GruNonlinearityComponent (fast-gru-layer, fast-pgru-layer, fast-norm-pgru-layer): its h needs a third serial matrix product, which "
+                    "the HIP kernel does not have");
+        if (comp_type(n) == "OutputGruNonlinearityComponent") {
+          if (b.nl >= 0) refuse(n, "a second OutputGruNonlinearityComponent in one cycle");
+          b.nl = n;
+        }
+      }
+      auto only_input = [&](int n) { const NnetNode &nd = nodes[n]; return nd.input.parts.size() == 1 && plain_part(nd.input.parts[0]) ? nd.input.parts[0].terms[0].node : -1; };
+      auto is_affine = [&](int n) { const std::string t = comp_type(n); return t == "AffineComponent" || t == "NaturalGradientAffineComponent"; };
+      // the nonlinearity: Append(z_t, hpart_t, IfDefined(Offset(c_t, -d)))
+      const NnetNode &nl = nodes[b.nl];
+      const int C = b.cell = nl.dim / 2;
+      if (nl.input.parts.size() != 3) refuse(b.nl, "its input is not Append(z_t, hpart_t, IfDefined(Offset(c_t, -delay)))");
+      for (auto &p : nl.input.parts) if (p.dim != C) refuse(b.nl, "its three inputs are not of the cell's dim");
+      if (!plain_part(nl.input.parts[0]) || !plain_part(nl.input.parts[1])) refuse(b.nl, "its first two inputs are not the nodes z_t and hpart_t");
+      const int z_t = nl.input.parts[0].terms[0].node;
+      b.hp = nl.input.parts[1].terms[0].node;
+      b.delay = recurrent_part(b.nl, nl.input.parts[2], &b.sc);
+      if (!range_of(b.sc, b.nl, C, C)) refuse(b.sc, "the cell state is not the second cell-dim columns of the nonlinearity");
+      // a gate: [DropoutComponent over] a SigmoidComponent over an affine over Append(x, IfDefined(Offset(s_t, -d)))
+      auto gate = [&](int g, int *drop, int *sig, int *aff, int *state) {
+        *drop = -1;
+        if (comp_type(g) == "DropoutComponent") {
+          *drop = g;
+          g = only_input(g);
+          if (g < 0) refuse(*drop, "the dropout's input is not one node");
+        }
+        if (comp_type(g) != "SigmoidComponent") refuse(g, "the gate is not a SigmoidComponent node [behind a DropoutComponent]");
+        *sig = g;
+        const int a = only_input(g);
+        if (a < 0 || !is_affine(a)) refuse(g, "the sigmoid's input is not an affine component node");
+        *aff = a;
+        const NnetNode &an = nodes[a];
+        if (an.input.parts.size() < 2) refuse(a, "its input is not Append(x, IfDefined(Offset(s_t, -delay)))");
+        const int d2 = recurrent_part(a, an.input.parts.back(), state);
+        if (d2 != b.delay) refuse(a, "two different delays in one block, " + std::to_string(d2) + " and " + std::to_string(b.delay));
+        if (an.dim != C) refuse(a, "the gate's affine has " + std::to_string(an.dim) + " rows, not the cell's dim " + std::to_string(C));
+      };
+      int s_z = -1, s_o = -1;
+      gate(z_t, &b.zd, &b.zs, &b.wa, &s_z);
+      // the product Append(c_t, o_t), W_y over it, the state from W_y's first columns
+      b.tr = b.sr = s_z;
+      if (comp_type(b.tr) != "BackpropTruncationComponent") refuse(b.tr, "the recurrent state does not come through a BackpropTruncationComponent");
+      int src = only_input(b.tr);
+      if (src >= 0 && comp_type(src) == "NormalizeComponent") {
+        b.nm = src;
+        const Component &nc = net.components[nodes[b.nm].component];
+        if (nc.f.count("<AddLogStddev>") && nc.f.at("<AddLogStddev>")[0] != 0.0) refuse(b.nm, "a NormalizeComponent with add-log-stddev=true is not supported");
+        if (nc.f.count("<BlockDim>") && nc.Int("<BlockDim>") != (nc.i.count("<InputDim>") ? nc.Int("<InputDim>") : nc.Int("<Dim>")))
+          refuse(b.nm, "a NormalizeComponent with block-dim is not supported");
+        src = only_input(b.nm);
+      }
+      if (src < 0 || nodes[src].kind != NnetNode::kDimRange) refuse(b.tr, "the recurrent state is not a dim-range of W_y's node [through a NormalizeComponent]");
+      b.sp = src;
+      b.wy = nodes[b.sp].range_node;
+      b.rec_dim = nodes[b.sp].dim;
+      if (!is_affine(b.wy) || !range_of(b.sp, b.wy, 0, b.rec_dim) || nodes[b.tr].dim != b.rec_dim)
+        refuse(b.sp, "the recurrent state is not the first columns of an affine component node");
+      b.cd = only_input(b.wy);
+      if (b.cd < 0 || comp_type(b.cd) != "ElementwiseProductComponent") refuse(b.wy, "W_y's input is not an ElementwiseProductComponent node");
+      const NnetNode &cd = nodes[b.cd];
+      if (cd.input.parts.size() != 2 || !plain_part(cd.input.parts[0]) || !plain_part(cd.input.parts[1]) || cd.input.parts[0].terms[0].node != b.sc ||
+          cd.input.parts[1].dim != C || cd.dim != C)
+        refuse(b.cd, "the product's input is not Append(c_t, o_t)");
+      gate(cd.input.parts[1].terms[0].node, &b.od, &b.os, &b.wo, &s_o);
+      if (s_o != b.tr) refuse(b.wo, "the two gates read different recurrent states, " + nodes[s_z].name + " and " + nodes[s_o].name);
+      if ((b.zd >= 0) != (b.od >= 0) || (b.zd >= 0 && nodes[b.zd].component != nodes[b.od].component))
+        refuse(b.zd >= 0 ? b.zd : b.od, "the two gates do not share one DropoutComponent");
+      // the feed-forward input: the same descriptor in front of both gates and under hpart_t
+      const NnetNode &wz = nodes[b.wa], &wo = nodes[b.wo], &hp = nodes[b.hp];
+      b.x_parts.assign(wz.input.parts.begin(), wz.input.parts.end() - 1);
+      auto same_parts = [&](const std::vector<DescPart> &a, size_t na, const std::vector<DescPart> &c) {
+        if (na != c.size()) return false;
+        for (size_t i = 0; i < na; i++) {
+          if (a[i].dim != c[i].dim || a[i].terms.size() != c[i].terms.size()) return false;
+          for (size_t j = 0; j < a[i].terms.size(); j++) {
+            const DescTerm &s = a[i].terms[j], &t = c[i].terms[j];
+            if (s.node != t.node || s.offset != t.offset || s.scale != t.scale || s.const_t != t.const_t || s.optional != t.optional) return false;
+          }
+        }
+        return true;
+      };
+      if (!same_parts(wo.input.parts, wo.input.parts.size() - 1, b.x_parts)) refuse(b.wo, "the two gates do not read the same feed-forward input");
+      if (!is_affine(b.hp) || !same_parts(hp.input.parts, hp.input.parts.size(), b.x_parts))
+        refuse(b.hp, "hpart_t is not an affine component node over the gates' feed-forward input");
+      for (auto &p : b.x_parts) for (auto &t : p.terms) if (in_scc(t.node)) refuse(b.wa, "its feed-forward input reads " + nodes[t.node].name + ", a node of the cycle");
+      b.members = {b.wa, b.wo, b.zs, b.os, b.nl, b.sc, b.cd, b.wy, b.sp, b.tr};
+      for (int n : {b.zd, b.od, b.nm}) if (n >= 0) b.members.push_back(n);
+      std::sort(b.members.begin(), b.members.end());
+      if (std::adjacent_find(b.members.begin(), b.members.end()) != b.members.end()) refuse(b.nl, "a node has two roles in the block");
+      for (int n : scc) if (!std::binary_search(b.members.begin(), b.members.end(), n)) refuse(n, "the node is part of the cycle but not of such a block");
+      for (int n : b.members) if (!in_scc(n)) refuse(n, "the node is not part of the cycle");
+      if (in_scc(b.hp) || (*block_of)[b.hp] >= 0) refuse(b.hp, "hpart_t is part of a cycle");
+      // dims against the weights
+      int x_dim = 0;
+      for (auto &p : b.x_parts) x_dim += p.dim;
+      const int R = b.rec_dim;
+      for (int a : {b.wa, b.wo}) {
+        const MatF &W = net.components[nodes[a].component].m.at("<LinearParams>");
+        if (W.rows != C || W.cols != x_dim + R)
+          refuse(a, "its weights are " + std::to_string(W.rows) + " x " + std::to_string(W.cols) + ", the block needs cell-dim rows and the feed-forward input's " +
+                        std::to_string(x_dim) + " + the recurrent input's " + std::to_string(R) + " columns");
+      }
+      const MatF &Wh = net.components[hp.component].m.at("<LinearParams>"), &Wy = net.components[nodes[b.wy].component].m.at("<LinearParams>");
+      if (Wh.rows != C || Wh.cols != x_dim) refuse(b.hp, "its weights are " + std::to_string(Wh.rows) + " x " + std::to_string(Wh.cols) + ", not cell-dim x the feed-forward input's dim");
+      if (Wy.cols != C || Wy.rows < R) refuse(b.wy, "W_y is " + std::to_string(Wy.rows) + " x " + std::to_string(Wy.cols) + ", the block needs cell-dim columns and at least the recurrent dim's rows");
+      if (nl.input.dim != 3 * C) refuse(b.nl, "its input dim is not 3 x cell-dim");
+      // only what has a buffer may be read from outside the block: the nonlinearity, c_t, W_y's node, its dim-range and the state
+      for (int n = 0; n < N; n++) {
+        if (std::binary_search(b.members.begin(), b.members.end(), n) || index[n] < 0) continue;
+        std::vector<int> d;
+        deps(n, &d);
+        for (int m : d)
+          if (m == b.wa || m == b.wo || m == b.zs || m == b.os || m == b.zd || m == b.od || m == b.cd || m == b.nm || (m == b.hp && n != b.nl))
+            refuse(m, "the node is read from outside the block, by " + nodes[n].name);
+      }
+      b.members.push_back(b.hp);
+      std::sort(b.members.begin(), b.members.end());
+      for (int n : b.members) (*block_of)[n] = (int)blocks->size();
+      blocks->push_back(std::move(b));
+      continue;
+    }
     // the nonlinearity: Append(W_all, IfDefined(Offset(c_trunc, -d)) [, dropout_mask])
     const NnetNode &nl = nodes[b.nl];
     const int C = b.cell = nl.dim / 2;
@@ -1251,7 +1394,8 @@ void Nnet::Compile() {
   int out_node = FindNode("output");
   int in_node = FindNode("input"), iv_node = FindNode("ivector");
   const int N = (int)nodes.size();
-  // recurrent blocks: the cycles of the node graph, each of which has to be what fast-lstmp-layer / fast-lstm-layer emit
+  // recurrent blocks: the cycles of the node graph, each of which has to be what fast-lstmp-layer / fast-lstm-layer or
+  // fast-opgru-layer / fast-norm-opgru-layer emit
   std::vector<BlockNodes> blocks;
   std::vector<int> block_of(N, -1);
   FindBlocks(*this, out_node, &blocks, &block_of);
@@ -1438,6 +1582,68 @@ void Nnet::Compile() {
     if (block_of[n] >= 0) {
       // ---- a recurrent block: the feed-forward columns of W_all as a layer GEMM over all rows (bias included), then the walk
       const BlockNodes &b = blocks[block_of[n]];
+      if (b.gru) {
+        // ---- a GRU block: the x-columns of W_z, W_o and W_hpart stacked to one layer GEMM of 3 cell rows with their biases (each
+        // element's sum over k is what its own affine would compute), then the walk
+        const int C = b.cell, R = b.rec_dim, l = lext[b.wa], r = rext[b.wa];
+        const Component *aff[3] = {&components[nodes[b.wa].component], &components[nodes[b.wo].component], &components[nodes[b.hp].component]};
+        const int in_dim = aff[2]->m.at("<LinearParams>").cols;
+        LayerOp g;
+        g.kind = LayerOp::kGemm;
+        g.name = nodes[b.nl].name + ".x";
+        g.out_dim = 3 * C;
+        g.W.Resize(3 * C, in_dim);
+        g.bias.assign(3 * C, 0.0f);
+        LayerOp w;
+        w.kind = LayerOp::kGru;
+        w.name = nodes[b.nl].name;
+        w.out_dim = 2 * C;
+        GruBlock &k = w.gru;
+        k.W_s.Resize(2 * C, R);
+        for (int a = 0; a < 3; a++) {
+          const MatF &W = aff[a]->m.at("<LinearParams>");
+          for (int row = 0; row < C; row++) {
+            for (int c = 0; c < in_dim; c++) g.W(a * C + row, c) = W(row, c);
+            if (a < 2) for (int c = 0; c < R; c++) k.W_s(a * C + row, c) = W(row, in_dim + c);
+          }
+          auto bit = aff[a]->v.find("<BiasParams>");
+          if (bit != aff[a]->v.end() && !bit->second.empty()) {
+            if ((int)bit->second.size() != C) Fail("nnet3: bias dim mismatch in node " + nodes[a == 0 ? b.wa : a == 1 ? b.wo : b.hp].name);
+            std::copy(bit->second.begin(), bit->second.end(), g.bias.begin() + a * C);
+          }
+        }
+        const int wcol = add_gemm_segs(&g, b.x_parts, b.wa, {0});
+        if (wcol != in_dim) Fail("nnet3: internal error, the feed-forward input of recurrent block " + w.name + " does not cover its weights' columns");
+        g.out_buf = new_buf(3 * C, l, r);
+        ops.push_back(g);
+        const Component &wy = components[nodes[b.wy].component];
+        k.in_dim = in_dim; k.cell = C; k.rec = R; k.nonrec = nodes[b.wy].dim - R;
+        k.delay = b.delay;
+        k.scale = TruncationScale(components[nodes[b.tr].component]);
+        k.norm = b.nm >= 0;
+        if (k.norm) { const Component &nc = components[nodes[b.nm].component]; k.target_rms = nc.f.count("<TargetRms>") ? (float)nc.f.at("<TargetRms>")[0] : 1.0f; }
+        k.dropout = b.zd >= 0;
+        k.w_h = components[nodes[b.nl].component].v.at("<w_h>");
+        k.W_y = wy.m.at("<LinearParams>");
+        auto yb = wy.v.find("<BiasParams>");
+        k.b_y = yb != wy.v.end() && !yb->second.empty() ? yb->second : std::vector<float>(k.W_y.rows, 0.0f);
+        if ((int)k.b_y.size() != k.W_y.rows) Fail("nnet3: bias dim mismatch in node " + nodes[b.wy].name);
+        k.need_lext = b.need_lext;
+        k.pre_buf = g.out_buf;
+        k.hc_buf = new_buf(2 * C, l, r);
+        k.y_buf = new_buf(R + k.nonrec, l, r);
+        k.s_buf = new_buf(R, l, r);
+        node_buf[b.hp] = k.pre_buf;
+        node_col[b.hp] = 2 * C;
+        node_buf[b.nl] = node_buf[b.sc] = k.hc_buf;
+        node_col[b.sc] = C;
+        node_buf[b.wy] = node_buf[b.sp] = k.y_buf;
+        node_buf[b.tr] = k.s_buf;
+        w.out_buf = k.hc_buf;
+        w.terms.push_back({k.pre_buf, 0, 0, 1.0f});
+        ops.push_back(w);
+        continue;
+      }
       const Component &wa = components[nodes[b.wa].component];
       const MatF &W = wa.m.at("<LinearParams>");
       const int C = b.cell, rec = b.rec_dim, in_dim = W.cols - rec, l = lext[b.wa], r = rext[b.wa];
@@ -1700,6 +1906,13 @@ void Nnet::SetSubsampling(int factor) {
         for (int r = 0; r < factor; r++) if (all >> r & 1u) all |= 1u << mod(r - k.delay);
       need[k.cm_buf] = need[k.st_buf] = all;
       if (k.rp_buf >= 0) need[k.rp_buf] = all;
+    }
+    if (it->kind == LayerOp::kGru) {      // (the same rule for a GRU block's three buffers)
+      const GruBlock &k = it->gru;
+      unsigned all = need[k.hc_buf] | need[k.y_buf] | need[k.s_buf];
+      for (int round = 0; round < factor; round++)
+        for (int r = 0; r < factor; r++) if (all >> r & 1u) all |= 1u << mod(r - k.delay);
+      need[k.hc_buf] = need[k.y_buf] = need[k.s_buf] = all;
     }
     const unsigned out = need[it->out_buf];
     auto reads = [&](int src, int off) {

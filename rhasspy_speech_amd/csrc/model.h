@@ -225,10 +225,34 @@ struct LstmBlock {
 };
 constexpr int kLstmMaxDelay = 8;
 
+// A recurrent block of the output-gate projected GRU: what nnet3's fast-opgru-layer / fast-norm-opgru-layer emit (xconfig/gru.py),
+// recognised as a unit (Nnet::Compile).  With s the recurrent state (scaled), c the cell state (read back unscaled), zero where the
+// chain has not started, d the delay, per row t:
+//   z = Sigmoid(pre_z[t] + W_z,s s[t - d]),  o = Sigmoid(pre_o[t] + W_o,s s[t - d])     pre = [W_z,x; W_o,x; W_hpart] x + b, a kGemm op
+//   h = Tanh(pre_h[t] + w_h . c[t - d]);  c = h - z . h + z . c[t - d]                   OutputGruNonlinearityComponent::Propagate
+//   y = W_y (c . o) + b_y                                                                ElementwiseProductComponent, affine
+//   s[t] = scale y[0:rec]   or, norm,   scale Normalize(y[0:rec])                        BackpropTruncationComponent::Propagate
+struct GruBlock {
+  int in_dim = 0, cell = 0, rec = 0, nonrec = 0;
+  int delay = 0;                  // frames towards the past, 1 .. kLstmMaxDelay
+  float scale = 1.0f;
+  bool norm = false;              // fast-norm-opgru-layer: a NormalizeComponent between y[0:rec] and the truncation component
+  float target_rms = 1.0f;        // its <TargetRms>
+  bool dropout = false;           // the norm variant's shared DropoutComponent behind the sigmoids: a copy in test mode
+  MatF W_s;                       // 2 cell x rec: the recurrent columns of W_z over those of W_o
+  std::vector<float> w_h;         // cell
+  MatF W_y;                       // (rec + nonrec) x cell
+  std::vector<float> b_y;
+  // buffers: pre-activations [z | o | hpart] (3 cell), the nonlinearity's output [h | c], y (rec + nonrec), the state s (rec)
+  int pre_buf = -1, hc_buf = -1, y_buf = -1, s_buf = -1;
+  int need_lext = 0;              // as LstmBlock::need_lext
+  int StateDim() const { return cell + rec; }      // a parked state row: [c | s]
+};
+
 struct LayerOp {
   // kConv: out = stages(bias + conv(terms)); kGather: out[:, i] = part(gather_part[i])[:, gather_col[i]] (PermuteComponent over an Append)
-  // kLstm: the serial part of a recurrent block (lstm); out_buf = lstm.cm_buf
-  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm } kind = kGemm;
+  // kLstm: the serial part of a recurrent block (lstm); out_buf = lstm.cm_buf.  kGru: the same of a GRU block (gru); out_buf = gru.hc_buf
+  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm, kGru } kind = kGemm;
   std::string name;
   int out_buf = -1, out_dim = 0;
   // kGemm
@@ -247,6 +271,7 @@ struct LayerOp {
   ConvGeom conv;                           // kConv
   std::vector<int> gather_part, gather_col;   // kGather, per output column: the term and the column inside it
   LstmBlock lstm;                             // kLstm
+  GruBlock gru;                               // kGru
 };
 struct BufferInfo {
   int dim = 0, lext = 0, rext = 0;   // rows cover t in [-lext, T + rext)
@@ -265,7 +290,7 @@ struct Nnet {
   std::vector<BufferInfo> bufs;
   int input_buf = -1, output_buf = -1;
   int left_context = 0, right_context = 0;
-  bool recurrent = false;      // has at least one recurrent block (kLstm op)
+  bool recurrent = false;      // has at least one recurrent block (kLstm or kGru op)
   // What the reference's binaries do to the network before the first frame (nnet3_setup.h): the network is the one
   // CollapseModel leaves behind, and rand() has been called `setup_rand_calls` times (the dither seeds follow from that).
   long setup_rand_calls = 0;

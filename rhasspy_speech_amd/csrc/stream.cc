@@ -159,7 +159,7 @@ struct StreamPool {
   // still be taken, until they are freed or an open / a growing stream needs the room (oldest first)
   std::vector<rs_stream *> ended;
   long long *dec_ctr = nullptr;
-  // Recurrent blocks: per kLstm op (indexed like the network's ops, null elsewhere) and slot, the `delay` state rows [s_c | s_r] the
+  // Recurrent blocks: per kLstm / kGru op (indexed like the network's ops, null elsewhere) and slot, the `delay` state rows [s_c | s_r] the
   // stream's next advance re-enters the block behind -- row (t mod delay) holds the state of the one t in
   // [ll_done - need_lext - delay, ll_done - need_lext) of that class (lstm_plan.h: LstmDev::ring).  Written by the advance that
   // computes those rows, read by the next one; a stream's first advance reads nothing (it starts from zeros), so opening, growing,
@@ -289,6 +289,9 @@ StreamPool *Model::Pool() {
     if (nn.ops[i].kind == LayerOp::kLstm) {
       const LstmBlock &k = nn.ops[i].lstm;
       p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * (k.cell + k.RecDim()) * 4));
+    } else if (nn.ops[i].kind == LayerOp::kGru) {      // (a GRU block's rows are [c | s]: gru_plan.h)
+      const GruBlock &k = nn.ops[i].gru;
+      p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * k.StateDim() * 4));
     }
   if (fc_.ie.present) {
     const int Di = fc_.ie.ivector_dim(), usz = Di * (Di + 1) / 2;

@@ -220,6 +220,12 @@ class ModelSpec:
     # BackpropTruncationComponent's <Scale>, 1 - delay / decay-time in a recipe; default 1), dropout (use-dropout=true with its
     # DropoutMaskComponent node, default False), batchnorm (a BatchNorm on the block's output, default False).
     lstm_layers: Tuple[Dict[str, object], ...] = ()
+    # Recurrent blocks of the output-gate projected GRU (nnet3's fast-opgru-layer / fast-norm-opgru-layer, xconfig/gru.py), placed
+    # like lstm_layers (behind the LSTM blocks of the same `after`).  One dict per block: after, cell, rec, nonrec (both positive),
+    # delay (default 3), scale (the BackpropTruncationComponent's <Scale>, default 1), norm (the norm variant: a NormalizeComponent
+    # in the recurrence and a BatchNorm on the output, default False), dropout (norm variant only: the shared DropoutComponent
+    # behind the two sigmoids, default False).
+    gru_layers: Tuple[Dict[str, object], ...] = ()
 
     @property
     def num_pdfs(self) -> int:
@@ -618,6 +624,109 @@ def _lstm_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.
     return out, out_dim
 
 
+def _w_output_gru_nonlinearity(w: KaldiWriter, w_h: np.ndarray) -> None:
+    # nnet-combined-component.cc:2204-2241 (OutputGruNonlinearityComponent::Write), behind WriteUpdatableCommon
+    cell = w_h.shape[0]
+    _updatable_open(w, "OutputGruNonlinearityComponent")
+    w.token("<CellDim>").i32(cell).token("<w_h>").vector(w_h)
+    w.token("<ValueAvg>").vector(np.zeros(cell, np.float32)).token("<DerivAvg>").vector(np.zeros(cell, np.float32))
+    w.token("<SelfRepairTotal>").f64(0.0).token("<Count>").f64(0.0)
+    w.token("<SelfRepairThreshold>").f32(0.2).token("<SelfRepairScale>").f32(1e-5)
+    w.token("<Alpha>").f32(4.0).token("<Rank>").i32(8).token("<UpdatePeriod>").i32(10)
+    w.token("</OutputGruNonlinearityComponent>")
+
+
+def _w_normalize(w: KaldiWriter, dim: int, target_rms: float = 1.0, add_log_stddev: bool = False) -> None:
+    # nnet-normalize-component.cc:98-111 (<BlockDim> only where it differs from the dim)
+    w.token("<NormalizeComponent>").token("<InputDim>").i32(dim).token("<TargetRms>").f32(target_rms)
+    w.token("<AddLogStddev>").boolean(add_log_stddev).token("</NormalizeComponent>")
+
+
+def _w_dropout(w: KaldiWriter, dim: int, proportion: float = 0.0, per_frame: bool = False) -> None:
+    # nnet-simple-component.cc:225-236
+    w.token("<DropoutComponent>").token("<Dim>").i32(dim).token("<DropoutProportion>").f32(proportion)
+    w.token("<DropoutPerFrame>").boolean(per_frame).token("<TestMode>").boolean(False).token("</DropoutComponent>")
+
+
+def _w_elementwise_product(w: KaldiWriter, input_dim: int, output_dim: int) -> None:
+    # nnet-simple-component.cc:312-319
+    w.token("<ElementwiseProductComponent>").token("<InputDim>").i32(input_dim).token("<OutputDim>").i32(output_dim)
+    w.token("</ElementwiseProductComponent>")
+
+
+def gru_layer_dims(layer: Dict[str, object]) -> Tuple[int, int, int, int]:
+    """(cell, recurrent, non-recurrent, output) dims of a ModelSpec.gru_layers entry."""
+    C, R, P = int(layer["cell"]), int(layer["rec"]), int(layer["nonrec"])
+    if C <= 0 or R <= 0 or P <= 0:
+        raise ValueError("gru layer: cell, rec and nonrec are positive")
+    if layer.get("dropout", False) and not layer.get("norm", False):
+        raise ValueError("gru layer: only the norm variant has the dropout component")
+    return C, R, P, R + P
+
+
+def _gru_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.Generator, name: str, layer: Dict[str, object],
+               prev: str, prev_dim: int) -> Tuple[str, int]:
+    """The components and nodes XconfigFastOpgruLayer / XconfigFastNormOpgruLayer emit (xconfig/gru.py:1823-1866, 2046-2111), in
+    their order.  Returns the node the next layer reads and its dim."""
+    C, R, P, out_dim = gru_layer_dims(layer)
+    d, scale = int(layer.get("delay", 3)), float(layer.get("scale", 1.0))
+    norm, dropout = bool(layer.get("norm", False)), bool(layer.get("dropout", False))
+
+    def randn(o, i):
+        return (rng.standard_normal((o, i)) / math.sqrt(i)).astype(np.float32)
+
+    def randb(n):
+        return (rng.standard_normal(n) * 0.1).astype(np.float32)
+
+    def affine(W, b):
+        return lambda w, W=W, b=b: _w_affine(w, "NaturalGradientAffineComponent", W, b)
+
+    W_z, b_z = np.concatenate([randn(C, prev_dim), randn(C, R)], axis=1), randb(C)
+    W_o, b_o = np.concatenate([randn(C, prev_dim), randn(C, R)], axis=1), randb(C)
+    W_h, b_h = randn(C, prev_dim), randb(C)
+    w_h = (rng.standard_normal(C) * 0.3).astype(np.float32)
+    W_y, b_y = randn(R + P, C), randb(R + P)
+    comps.append((f"{name}.W_z.xs", affine(W_z, b_z)))
+    comps.append((f"{name}.W_o.xs", affine(W_o, b_o)))
+    comps.append((f"{name}.W_hpart.x", affine(W_h, b_h)))
+    comps.append((f"{name}.z", lambda w: _w_nonlinear(w, "SigmoidComponent", C)))
+    comps.append((f"{name}.o", lambda w: _w_nonlinear(w, "SigmoidComponent", C)))
+    if dropout:
+        comps.append((f"{name}.dropout", lambda w: _w_dropout(w, C)))
+    rec = f"IfDefined(Offset({name}.s_t, {-d}))"
+    for g in ("z", "o"):
+        cfg.append(f"component-node name={name}.{g}_t_pre component={name}.W_{g}.xs input=Append({prev}, {rec})")
+        if dropout:
+            cfg.append(f"component-node name={name}.{g}_t_predrop component={name}.{g} input={name}.{g}_t_pre")
+            cfg.append(f"component-node name={name}.{g}_t component={name}.dropout input={name}.{g}_t_predrop")
+        else:
+            cfg.append(f"component-node name={name}.{g}_t component={name}.{g} input={name}.{g}_t_pre")
+    cfg.append(f"component-node name={name}.hpart_t component={name}.W_hpart.x input={prev}")
+    comps.append((f"{name}.gru_nonlin", lambda w: _w_output_gru_nonlinearity(w, w_h)))
+    cfg.append(f"component-node name={name}.gru_nonlin_t component={name}.gru_nonlin "
+               f"input=Append({name}.z_t, {name}.hpart_t, IfDefined(Offset({name}.c_t, {-d})))")
+    cfg.append(f"dim-range-node name={name}.c_t input-node={name}.gru_nonlin_t dim-offset={C} dim={C}")
+    comps.append((f"{name}.cdoto", lambda w: _w_elementwise_product(w, 2 * C, C)))
+    cfg.append(f"component-node name={name}.cdoto component={name}.cdoto input=Append({name}.c_t, {name}.o_t)")
+    comps.append((f"{name}.W_y.cdoto", affine(W_y, b_y)))
+    y = f"{name}.y_t_tmp" if norm else f"{name}.y_t"
+    cfg.append(f"component-node name={y} component={name}.W_y.cdoto input={name}.cdoto")
+    if norm:
+        comps.append((f"{name}.renorm", lambda w: _w_normalize(w, R)))
+    comps.append((f"{name}.s_r", lambda w: _w_backprop_truncation(w, R, scale, d)))
+    if norm:
+        cfg.append(f"dim-range-node name={name}.s_t_pre input-node={y} dim-offset=0 dim={R}")
+        cfg.append(f"component-node name={name}.s_t_renorm component={name}.renorm input={name}.s_t_pre")
+        cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.s_t_renorm")
+        mean, var = (0.1 * rng.standard_normal(out_dim)).astype(np.float32), rng.uniform(0.05, 0.2, out_dim).astype(np.float32)
+        comps.append((f"{name}.batchnorm", lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+        cfg.append(f"component-node name={name}.y_t component={name}.batchnorm input={y}")
+    else:
+        cfg.append(f"dim-range-node name={name}.s_t_preclip input-node={y} dim-offset=0 dim={R}")
+        cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.s_t_preclip")
+    return f"{name}.y_t", out_dim
+
+
 def _append_desc(src: str, offsets: Sequence[int]) -> str:
     parts = [src if o == 0 else f"Offset({src}, {o})" for o in offsets]
     return parts[0] if len(parts) == 1 else "Append(" + ", ".join(parts) + ")"
@@ -701,11 +810,17 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
         for k, layer in enumerate(spec.lstm_layers, start=1):
             if int(layer["after"]) == n_layers:
                 prev, prev_dim = _lstm_block(cfg, comps, rng, f"lstm{k}", layer, prev, prev_dim)
+        for k, layer in enumerate(spec.gru_layers, start=1):
+            if int(layer["after"]) == n_layers:
+                prev, prev_dim = _gru_block(cfg, comps, rng, f"gru{k}", layer, prev, prev_dim)
         return prev, prev_dim
 
     for layer in spec.lstm_layers:
         if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
             raise ValueError("lstm layer: 'after' counts the TDNN layers in front of the block, 1 .. len(layer_offsets)")
+    for layer in spec.gru_layers:
+        if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
+            raise ValueError("gru layer: 'after' counts the TDNN layers in front of the block, 1 .. len(layer_offsets)")
     for li, offs in enumerate(spec.layer_offsets, start=1):
         H = spec.hidden_dim
         prev, prev_dim = lstm_blocks_after(li - 1, prev, prev_dim)
