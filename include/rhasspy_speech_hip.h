@@ -444,7 +444,10 @@ int rs_bind_host_thread(int32_t device_id);
  * model's k-th recurrent block of either kind, in network order, what the layers above it read (an LSTM block: T x (recurrent +
  * non-recurrent) dim: rp, before any BatchNorm; or T x cell dim: m, without a projection; a GRU block: T x (recurrent +
  * non-recurrent) dim: W_y's rows, before any BatchNorm; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
- * hold anything). */
+ * hold anything); 128 + k = the output rows of the model's k-th RestrictedAttentionComponent, in network order (T x heads *
+ * (value-dim [+ num-left-inputs + 1 + num-right-inputs with output-context]): per head the weighted values, then the softmax
+ * weights; before the ReLU / BatchNorm / Normalize nodes behind it; batch calls only; under --frame-subsampling-factor only the rows
+ * the op was evaluated on hold anything). */
 int rs_result_matrix(const rs_result *r, int32_t utt, int32_t kind, const float **data, int32_t *rows, int32_t *cols);
 /* Decoder work counters of one utterance, for the algorithmic-bytes figure of SURVEY.md section 8(d):
  * out[0] = tokens expanded, [1] = arcs examined, [2] = token insertions (FindOrAddToken calls),

@@ -790,8 +790,9 @@ int rs_result_matrix(const rs_result *r, int32_t utt, int32_t kind, const float 
   if (kind == 0) { v = &u->feats; c = u->feat_dim; rws = c ? (int)(v->size() / c) : 0; }
   else if (kind == 1) { v = &u->ivector; c = u->ivec_dim; rws = c ? (int)(v->size() / c) : 0; }
   else if (kind == 2) { v = &u->loglikes; c = u->num_pdfs; rws = c ? (int)(v->size() / c) : 0; }
-  else if (kind >= 64 && kind - 64 < (int)u->lstm_out.size()) { v = &u->lstm_out[kind - 64]; c = u->lstm_dim[kind - 64]; rws = c ? (int)(v->size() / c) : 0; }
-  else if (kind >= 3 && kind - 3 < (int)u->conv_out.size()) { v = &u->conv_out[kind - 3]; c = u->conv_dim[kind - 3]; rws = c ? (int)(v->size() / c) : 0; }
+  else if (kind >= 128 && kind - 128 < (int)u->attention_out.size()) { v = &u->attention_out[kind - 128]; c = u->attention_dim[kind - 128]; rws = c ? (int)(v->size() / c) : 0; }
+  else if (kind >= 64 && kind < 128 && kind - 64 < (int)u->lstm_out.size()) { v = &u->lstm_out[kind - 64]; c = u->lstm_dim[kind - 64]; rws = c ? (int)(v->size() / c) : 0; }
+  else if (kind >= 3 && kind < 64 && kind - 3 < (int)u->conv_out.size()) { v = &u->conv_out[kind - 3]; c = u->conv_dim[kind - 3]; rws = c ? (int)(v->size() / c) : 0; }
   else return ArgError("rs_result_matrix: unknown kind");
   if (v->empty() && c == 0) return ArgError("rs_result_matrix: intermediates were not kept (set rs_decode_opts.keep_intermediates)");
   *data = v->data();

@@ -282,6 +282,9 @@ Model::Model(const std::string &final_mdl, const std::string &hclg, const std::s
   gru_plans_.assign(am_.nnet.ops.size(), GruLaunchPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++)
     if (am_.nnet.ops[i].kind == LayerOp::kGru) gru_plans_[i] = PlanGru(am_.nnet.ops[i].gru, am_.nnet.ops[i].name);
+  attention_plans_.assign(am_.nnet.ops.size(), AttentionLaunchPlan());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++)
+    if (am_.nnet.ops[i].kind == LayerOp::kAttention) attention_plans_[i] = PlanAttention(am_.nnet.ops[i].attention, am_.nnet.ops[i].name);
 }
 
 // rs_decode_opts.prune_output_pdfs: the search looks log-likelihoods up by the pdf of the arc it crosses
@@ -423,7 +426,7 @@ template <typename T> T *Model::Upload(const std::vector<T> &v) { return static_
 
 void Model::BuildGemmPlan(const LayerOp &op, GemmPlan *plan) {
   plan->op = &op;
-  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm || op.kind == LayerOp::kGru) {      // (their own operands: ToDevice; here the bias and the fused stages)
+  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm || op.kind == LayerOp::kGru || op.kind == LayerOp::kAttention) {      // (their own operands: ToDevice; here the bias and the fused stages)
     plan->d_bias = op.bias.empty() ? nullptr : Upload(op.bias);
     plan->d_stage.clear();
     for (auto &st : op.stages) {
@@ -934,7 +937,7 @@ std::string Model::Describe() const {
      << " left_context=" << n.left_context << " right_context=" << n.right_context << " priors=" << n.priors.size()
      << " components=" << n.components.size() << " ops=" << n.ops.size() << "\n";
   for (auto &op : n.ops) {
-    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm", "gru"};
+    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm", "gru", "attention"};
     os << "op: " << kinds[op.kind] << " " << op.name << " out_dim=" << op.out_dim;
     if (op.kind == LayerOp::kGemm) {
       os << " k=" << op.W.cols << " segs=";
@@ -953,6 +956,8 @@ std::string Model::Describe() const {
     if (n.ops[i].kind == LayerOp::kLstm) os << "lstm: " << DescribeLstm(n.ops[i].name, n.ops[i].lstm, lstm_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)
     if (n.ops[i].kind == LayerOp::kGru) os << "gru: " << DescribeGru(n.ops[i].name, n.ops[i].gru, gru_plans_[i]) << "\n";
+  for (size_t i = 0; i < n.ops.size(); i++)      // (one line per attention op: its geometry and what the planner chose for it at load)
+    if (n.ops[i].kind == LayerOp::kAttention) os << "attention: " << DescribeAttention(n.ops[i].name, n.ops[i].attention, attention_plans_[i]) << "\n";
   os << "transition_model: tids=" << am_.trans.id2pdf.size() - 1 << " pdfs=" << am_.trans.num_pdfs << "\n";
   if (pruned_from_) os << "output layer: pruned to the " << am_.nnet.output_dim << " of " << pruned_from_ << " pdfs that occur on HCLG arcs\n";
   os << "hclg: states=" << hclg_.num_states() << " arcs=" << hclg_.arcs.size() << " start=" << hclg_.start << "\n";
@@ -1445,6 +1450,23 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
           if ((*imgs)[b].base)
             LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
       continue;
+    } else if (op.kind == LayerOp::kAttention) {
+      const AttentionGeom &g = op.attention;
+      AttentionDev d;
+      std::memset(&d, 0, sizeof(d));
+      d.src = bufp[op.terms[0].src_buf]; d.ld = buf_ld[op.terms[0].src_buf]; d.col0 = op.terms[0].src_col; d.row_off = op.terms[0].offset;
+      d.heads = g.heads; d.key_dim = g.key_dim; d.value_dim = g.value_dim; d.left = g.left; d.context = g.Context(); d.stride = g.stride;
+      d.output_context = g.output_context ? 1 : 0; d.key_scale = g.key_scale;
+      d.out = bufp[op.out_buf]; d.ldo = buf_ld[op.out_buf];
+      d.plan = attention_plans_[i];
+      const BufferInfo &ob = nn.bufs[op.out_buf];
+      if (const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride)) {     // only the rows somebody reads
+        d.row_map = rm->rows;
+        LaunchAttention(d, rm->count, s);
+        conv_map = rm->rows; conv_rows = rm->count;
+      } else {
+        LaunchAttention(d, rows, s);
+      }
     } else if (op.kind == LayerOp::kGather) {
       GatherDev d;
       std::memset(&d, 0, sizeof(d));
@@ -2117,6 +2139,16 @@ void Model::BatchIntermediates(const BatchCall &b, const float *ll, int ll_ld, U
       ur.conv_out.emplace_back((size_t)T * op.out_dim);
       const int ld = b.buf_ld[op.out_buf];
       RS_HIP(hipMemcpy2D(ur.conv_out.back().data(), sizeof(float) * op.out_dim, b.bufp[op.out_buf] + ((size_t)b.row_base[u] + L_) * ld, sizeof(float) * ld,
+                         sizeof(float) * op.out_dim, T, hipMemcpyDeviceToHost));
+    }
+    ur.attention_out.clear();
+    ur.attention_dim.clear();
+    for (auto &op : nn.ops) {
+      if (op.kind != LayerOp::kAttention) continue;
+      ur.attention_dim.push_back(op.out_dim);
+      ur.attention_out.emplace_back((size_t)T * op.out_dim);
+      const int ld = b.buf_ld[op.out_buf];
+      RS_HIP(hipMemcpy2D(ur.attention_out.back().data(), sizeof(float) * op.out_dim, b.bufp[op.out_buf] + ((size_t)b.row_base[u] + L_) * ld, sizeof(float) * ld,
                          sizeof(float) * op.out_dim, T, hipMemcpyDeviceToHost));
     }
     ur.lstm_out.clear();

@@ -71,6 +71,10 @@ struct UttResult {
   // before any BatchNorm: T x dim)
   std::vector<std::vector<float>> lstm_out;
   std::vector<int> lstm_dim;
+  // the same per attention op: the RestrictedAttentionComponent's output rows (T x heads * (value-dim [+ context positions])), before
+  // the ReLU / BatchNorm / Normalize nodes behind it
+  std::vector<std::vector<float>> attention_out;
+  std::vector<int> attention_dim;
   int feat_dim = 0, ivec_rows = 0, ivec_dim = 0, num_pdfs = 0;
   std::shared_ptr<CompactLat> clat;              // emit_lattice only
 };
@@ -388,6 +392,7 @@ class Model {
   std::vector<LstmLaunchPlan> lstm_plans_;   // indexed like am_.nnet.ops: what the planner chose at load for the recurrent blocks
   std::vector<LstmOperands> lstm_dev_;       // indexed like am_.nnet.ops: their device operands
   std::vector<GruLaunchPlan> gru_plans_;     // the same for the GRU blocks
+  std::vector<AttentionLaunchPlan> attention_plans_;   // the same for the attention ops
   std::vector<GruOperands> gru_dev_;
   float *d_log_priors_ = nullptr;
   HclgDev hclg_dev_{};

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "attention_plan.h"
 #include "conv_plan.h"
 #include "gemm_launch.h"
 #include "gru_plan.h"
@@ -173,6 +174,9 @@ int DeviceNumCu();      // compute units of the current device, asked once per p
 // TimeHeightConvolutionComponent / PermuteComponent (nnet_conv.hip; the descriptors and the load-time plan: conv_plan.h)
 void LaunchConv(const ConvDev &d, int rows, hipStream_t s);
 void LaunchGather(const GatherDev &d, int rows, hipStream_t s);
+
+// RestrictedAttentionComponent (nnet_attention.hip; the descriptor and the load-time plan: attention_plan.h)
+void LaunchAttention(const AttentionDev &d, int rows, hipStream_t s);
 // The walk of a recurrent block over the chains of a call (nnet_lstm.hip; the descriptor and the load-time plan: lstm_plan.h)
 void LaunchLstm(const LstmDev &d, hipStream_t s);
 // ... of a GRU block (nnet_gru.hip; gru_plan.h)

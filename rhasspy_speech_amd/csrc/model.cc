@@ -699,6 +699,41 @@ ConvGeom ReadConvGeom(const Component &c, const std::string &name) {
   return g;
 }
 
+// The fields of a RestrictedAttentionComponent (Write, nnet-attention-component.cc:442-471; the statistics behind <KeyScale> are
+// read and dropped) with what RestrictedAttentionComponent::Check() (:277-289) asks of them.
+AttentionGeom ReadAttentionGeom(const Component &c, const std::string &name, const std::string &node) {
+  const std::string what = "nnet3: RestrictedAttentionComponent '" + name + "'" + (node.empty() ? std::string() : " (node " + node + ")") + ": ";
+  for (const char *k : {"<NumHeads>", "<KeyDim>", "<ValueDim>", "<NumLeftInputs>", "<NumRightInputs>", "<TimeStride>", "<NumLeftInputsRequired>",
+                        "<NumRightInputsRequired>", "<OutputContext>"})
+    if (!c.i.count(k) || c.i.at(k).empty()) Fail(what + "no " + k);
+  if (!c.f.count("<KeyScale>") || c.f.at("<KeyScale>").empty()) Fail(what + "no <KeyScale>");
+  AttentionGeom g;
+  g.heads = c.Int("<NumHeads>"); g.key_dim = c.Int("<KeyDim>"); g.value_dim = c.Int("<ValueDim>");
+  g.left = c.Int("<NumLeftInputs>"); g.right = c.Int("<NumRightInputs>"); g.stride = c.Int("<TimeStride>");
+  g.output_context = c.Int("<OutputContext>") != 0;
+  g.key_scale = (float)c.f.at("<KeyScale>")[0];
+  const int left_req = c.Int("<NumLeftInputsRequired>"), right_req = c.Int("<NumRightInputsRequired>");
+  const double stats_count = c.f.count("<StatsCount>") && !c.f.at("<StatsCount>").empty() ? c.f.at("<StatsCount>")[0] : 0.0;
+  auto check = [&](bool ok, const char *clause) { if (!ok) Fail(what + "Check() fails: " + clause); };
+  check(g.heads > 0 && g.key_dim > 0 && g.value_dim > 0, "num_heads_ > 0 && key_dim_ > 0 && value_dim_ > 0");
+  check(g.left >= 0 && g.right >= 0 && g.left + g.right > 0,
+        "num_left_inputs_ >= 0 && num_right_inputs_ >= 0 && (num_left_inputs_ + num_right_inputs_) > 0");
+  check(g.stride > 0, "time_stride_ > 0");
+  check(left_req >= 0 && left_req <= g.left, "num_left_inputs_required_ >= 0 && num_left_inputs_required_ <= num_left_inputs_");
+  check(right_req >= 0 && right_req <= g.right, "num_right_inputs_required_ >= 0 && num_right_inputs_required_ <= num_right_inputs_");
+  check(g.key_scale > 0.0f && g.key_scale <= 1.0f, "key_scale_ > 0.0 && key_scale_ <= 1.0");
+  check(stats_count >= 0.0, "stats_count_ >= 0.0");
+  // Zero padding in time: a frame whose optional inputs fall outside the chunk's input attends to zero rows in their place, so the
+  // result depends on where the chunk boundaries lie.  Never approximated.
+  if (left_req < g.left)
+    Fail(what + "num-left-inputs-required " + std::to_string(left_req) + " is smaller than num-left-inputs " + std::to_string(g.left) +
+         " (zero padding in time, whose result depends on the frames a chunk holds): not supported by the HIP acoustic-model kernels");
+  if (right_req < g.right)
+    Fail(what + "num-right-inputs-required " + std::to_string(right_req) + " is smaller than num-right-inputs " + std::to_string(g.right) +
+         " (zero padding in time, whose result depends on the frames a chunk holds): not supported by the HIP acoustic-model kernels");
+  return g;
+}
+
 // ---- descriptor parser (nnet3/nnet-descriptor.cc grammar subset) ----
 namespace {
 struct DescParser {
@@ -846,6 +881,7 @@ int ComponentOutputDim(const Component &c, const std::string &name) {
   }
   if ((c.type == "DropoutMaskComponent" || c.type == "ElementwiseProductComponent") && c.i.count("<OutputDim>")) return c.Int("<OutputDim>");
   if (c.type == "TimeHeightConvolutionComponent") { const ConvGeom g = ReadConvGeom(c, name); return g.filters_out * g.height_out; }
+  if (c.type == "RestrictedAttentionComponent") return ReadAttentionGeom(c, name).OutDim();
   if (c.type == "PermuteComponent") {
     auto it = c.iv.find("<ColumnMap>");
     if (it == c.iv.end() || it->second.empty()) Fail("nnet3: PermuteComponent '" + name + "' has no <ColumnMap>");
@@ -887,7 +923,13 @@ void ReadNnetComponents(KaldiReader &r, std::vector<std::string> *names, std::ve
   r.ExpectToken("</Nnet3>");
 }
 
-namespace { void CheckRecurrence(const Nnet &net); }
+namespace {
+void CheckRecurrence(const Nnet &net);
+std::string AttentionInputRefusal(const std::string &node, bool ivector) {
+  if (ivector) return "nnet3: attention node " + node + " reads the iVector input directly: not supported";
+  return "nnet3: attention node " + node + " reads a Sum(), a Scale() or an Append() of several parts directly: its input must be one node or an Offset() of one";
+}
+}  // namespace
 
 void Nnet::Read(KaldiReader &r, int frames_per_chunk, int extra_left_context_initial, int frame_subsampling_factor) {
   r.ExpectToken("<Nnet3>");
@@ -903,12 +945,35 @@ void Nnet::Read(KaldiReader &r, int frames_per_chunk, int extra_left_context_ini
   ReadNnetComponents(r, &component_names, &components);
   for (size_t c = 0; c < components.size(); c++)      // (checked before the set-up walks the network with their offsets)
     if (components[c].type == "TimeHeightConvolutionComponent") (void)ReadConvGeom(components[c], component_names[c]);
+  // (a RestrictedAttentionComponent too; its refusal names the node that runs it, where the config lines parse)
+  {
+    std::vector<std::string> node_of(components.size());
+    for (auto &l : cfg) {
+      std::string first;
+      auto kv = ParseConfigLine(l, &first);
+      if (first != "component-node") continue;
+      auto it = std::find(component_names.begin(), component_names.end(), kv["component"]);
+      if (it != component_names.end() && node_of[it - component_names.begin()].empty()) node_of[it - component_names.begin()] = kv["name"];
+    }
+    for (size_t c = 0; c < components.size(); c++)
+      if (components[c].type == "RestrictedAttentionComponent") (void)ReadAttentionGeom(components[c], component_names[c], node_of[c]);
+  }
   // The network as written, and its cycles: a recurrence that is not a fast-lstm(p) or fast-(norm-)opgru block is refused here, with its node and the
   // reason, before the set-up below walks the network.  (Lines this parser does not take may belong to orphan nodes the set-up
   // drops: then the check waits for Compile, which sees the network the set-up leaves.)
   bool parsed = true;
   try { ParseNodes(cfg); } catch (const Error &) { parsed = false; }
   if (parsed) CheckRecurrence(*this);
+  if (parsed) {
+    // what an attention node may read: one node or an Offset() of one, not the iVector (refused here, with the node, before the
+    // set-up walks a network it would take for something else)
+    const int iv = FindNode("ivector");
+    for (const NnetNode &nd : nodes) {
+      if (nd.kind != NnetNode::kComponent || components[nd.component].type != "RestrictedAttentionComponent") continue;
+      if (nd.input.parts.size() != 1 || nd.input.parts[0].terms.size() != 1 || nd.input.parts[0].terms[0].scale != 1.0f) Fail(AttentionInputRefusal(nd.name, false));
+      if (nd.input.parts[0].terms[0].const_t || nd.input.parts[0].terms[0].node == iv) Fail(AttentionInputRefusal(nd.name, true));
+    }
+  }
   {
     // CollapseModel + the rand() calls of the reference's set-up (nnet3_setup.h); RS_NO_COLLAPSE=1 keeps the layers as
     // written (A/B of the rounding difference; the rand() count is that of the reference either way)
@@ -1441,6 +1506,12 @@ void Nnet::Compile() {
     }
     if (nd.kind == NnetNode::kComponent && components[nd.component].type == "TimeHeightConvolutionComponent")
       return ReadConvGeom(components[nd.component], component_names[nd.component]).time_offsets;
+    if (nd.kind == NnetNode::kComponent && components[nd.component].type == "RestrictedAttentionComponent") {
+      const AttentionGeom g = ReadAttentionGeom(components[nd.component], component_names[nd.component], nd.name);
+      std::vector<int> offs;
+      for (int o = 0; o < g.Context(); o++) offs.push_back(g.TimeOffset(o));
+      return offs;
+    }
     return {0};
   };
   // required extension per node: rows t in [-lext, T+rext)
@@ -1711,9 +1782,10 @@ void Nnet::Compile() {
     const Component *comp = nd.kind == NnetNode::kComponent ? &components[nd.component] : nullptr;
     bool affine = comp && IsAffineLike(comp->type);
     const bool conv = comp && comp->type == "TimeHeightConvolutionComponent", permute = comp && comp->type == "PermuteComponent";
+    const bool attention = comp && comp->type == "RestrictedAttentionComponent";
     std::vector<EltStage> stages;
-    bool elt = !affine && !conv && !permute && (comp == nullptr || EltStagesFor(*comp, nd.name, &stages));
-    if (!affine && !elt && !conv && !permute)
+    bool elt = !affine && !conv && !permute && !attention && (comp == nullptr || EltStagesFor(*comp, nd.name, &stages));
+    if (!affine && !elt && !conv && !permute && !attention)
       Fail("nnet3: component type " + comp->type + " (node " + nd.name + ") is not supported by the HIP acoustic-model kernels");
 
     // ---- fuse an elementwise node into its producer when it is the only consumer of a plain reference
@@ -1726,7 +1798,7 @@ void Nnet::Compile() {
         bool ok = true;
         // a row-wise reduction can only be fused when the op's tile covers the whole row; keep those standalone
         for (auto &s : stages) if (s.kind == EltStage::kLogSoftmax || s.kind == EltStage::kNormalize) ok = false;
-        if (op.kind == LayerOp::kGather) ok = false;      // (a column gather has no epilogue)
+        if (op.kind == LayerOp::kGather || op.kind == LayerOp::kAttention) ok = false;      // (a column gather and the attention kernel have no epilogue)
         if (ok) {
           op.stages.insert(op.stages.end(), stages.begin(), stages.end());
           op.name += "+" + nd.name;
@@ -1769,6 +1841,20 @@ void Nnet::Compile() {
         Fail("nnet3: convolution node " + nd.name + " expects input dim " + std::to_string(op.conv.filters_in * op.conv.height_in) +
              " but its descriptor provides " + std::to_string(nd.input.dim));
       for (int dt : op.conv.time_offsets) op.terms.push_back({b, c, t.offset + dt, 1.0f});
+    } else if (attention) {
+      // one term, the source: the rows of the C context positions follow from the op's geometry (AttentionGeom::TimeOffset)
+      op.kind = LayerOp::kAttention;
+      op.attention = ReadAttentionGeom(*comp, component_names[nd.component], nd.name);
+      if (nd.input.parts.size() != 1 || nd.input.parts[0].terms.size() != 1 || nd.input.parts[0].terms[0].scale != 1.0f)
+        Fail(AttentionInputRefusal(nd.name, false));
+      const DescTerm &t = nd.input.parts[0].terms[0];
+      int b, c;
+      term_src(t, &b, &c);
+      if (b == -2 || t.const_t) Fail(AttentionInputRefusal(nd.name, true));
+      if (nd.input.dim != op.attention.InDim())
+        Fail("nnet3: attention node " + nd.name + " expects input dim " + std::to_string(op.attention.InDim()) + " but its descriptor provides " +
+             std::to_string(nd.input.dim));
+      op.terms.push_back({b, c, t.offset, 1.0f});
     } else if (permute) {
       // out[:, i] = in[:, column_map[i]] (CopyCols, nnet-simple-component.cc:3990-3995) over the parts of an Append
       op.kind = LayerOp::kGather;
@@ -1877,7 +1963,11 @@ void Nnet::Compile() {
         Fail("nnet3: internal error, buffer extents of op " + op.name + " are inconsistent");
     };
     for (auto &s : op.segs) check(s.src_buf, s.offset);
-    for (auto &t : op.terms) check(t.src_buf, t.offset);
+    for (auto &t : op.terms) {
+      check(t.src_buf, t.offset);
+      if (op.kind == LayerOp::kAttention)
+        for (int o = 0; o < op.attention.Context(); o++) check(t.src_buf, t.offset + op.attention.TimeOffset(o));
+    }
     check(op.res_buf, 0);
   }
 }
@@ -1920,7 +2010,12 @@ void Nnet::SetSubsampling(int factor) {
       for (int r = 0; r < factor; r++) if (out >> r & 1u) need[src] |= 1u << mod(r + off);
     };
     for (auto &sg : it->segs) reads(sg.src_buf, sg.offset);
-    for (auto &t : it->terms) reads(t.src_buf, t.offset);
+    for (auto &t : it->terms) {
+      if (it->kind == LayerOp::kAttention)      // (the rows of its context positions)
+        for (int o = 0; o < it->attention.Context(); o++) reads(t.src_buf, t.offset + it->attention.TimeOffset(o));
+      else
+        reads(t.src_buf, t.offset);
+    }
     reads(it->res_buf, 0);
   }
   for (size_t b = 0; b < bufs.size(); b++) if (!bufs[b].is_input && need[b] == 1u) bufs[b].stride = factor;

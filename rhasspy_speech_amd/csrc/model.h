@@ -249,10 +249,27 @@ struct GruBlock {
   int StateDim() const { return cell + rec; }      // a parked state row: [c | s]
 };
 
+// RestrictedAttentionComponent (nnet3/nnet-attention-component.h, attention.h): an input row is `heads` blocks of
+// [key(K) | value(V) | query(K + C)], C = left + 1 + right; an output row is `heads` blocks of [value(V) | c(C) if output_context].
+// Per frame t and head, o = 0 .. C-1:  b[o] = key_scale <query_key(t), key(t + (o - left) stride)> + query_context(t)[o],
+// c = softmax(b), value_out = sum_o c[o] value(t + (o - left) stride).
+struct AttentionGeom {
+  int heads = 0, key_dim = 0, value_dim = 0, left = 0, right = 0, stride = 1;
+  bool output_context = true;
+  float key_scale = 1.0f;
+  int Context() const { return left + 1 + right; }
+  int InDimPerHead() const { return 2 * key_dim + value_dim + Context(); }
+  int OutDimPerHead() const { return value_dim + (output_context ? Context() : 0); }
+  int InDim() const { return heads * InDimPerHead(); }
+  int OutDim() const { return heads * OutDimPerHead(); }
+  int TimeOffset(int o) const { return (o - left) * stride; }
+};
+
 struct LayerOp {
   // kConv: out = stages(bias + conv(terms)); kGather: out[:, i] = part(gather_part[i])[:, gather_col[i]] (PermuteComponent over an Append)
   // kLstm: the serial part of a recurrent block (lstm); out_buf = lstm.cm_buf.  kGru: the same of a GRU block (gru); out_buf = gru.hc_buf
-  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm, kGru } kind = kGemm;
+  // kAttention: out = attention(terms[0]), no fused stage (the result matrix of the op is the component's output): one term, the source; the rows it reads are terms[0].offset + attention.TimeOffset(o)
+  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm, kGru, kAttention } kind = kGemm;
   std::string name;
   int out_buf = -1, out_dim = 0;
   // kGemm
@@ -272,6 +289,7 @@ struct LayerOp {
   std::vector<int> gather_part, gather_col;   // kGather, per output column: the term and the column inside it
   LstmBlock lstm;                             // kLstm
   GruBlock gru;                               // kGru
+  AttentionGeom attention;                    // kAttention
 };
 struct BufferInfo {
   int dim = 0, lext = 0, rext = 0;   // rows cover t in [-lext, T + rext)
@@ -306,6 +324,10 @@ struct Nnet {
 // The geometry of a parsed TimeHeightConvolutionComponent, checked as the reference checks it at load (and refused where its
 // required time offsets are fewer than its time offsets)
 ConvGeom ReadConvGeom(const Component &c, const std::string &name);
+
+// The geometry of a parsed RestrictedAttentionComponent, checked as RestrictedAttentionComponent::Check() checks it; refused
+// (naming `node` where it is known) where a required input count is smaller than the input count: zero padding in time
+AttentionGeom ReadAttentionGeom(const Component &c, const std::string &name, const std::string &node = std::string());
 
 // <NumComponents> ... </Nnet3> (nnet-nnet.cc:608-621)
 void ReadNnetComponents(KaldiReader &r, std::vector<std::string> *names, std::vector<Component> *comps);

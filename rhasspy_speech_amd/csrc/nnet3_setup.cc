@@ -510,7 +510,7 @@ struct Net {
   std::vector<Node> nodes;
   std::vector<std::string> *comp_names;
   std::vector<Component> *comps;
-  mutable std::map<int, std::vector<int32_t>> conv_offsets;   // per convolution component: its distinct time offsets
+  mutable std::map<int, std::vector<int32_t>> conv_offsets;   // per convolution or attention component: its distinct time offsets
 
   std::vector<std::string> Names() const {
     std::vector<std::string> n;
@@ -541,6 +541,17 @@ struct Net {
       for (size_t i = 0; i + 1 < it->second.size(); i += 2) t.push_back(it->second[i]);
       std::sort(t.begin(), t.end());
       t.erase(std::unique(t.begin(), t.end()), t.end());
+      return &(conv_offsets[c] = t);
+    }
+    if (k.type == "RestrictedAttentionComponent") {
+      // GetInputIndexes asks for t + (o - num-left-inputs) * time-stride, o = 0 .. context-dim - 1, and IsComputable needs the
+      // required ones (nnet-attention-component.cc:507-571) -- all of them in every model that loads (model.cc: ReadAttentionGeom).
+      // ReorderIndexes and PrecomputeIndexes (:376-440, :622-644) draw nothing.
+      auto have = conv_offsets.find(c);
+      if (have != conv_offsets.end()) return &have->second;
+      const AttentionGeom g = ReadAttentionGeom(k, (*comp_names)[c]);
+      std::vector<int32_t> t;
+      for (int o = 0; o < g.Context(); o++) t.push_back(g.TimeOffset(o));
       return &(conv_offsets[c] = t);
     }
     if (k.type != "TdnnComponent") return nullptr;

@@ -226,6 +226,12 @@ class ModelSpec:
     # in the recurrence and a BatchNorm on the output, default False), dropout (norm variant only: the shared DropoutComponent
     # behind the two sigmoids, default False).
     gru_layers: Tuple[Dict[str, object], ...] = ()
+    # Time-restricted self-attention layers between the TDNN layers (xconfig/attention.py), placed like lstm_layers (behind the
+    # recurrent blocks of the same `after`).  One dict per layer: after, heads, key_dim, value_dim, left, right (num-left-inputs,
+    # num-right-inputs), stride (time-stride); optional left_required, right_required (default -1: all of them), key_scale (default
+    # 1 / sqrt(key_dim)), output_context (default True); form, one of ATTENTION_FORMS (default attention-relu-renorm-layer);
+    # logit_gain (default 1: a factor on the key and query rows of the layer's affine, weights and bias).
+    attention_layers: Tuple[Dict[str, object], ...] = ()
 
     @property
     def num_pdfs(self) -> int:
@@ -727,6 +733,73 @@ def _gru_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.G
     return f"{name}.y_t", out_dim
 
 
+ATTENTION_FORMS = ("attention-renorm-layer", "attention-relu-renorm-layer", "attention-relu-batchnorm-layer", "relu-renorm-attention-layer")
+
+
+def attention_layer_dims(layer: Dict[str, object]) -> Tuple[int, int, int]:
+    """(context positions, input dim, output dim) of a ModelSpec.attention_layers entry (attention.py:91-107)."""
+    H, K, V = int(layer["heads"]), int(layer["key_dim"]), int(layer["value_dim"])
+    C = int(layer["left"]) + 1 + int(layer["right"])
+    return C, H * (2 * K + V + C), H * (V + (C if layer.get("output_context", True) else 0))
+
+
+def attention_key_scale(layer: Dict[str, object]) -> float:
+    return float(layer["key_scale"]) if "key_scale" in layer else 1.0 / math.sqrt(int(layer["key_dim"]))
+
+
+def _w_attention(w: KaldiWriter, layer: Dict[str, object]) -> None:
+    # nnet-attention-component.cc:442-471 (RestrictedAttentionComponent::Write); no statistics stored
+    left, right = int(layer["left"]), int(layer["right"])
+    left_req, right_req = int(layer.get("left_required", -1)), int(layer.get("right_required", -1))
+    w.token("<RestrictedAttentionComponent>").token("<NumHeads>").i32(int(layer["heads"]))
+    w.token("<KeyDim>").i32(int(layer["key_dim"])).token("<ValueDim>").i32(int(layer["value_dim"]))
+    w.token("<NumLeftInputs>").i32(left).token("<NumRightInputs>").i32(right).token("<TimeStride>").i32(int(layer.get("stride", 1)))
+    w.token("<NumLeftInputsRequired>").i32(left if left_req < 0 else left_req)
+    w.token("<NumRightInputsRequired>").i32(right if right_req < 0 else right_req)
+    w.token("<OutputContext>").boolean(bool(layer.get("output_context", True)))
+    w.token("<KeyScale>").f32(attention_key_scale(layer))
+    w.token("<StatsCount>").f64(0.0).token("<EntropyStats>").vector(np.zeros(0), double=True)
+    w.token("<PosteriorStats>").matrix(np.zeros((0, 0)), double=True)
+    w.token("</RestrictedAttentionComponent>")
+
+
+def _attention_layer(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.Generator, name: str, layer: Dict[str, object],
+                     prev: str, prev_dim: int) -> Tuple[str, int]:
+    """The components and nodes XconfigAttentionLayer emits (xconfig/attention.py:139-249), in their order: the affine, then one node
+    per word of the layer's name.  Returns the node the next layer reads and its dim."""
+    form = str(layer.get("form", "attention-relu-renorm-layer"))
+    if form not in ATTENTION_FORMS:
+        raise ValueError(f"attention layer: form {form!r}: one of {ATTENTION_FORMS}")
+    H, K, V = int(layer["heads"]), int(layer["key_dim"]), int(layer["value_dim"])
+    C, in_dim, out_dim = attention_layer_dims(layer)
+    W = (rng.standard_normal((in_dim, prev_dim)) / math.sqrt(prev_dim)).astype(np.float32)
+    b = (rng.standard_normal(in_dim) * 0.1).astype(np.float32)
+    gain = np.float32(layer.get("logit_gain", 1.0))
+    if gain != 1.0:
+        per_head = 2 * K + V + C
+        for h in range(H):
+            for lo, hi in ((0, K), (K + V, per_head)):      # the key rows, the query rows (key part and context part)
+                W[h * per_head + lo:h * per_head + hi] *= gain
+                b[h * per_head + lo:h * per_head + hi] *= gain
+    comps.append((f"{name}.affine", lambda w, W=W, b=b: _w_affine(w, "NaturalGradientAffineComponent", W, b)))
+    cfg.append(f"component-node name={name}.affine component={name}.affine input={prev}")
+    cur, dim = f"{name}.affine", in_dim
+    for word in form.split("-")[:-1]:
+        if word == "relu":
+            comps.append((f"{name}.relu", lambda w, d=dim: _w_nonlinear(w, "RectifiedLinearComponent", d)))
+        elif word == "attention":
+            comps.append((f"{name}.attention", lambda w, l=dict(layer): _w_attention(w, l)))
+            dim = out_dim
+        elif word == "renorm":
+            comps.append((f"{name}.renorm", lambda w, d=dim: _w_normalize(w, d)))
+        else:
+            mean, var = (0.1 * rng.standard_normal(dim)).astype(np.float32), rng.uniform(0.05, 0.2, dim).astype(np.float32)
+            comps.append((f"{name}.batchnorm", lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+        cfg.append(f"component-node name={name}.{word} component={name}.{word} input={cur}")
+        cur = f"{name}.{word}"
+    return cur, dim
+
+
 def _append_desc(src: str, offsets: Sequence[int]) -> str:
     parts = [src if o == 0 else f"Offset({src}, {o})" for o in offsets]
     return parts[0] if len(parts) == 1 else "Append(" + ", ".join(parts) + ")"
@@ -813,6 +886,9 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
         for k, layer in enumerate(spec.gru_layers, start=1):
             if int(layer["after"]) == n_layers:
                 prev, prev_dim = _gru_block(cfg, comps, rng, f"gru{k}", layer, prev, prev_dim)
+        for k, layer in enumerate(spec.attention_layers, start=1):
+            if int(layer["after"]) == n_layers:
+                prev, prev_dim = _attention_layer(cfg, comps, rng, f"attention{k}", layer, prev, prev_dim)
         return prev, prev_dim
 
     for layer in spec.lstm_layers:
@@ -821,6 +897,9 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
     for layer in spec.gru_layers:
         if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
             raise ValueError("gru layer: 'after' counts the TDNN layers in front of the block, 1 .. len(layer_offsets)")
+    for layer in spec.attention_layers:
+        if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
+            raise ValueError("attention layer: 'after' counts the TDNN layers in front of the layer, 1 .. len(layer_offsets)")
     for li, offs in enumerate(spec.layer_offsets, start=1):
         H = spec.hidden_dim
         prev, prev_dim = lstm_blocks_after(li - 1, prev, prev_dim)
