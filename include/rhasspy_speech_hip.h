@@ -118,8 +118,17 @@ const char *rs_last_error(void);
  * the affine W_y, the dim-range [0, R) of W_y's node, optionally a NormalizeComponent (no add-log-stddev, no block-dim), and one
  * BackpropTruncationComponent whose node is s_t; a BatchNorm on W_y's node is an ordinary layer.  The same delays and the limits
  * cell dim <= 2048, R + P <= 4096, 64 * (2 * R + cell dim + 12) bytes <= 144 KiB of LDS (dims rounded up to 16).  Refused, in a
- * sentence of their own that names the node and the reason: anything else in a cycle that holds an OutputGruNonlinearityComponent,
- * and every cycle that holds a GruNonlinearityComponent (fast-gru-layer, fast-pgru-layer, fast-norm-pgru-layer); the non-fast
+ * sentence of their own that names the node and the reason: anything else in a cycle that holds an OutputGruNonlinearityComponent.
+ * Or a cycle may be what fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer emit (TDNN-PGRU recipes; the plain GRU): the
+ * affines W_z (cell-dim rows) and W_r (R rows) over Append(x, IfDefined(Offset(s_t, -d))), each behind a SigmoidComponent [and a
+ * DropoutComponent each, copies in test mode], W_hpart over the same x, a GruNonlinearityComponent (<CellDim>, <RecurrentDim> R,
+ * <w_h> a cell x R matrix) over Append(z_t, r_t, hpart_t, IfDefined(Offset(c_t, -d)), IfDefined(Offset(s_t, -d))) with c_t its
+ * second cell-dim columns, the affine W_y over c_t, the dim-range [0, R) of W_y's node, optionally a NormalizeComponent, and one
+ * BackpropTruncationComponent whose node is s_t; fast-gru-layer: R = cell dim, a four-part input without c_t, no W_y, s_t the
+ * truncation component over the nonlinearity's second cell-dim columns.  The same delays; cell dim <= 2048, R + P <= 4096,
+ * 64 * (3 * R + cell dim + 16) bytes <= 144 KiB of LDS, without a projection 64 * (3 * cell dim + 12) bytes (dims rounded up to 16: a
+ * cell dim of 752 at most).  Anything else in a cycle that holds a GruNonlinearityComponent is refused in that sentence, extended
+ * by these three layers.  The non-fast
  * gru-layer / pgru-layer / opgru-layer and their norm forms (cells of Sigmoid / Tanh / ElementwiseProduct components without either
  * nonlinearity) are refused like lstmp-layer.  The
  * rand() calls of a recurrent compilation are not replayed, so such a model loads only with --dither=0 in its mfcc.conf / fbank.conf
@@ -144,7 +153,10 @@ void rs_model_free(rs_model *model);
  * feed-forward + recurrent, cell and projection tiles, the grid rule.  Then one `gru:` line per GRU block: name, input dim, cell /
  * recurrent / non-recurrent dims, delay, the truncation component's scale, norm=0|1 (a NormalizeComponent in the recurrence),
  * dropout=0|1, the kernel instantiation, chains per workgroup, LDS bytes, the split of W_z's and W_o's columns, cell and output tiles,
- * the grid rule; its `op: gru` line follows the `op: gemm` of the stacked feed-forward columns (3 x cell dim rows).  Two lines are state, not structure: `layer_gemm:` and
+ * the grid rule; its `op: gru` line follows the `op: gemm` of the stacked feed-forward columns (3 x cell dim rows).  Then one `pgru:` line per
+ * block around a GruNonlinearityComponent: the same fields (rec=0 nonrec=0: fast-gru-layer), the split of W_z's and W_r's columns
+ * (w_zr), cell, recurrent and output tiles; its `op: pgru` line follows the `op: gemm` of the stacked feed-forward columns (2 x cell
+ * dim + R rows).  Two lines are state, not structure: `layer_gemm:` and
  *   arenas: device blocks=B bytes=N allocations=A; host blocks=B bytes=N allocations=A
  * summed over the model's decode contexts: the blocks and bytes their per-call arenas hold now, and the hipMalloc / hipHostMalloc
  * calls they have made since the model was loaded.  `allocations` stands still once every context has seen its largest call twice.
@@ -441,9 +453,9 @@ int rs_bind_host_thread(int32_t device_id);
 /* Parity taps (only with opts.keep_intermediates): kind 0 = nnet input features (T x C), 1 = iVector
  * (n x D_iv: one row offline, one row per nnet chunk for streams), 2 = log-likelihoods (T x P); 3 + k = the output of the
  * model's k-th convolution (T x heights * filters, ReLU and BatchNorm applied; batch calls only); 64 + k = the output rows of the
- * model's k-th recurrent block of either kind, in network order, what the layers above it read (an LSTM block: T x (recurrent +
- * non-recurrent) dim: rp, before any BatchNorm; or T x cell dim: m, without a projection; a GRU block: T x (recurrent +
- * non-recurrent) dim: W_y's rows, before any BatchNorm; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
+ * model's k-th recurrent block of any kind, in network order, what the layers above it read (an LSTM block: T x (recurrent +
+ * non-recurrent) dim: rp, before any BatchNorm; or T x cell dim: m, without a projection; an OPGRU or PGRU block: T x (recurrent +
+ * non-recurrent) dim: W_y's rows, before any BatchNorm; a fast-gru-layer block: T x cell dim: c; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
  * hold anything); 128 + k = the output rows of the model's k-th RestrictedAttentionComponent, in network order (T x heads *
  * (value-dim [+ num-left-inputs + 1 + num-right-inputs with output-context]): per head the weighted values, then the softmax
  * weights; before the ReLU / BatchNorm / Normalize nodes behind it; batch calls only; under --frame-subsampling-factor only the rows

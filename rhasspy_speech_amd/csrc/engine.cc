@@ -282,6 +282,9 @@ Model::Model(const std::string &final_mdl, const std::string &hclg, const std::s
   gru_plans_.assign(am_.nnet.ops.size(), GruLaunchPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++)
     if (am_.nnet.ops[i].kind == LayerOp::kGru) gru_plans_[i] = PlanGru(am_.nnet.ops[i].gru, am_.nnet.ops[i].name);
+  pgru_plans_.assign(am_.nnet.ops.size(), PgruLaunchPlan());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++)
+    if (am_.nnet.ops[i].kind == LayerOp::kPgru) pgru_plans_[i] = PlanPgru(am_.nnet.ops[i].pgru, am_.nnet.ops[i].name);
   attention_plans_.assign(am_.nnet.ops.size(), AttentionLaunchPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++)
     if (am_.nnet.ops[i].kind == LayerOp::kAttention) attention_plans_[i] = PlanAttention(am_.nnet.ops[i].attention, am_.nnet.ops[i].name);
@@ -426,7 +429,7 @@ template <typename T> T *Model::Upload(const std::vector<T> &v) { return static_
 
 void Model::BuildGemmPlan(const LayerOp &op, GemmPlan *plan) {
   plan->op = &op;
-  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm || op.kind == LayerOp::kGru || op.kind == LayerOp::kAttention) {      // (their own operands: ToDevice; here the bias and the fused stages)
+  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm || op.kind == LayerOp::kGru || op.kind == LayerOp::kPgru || op.kind == LayerOp::kAttention) {      // (their own operands: ToDevice; here the bias and the fused stages)
     plan->d_bias = op.bias.empty() ? nullptr : Upload(op.bias);
     plan->d_stage.clear();
     for (auto &st : op.stages) {
@@ -758,6 +761,19 @@ void Model::ToDevice() {
     gru_dev_[i].b_y = Upload(op.gru.b_y);
     gru_dev_[i].w_h = Upload(op.gru.w_h);
   }
+  pgru_dev_.assign(am_.nnet.ops.size(), PgruOperands());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++) {
+    const LayerOp &op = am_.nnet.ops[i];
+    if (op.kind != LayerOp::kPgru) continue;
+    std::vector<float> wr_t, wzh_t, wy_t;
+    PgruWeightImages(op.pgru, pgru_plans_[i], &wr_t, &wzh_t, &wy_t);
+    pgru_dev_[i].wr_t = Upload(wr_t);
+    pgru_dev_[i].wzh_t = Upload(wzh_t);
+    if (op.pgru.proj()) {
+      pgru_dev_[i].wy_t = Upload(wy_t);
+      pgru_dev_[i].b_y = Upload(op.pgru.b_y);
+    }
+  }
   {
     // operand images: a buffer gets one when a split-bf16 layer reads it through GemmKernelB3I; it is still stored as plain
     // floats when anything else reads it (the nnet's input / output, an elementwise op, a layer on another kernel)
@@ -937,7 +953,7 @@ std::string Model::Describe() const {
      << " left_context=" << n.left_context << " right_context=" << n.right_context << " priors=" << n.priors.size()
      << " components=" << n.components.size() << " ops=" << n.ops.size() << "\n";
   for (auto &op : n.ops) {
-    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm", "gru", "attention"};
+    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm", "gru", "attention", "pgru"};
     os << "op: " << kinds[op.kind] << " " << op.name << " out_dim=" << op.out_dim;
     if (op.kind == LayerOp::kGemm) {
       os << " k=" << op.W.cols << " segs=";
@@ -956,6 +972,8 @@ std::string Model::Describe() const {
     if (n.ops[i].kind == LayerOp::kLstm) os << "lstm: " << DescribeLstm(n.ops[i].name, n.ops[i].lstm, lstm_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)
     if (n.ops[i].kind == LayerOp::kGru) os << "gru: " << DescribeGru(n.ops[i].name, n.ops[i].gru, gru_plans_[i]) << "\n";
+  for (size_t i = 0; i < n.ops.size(); i++)
+    if (n.ops[i].kind == LayerOp::kPgru) os << "pgru: " << DescribePgru(n.ops[i].name, n.ops[i].pgru, pgru_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)      // (one line per attention op: its geometry and what the planner chose for it at load)
     if (n.ops[i].kind == LayerOp::kAttention) os << "attention: " << DescribeAttention(n.ops[i].name, n.ops[i].attention, attention_plans_[i]) << "\n";
   os << "transition_model: tids=" << am_.trans.id2pdf.size() - 1 << " pdfs=" << am_.trans.num_pdfs << "\n";
@@ -1448,6 +1466,38 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       if (images_on)
         for (int b : outs)
           if ((*imgs)[b].base)
+            LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
+      continue;
+    } else if (op.kind == LayerOp::kPgru) {
+      if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
+      const PgruBlock &k = op.pgru;
+      const BufferInfo &ob = nn.bufs[op.out_buf];
+      const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride);
+      const int outs[3] = {k.hc_buf, k.s_buf, k.y_buf};      // (y_buf: -1 without a projection)
+      // (as for an LSTM block: the rows of a stream advance the walk does not reach hold zeros, not what the arena held)
+      if (!rm)
+        for (int b : outs)
+          if (b >= 0) RS_HIP(hipMemsetAsync(bufp[b], 0, sizeof(float) * (size_t)rows * buf_ld[b], s));
+      PgruDev d;
+      std::memset(&d, 0, sizeof(d));
+      d.pre = bufp[k.pre_buf]; d.ld_pre = buf_ld[k.pre_buf];
+      d.hc = bufp[k.hc_buf]; d.ld_hc = buf_ld[k.hc_buf];
+      if (k.proj()) { d.y = bufp[k.y_buf]; d.ld_y = buf_ld[k.y_buf]; }
+      d.st = bufp[k.s_buf]; d.ld_st = buf_ld[k.s_buf];
+      d.wr_t = pgru_dev_[i].wr_t; d.wzh_t = pgru_dev_[i].wzh_t; d.wy_t = pgru_dev_[i].wy_t; d.b_y = pgru_dev_[i].b_y;
+      d.cell = k.cell; d.rec = k.RecDim(); d.out_dim = k.rec + k.nonrec; d.proj = k.proj() ? 1 : 0;
+      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale;
+      d.norm = k.norm ? 1 : 0; d.norm_alpha = 1.0f / ((float)k.RecDim() * k.target_rms * k.target_rms);
+      d.n_utts = lstm->n_utts; d.L = L_; d.lext = ob.lext; d.rext = ob.rext;
+      d.num_frames = lstm->num_frames; d.row_base = lstm->row_base;
+      d.t0 = lstm->t0; d.slot = lstm->slot; d.lext_cont = k.need_lext;
+      d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
+      if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
+      d.plan = pgru_plans_[i];
+      LaunchPgru(d, s);
+      if (images_on)
+        for (int b : outs)
+          if (b >= 0 && (*imgs)[b].base)
             LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
       continue;
     } else if (op.kind == LayerOp::kAttention) {
@@ -2154,11 +2204,13 @@ void Model::BatchIntermediates(const BatchCall &b, const float *ll, int ll_ld, U
     ur.lstm_out.clear();
     ur.lstm_dim.clear();
     for (auto &op : nn.ops) {
-      if (op.kind != LayerOp::kLstm && op.kind != LayerOp::kGru) continue;
+      if (op.kind != LayerOp::kLstm && op.kind != LayerOp::kGru && op.kind != LayerOp::kPgru) continue;
       const LstmBlock &k = op.lstm;
-      const bool gru = op.kind == LayerOp::kGru;
-      const int buf = gru ? op.gru.y_buf : k.proj() ? k.rp_buf : k.cm_buf, col = gru || k.proj() ? 0 : k.cell;
-      const int dim = gru ? op.gru.rec + op.gru.nonrec : k.OutDim(), ld = b.buf_ld[buf];
+      const bool gru = op.kind == LayerOp::kGru, pgru = op.kind == LayerOp::kPgru;
+      // (a block around a GruNonlinearityComponent: W_y's rows, without a projection the c columns of [h | c])
+      const int buf = pgru ? (op.pgru.proj() ? op.pgru.y_buf : op.pgru.hc_buf) : gru ? op.gru.y_buf : k.proj() ? k.rp_buf : k.cm_buf;
+      const int col = pgru ? (op.pgru.proj() ? 0 : op.pgru.cell) : gru || k.proj() ? 0 : k.cell;
+      const int dim = pgru ? op.pgru.OutDim() : gru ? op.gru.rec + op.gru.nonrec : k.OutDim(), ld = b.buf_ld[buf];
       ur.lstm_dim.push_back(dim);
       ur.lstm_out.emplace_back((size_t)T * dim);
       RS_HIP(hipMemcpy2D(ur.lstm_out.back().data(), sizeof(float) * dim, b.bufp[buf] + ((size_t)b.row_base[u] + L_) * ld + col, sizeof(float) * ld,

@@ -67,8 +67,8 @@ struct UttResult {
   // fused stages applied; under --frame-subsampling-factor only the rows the op was evaluated on hold anything)
   std::vector<std::vector<float>> conv_out;
   std::vector<int> conv_dim;
-  // ... per recurrent block of either kind, in op order, the rows the layers above read (LSTM: rp, or m without a projection; GRU: y,
-  // before any BatchNorm: T x dim)
+  // ... per recurrent block of any kind, in op order, the rows the layers above read (LSTM: rp, or m without a projection; OPGRU and
+  // PGRU: y, before any BatchNorm; fast-gru-layer: c: T x dim)
   std::vector<std::vector<float>> lstm_out;
   std::vector<int> lstm_dim;
   // the same per attention op: the RestrictedAttentionComponent's output rows (T x heads * (value-dim [+ context positions])), before
@@ -109,6 +109,9 @@ struct LstmOperands {     // one LayerOp of kind kLstm: LstmWeightImages' two ma
 };
 struct GruOperands {      // one LayerOp of kind kGru: GruWeightImages' two matrices, W_y's bias, the nonlinearity's <w_h>
   float *ws_t = nullptr, *wy_t = nullptr, *b_y = nullptr, *w_h = nullptr;
+};
+struct PgruOperands {     // one LayerOp of kind kPgru: PgruWeightImages' three matrices, W_y's bias (the last two null without a projection)
+  float *wr_t = nullptr, *wzh_t = nullptr, *wy_t = nullptr, *b_y = nullptr;
 };
 // The utterances of the call a recurrent block is walked for (RunNnet): frames and first row of each, in the layout of kernels.h;
 // for a stream advance also the frames each stream had before it and its slot, and the pool's parked state per kLstm op
@@ -394,6 +397,8 @@ class Model {
   std::vector<GruLaunchPlan> gru_plans_;     // the same for the GRU blocks
   std::vector<AttentionLaunchPlan> attention_plans_;   // the same for the attention ops
   std::vector<GruOperands> gru_dev_;
+  std::vector<PgruLaunchPlan> pgru_plans_;   // ... and for the blocks around a GruNonlinearityComponent
+  std::vector<PgruOperands> pgru_dev_;
   float *d_log_priors_ = nullptr;
   HclgDev hclg_dev_{};
   RevGraphDev rev_dev_{};

@@ -12,6 +12,7 @@
 #include "gemm_launch.h"
 #include "gru_plan.h"
 #include "lstm_plan.h"
+#include "pgru_plan.h"
 #include "search_plan.h"
 
 namespace rs {
@@ -181,6 +182,8 @@ void LaunchAttention(const AttentionDev &d, int rows, hipStream_t s);
 void LaunchLstm(const LstmDev &d, hipStream_t s);
 // ... of a GRU block (nnet_gru.hip; gru_plan.h)
 void LaunchGru(const GruDev &d, hipStream_t s);
+// ... of a block around a GruNonlinearityComponent (nnet_pgru.hip; pgru_plan.h)
+void LaunchPgru(const PgruDev &d, hipStream_t s);
 
 struct SumTermDev { const float *src; int ld, col0, row_off; float scale; };
 struct EltwiseDev {

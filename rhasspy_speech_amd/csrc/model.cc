@@ -1147,6 +1147,10 @@ struct BlockNodes {
   // a GRU block (xconfig/gru.py: XconfigFastOpgruLayer :1771-1866, XconfigFastNormOpgruLayer :1994-2111): wa = z_t_pre, nl = gru_nonlin_t,
   // sc = c_t (a dim-range of nl, read back unscaled), tr = sr = s_t; and
   bool gru = false;
+  // a block around a GruNonlinearityComponent (XconfigFastPgruLayer, XconfigFastNormPgruLayer, XconfigFastGruLayer): the same fields with
+  // the reset gate r in the output gate's place (wo = r_t_pre, os / od = its sigmoid / dropout node), no cdoto; without a projection
+  // no wy, sp, nm either, and sc = y_t
+  bool pgru = false;
   int wo = -1, zs = -1, os = -1, zd = -1, od = -1;   // o_t_pre, the two SigmoidComponent nodes, with dropout the two DropoutComponent nodes
   int hp = -1, cd = -1, wy = -1, sp = -1, nm = -1;   // hpart_t (not part of the cycle), cdoto, y_t / y_t_tmp, its dim-range, s_t_renorm (norm variant)
   std::vector<int> members;                          // the cycle's nodes (a GRU block: and hpart_t)
@@ -1219,7 +1223,13 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
     // (a cycle that holds one of the two GRU nonlinearities is the GRU recogniser's, with wording of its own)
     bool gru_cycle = false;
     for (int n : scc) gru_cycle = gru_cycle || comp_type(n) == "OutputGruNonlinearityComponent" || comp_type(n) == "GruNonlinearityComponent";
+    // (... and one that holds a GruNonlinearityComponent has to be a fast-pgru / fast-norm-pgru / fast-gru block)
+    bool pgru_cycle = false;
+    for (int n : scc) pgru_cycle = pgru_cycle || comp_type(n) == "GruNonlinearityComponent";
     auto refuse = [&](int n, const std::string &why) {
+      if (pgru_cycle)
+        Fail("nnet3: recurrent GRU networks are supported only as fast-opgru-layer / fast-norm-opgru-layer blocks and, around a GruNonlinearityComponent, as "
+             "fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer blocks (cycle at node " + nodes[n].name + ": " + why + ")");
       if (gru_cycle)
         Fail("nnet3: recurrent GRU networks are supported only as fast-opgru-layer / fast-norm-opgru-layer blocks (cycle at node " + nodes[n].name + ": " + why + ")");
       Fail("nnet3: recurrent networks are supported only as fast-lstmp-layer / fast-lstm-layer blocks (cycle at node " + nodes[n].name + ": " + why + ")");
@@ -1245,20 +1255,164 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
     };
     auto plain_part = [&](const DescPart &p) { return p.terms.size() == 1 && !p.terms[0].const_t && !p.terms[0].optional && p.terms[0].offset == 0 && p.terms[0].scale == 1.0f; };
     auto range_of = [&](int n, int src, int off, int dim) { return nodes[n].kind == NnetNode::kDimRange && nodes[n].range_node == src && nodes[n].range_offset == off && nodes[n].dim == dim; };
+    auto only_input = [&](int n) { const NnetNode &nd = nodes[n]; return nd.input.parts.size() == 1 && plain_part(nd.input.parts[0]) ? nd.input.parts[0].terms[0].node : -1; };
+    auto is_affine = [&](int n) { const std::string t = comp_type(n); return t == "AffineComponent" || t == "NaturalGradientAffineComponent"; };
+    auto same_parts = [&](const std::vector<DescPart> &a, size_t na, const std::vector<DescPart> &c) {
+      if (na != c.size()) return false;
+      for (size_t i = 0; i < na; i++) {
+        if (a[i].dim != c[i].dim || a[i].terms.size() != c[i].terms.size()) return false;
+        for (size_t j = 0; j < a[i].terms.size(); j++) {
+          const DescTerm &s = a[i].terms[j], &t = c[i].terms[j];
+          if (s.node != t.node || s.offset != t.offset || s.scale != t.scale || s.const_t != t.const_t || s.optional != t.optional) return false;
+        }
+      }
+      return true;
+    };
+    if (pgru_cycle) {
+      // ---- a block around a GruNonlinearityComponent (xconfig/gru.py: XconfigFastGruLayer, XconfigFastPgruLayer, XconfigFastNormPgruLayer)
+      const std::string kWhat = "a GruNonlinearityComponent (fast-gru-layer, fast-pgru-layer, fast-norm-pgru-layer) ";
+      b.pgru = true;
+      b.nl = -1;
+      for (int n : scc)
+        if (comp_type(n) == "GruNonlinearityComponent") {
+          if (b.nl >= 0) refuse(n, "a second GruNonlinearityComponent in one cycle");
+          b.nl = n;
+        }
+      // the nonlinearity: Append(z_t, r_t, hpart_t, IfDefined(Offset(c_t, -d)), IfDefined(Offset(s_t, -d))); without a projection
+      // Append(z_t, r_t, hpart_t, IfDefined(Offset(s_t, -d)))
+      const NnetNode &nl = nodes[b.nl];
+      const Component &nc = net.components[nl.component];
+      const int C = b.cell = nl.dim / 2;
+      const size_t n_parts = nl.input.parts.size();
+      if (!nc.i.count("<RecurrentDim>") || nc.Int("<RecurrentDim>") <= 0)
+        refuse(b.nl, kWhat + "without a <RecurrentDim>, over an input of " + std::to_string(n_parts) + " parts");
+      const int R = b.rec_dim = nc.Int("<RecurrentDim>");
+      const bool proj = n_parts == 5;
+      if (n_parts != 4 && n_parts != 5)
+        refuse(b.nl, kWhat + "whose input has " + std::to_string(n_parts) + " parts, not Append(z_t, r_t, hpart_t, [IfDefined(Offset(c_t, -delay)),] IfDefined(Offset(s_t, -delay)))");
+      if (!proj && R != C)
+        refuse(b.nl, kWhat + "with <RecurrentDim> " + std::to_string(R) + " and <CellDim> " + std::to_string(C) + " over a four-part input: without a projection the two are equal");
+      {
+        // <w_h>: cell x R (a one-row text matrix lands in the vector map)
+        auto mit = nc.m.find("<w_h>");
+        auto vit = nc.v.find("<w_h>");
+        const int rows = mit != nc.m.end() ? mit->second.rows : vit != nc.v.end() && !vit->second.empty() ? 1 : 0;
+        const int cols = mit != nc.m.end() ? mit->second.cols : vit != nc.v.end() ? (int)vit->second.size() : 0;
+        if (rows != C || cols != R)
+          refuse(b.nl, kWhat + "whose <w_h> is " + std::to_string(rows) + " x " + std::to_string(cols) + ", not cell-dim " + std::to_string(C) + " x recurrent-dim " + std::to_string(R));
+      }
+      const int part_dims[5] = {C, R, C, C, R};      // (without a projection R = C: the fourth part is s_t)
+      for (size_t i = 0; i < n_parts; i++)
+        if (nl.input.parts[i].dim != part_dims[i]) refuse(b.nl, kWhat + "whose input parts are not of the dims cell, recurrent, cell, [cell,] recurrent");
+      for (int i = 0; i < 3; i++)
+        if (!plain_part(nl.input.parts[i])) refuse(b.nl, "its first three inputs are not the nodes z_t, r_t and hpart_t");
+      const int z_t = nl.input.parts[0].terms[0].node, r_t = nl.input.parts[1].terms[0].node;
+      b.hp = nl.input.parts[2].terms[0].node;
+      b.delay = recurrent_part(b.nl, nl.input.parts[3], &b.sc);
+      int s_nl = b.sc;
+      if (proj) {
+        const int d2 = recurrent_part(b.nl, nl.input.parts[4], &s_nl);
+        if (d2 != b.delay) refuse(b.nl, "two different delays in one block, " + std::to_string(d2) + " and " + std::to_string(b.delay));
+        if (!range_of(b.sc, b.nl, C, C)) refuse(b.sc, "the cell state is not the second cell-dim columns of the nonlinearity");
+      }
+      b.tr = b.sr = s_nl;
+      if (comp_type(b.tr) != "BackpropTruncationComponent") refuse(b.tr, "the recurrent state does not come through a BackpropTruncationComponent");
+      // a gate: [DropoutComponent over] a SigmoidComponent over an affine over Append(x, IfDefined(Offset(s_t, -d)))
+      auto gate = [&](int g, int rows, const char *rows_name, int *drop, int *sig, int *aff) {
+        *drop = -1;
+        if (comp_type(g) == "DropoutComponent") {
+          *drop = g;
+          g = only_input(g);
+          if (g < 0) refuse(*drop, "the dropout's input is not one node");
+        }
+        if (comp_type(g) != "SigmoidComponent") refuse(g, "the gate is not a SigmoidComponent node [behind a DropoutComponent]");
+        *sig = g;
+        const int a = only_input(g);
+        if (a < 0 || !is_affine(a)) refuse(g, "the sigmoid's input is not an affine component node");
+        *aff = a;
+        const NnetNode &an = nodes[a];
+        if (an.input.parts.size() < 2) refuse(a, "its input is not Append(x, IfDefined(Offset(s_t, -delay)))");
+        int state = -1;
+        const int d2 = recurrent_part(a, an.input.parts.back(), &state);
+        if (d2 != b.delay) refuse(a, "two different delays in one block, " + std::to_string(d2) + " and " + std::to_string(b.delay));
+        if (state != b.tr) refuse(a, "the gate and the nonlinearity read different recurrent states, " + nodes[state].name + " and " + nodes[b.tr].name);
+        if (an.dim != rows) refuse(a, "the gate's affine has " + std::to_string(an.dim) + " rows, not the " + rows_name + " " + std::to_string(rows));
+      };
+      gate(z_t, C, "cell's dim", &b.zd, &b.zs, &b.wa);
+      gate(r_t, R, "recurrent dim", &b.od, &b.os, &b.wo);
+      if ((b.zd >= 0) != (b.od >= 0)) refuse(b.zd >= 0 ? b.zd : b.od, "only one of the two gates has a DropoutComponent");
+      // the state: s_t from W_y's first columns [through a NormalizeComponent]; without a projection from the nonlinearity's c columns
+      int src = only_input(b.tr);
+      if (proj) {
+        if (src >= 0 && comp_type(src) == "NormalizeComponent") {
+          b.nm = src;
+          const Component &nmc = net.components[nodes[b.nm].component];
+          if (nmc.f.count("<AddLogStddev>") && nmc.f.at("<AddLogStddev>")[0] != 0.0) refuse(b.nm, "a NormalizeComponent with add-log-stddev=true is not supported");
+          if (nmc.f.count("<BlockDim>") && nmc.Int("<BlockDim>") != (nmc.i.count("<InputDim>") ? nmc.Int("<InputDim>") : nmc.Int("<Dim>")))
+            refuse(b.nm, "a NormalizeComponent with block-dim is not supported");
+          src = only_input(b.nm);
+        }
+        if (src < 0 || nodes[src].kind != NnetNode::kDimRange) refuse(b.tr, "the recurrent state is not a dim-range of W_y's node [through a NormalizeComponent]");
+        b.sp = src;
+        b.wy = nodes[b.sp].range_node;
+        if (!is_affine(b.wy) || !range_of(b.sp, b.wy, 0, R) || nodes[b.tr].dim != R) refuse(b.sp, "the recurrent state is not the first recurrent-dim columns of an affine component node");
+        if (only_input(b.wy) != b.sc) refuse(b.wy, "W_y's input is not the cell state " + nodes[b.sc].name);
+      } else {
+        if (src < 0 || !range_of(src, b.nl, C, C) || nodes[b.tr].dim != C) refuse(b.tr, "without a projection the recurrent state is not the second cell-dim columns of the nonlinearity");
+        b.sc = src;      // (y_t: the layer's output)
+      }
+      // the feed-forward input: the same descriptor in front of both gates and under hpart_t
+      const NnetNode &wz = nodes[b.wa], &wr = nodes[b.wo], &hp = nodes[b.hp];
+      b.x_parts.assign(wz.input.parts.begin(), wz.input.parts.end() - 1);
+      if (!same_parts(wr.input.parts, wr.input.parts.size() - 1, b.x_parts)) refuse(b.wo, "the two gates do not read the same feed-forward input");
+      if (!is_affine(b.hp) || !same_parts(hp.input.parts, hp.input.parts.size(), b.x_parts))
+        refuse(b.hp, "hpart_t is not an affine component node over the gates' feed-forward input");
+      for (auto &p : b.x_parts) for (auto &t : p.terms) if (in_scc(t.node)) refuse(b.wa, "its feed-forward input reads " + nodes[t.node].name + ", a node of the cycle");
+      b.members = {b.wa, b.wo, b.zs, b.os, b.nl, b.sc, b.tr};
+      for (int n : {b.zd, b.od, b.nm, b.wy, b.sp}) if (n >= 0) b.members.push_back(n);
+      std::sort(b.members.begin(), b.members.end());
+      if (std::adjacent_find(b.members.begin(), b.members.end()) != b.members.end()) refuse(b.nl, "a node has two roles in the block");
+      for (int n : scc) if (!std::binary_search(b.members.begin(), b.members.end(), n)) refuse(n, "the node is part of the cycle but not of such a block");
+      for (int n : b.members) if (!in_scc(n)) refuse(n, "the node is not part of the cycle");
+      if (in_scc(b.hp) || (*block_of)[b.hp] >= 0) refuse(b.hp, "hpart_t is part of a cycle");
+      // dims against the weights
+      int x_dim = 0;
+      for (auto &p : b.x_parts) x_dim += p.dim;
+      for (int a : {b.wa, b.wo}) {
+        const MatF &W = net.components[nodes[a].component].m.at("<LinearParams>");
+        if (W.cols != x_dim + R)
+          refuse(a, "its weights are " + std::to_string(W.rows) + " x " + std::to_string(W.cols) + ", the block needs the feed-forward input's " +
+                        std::to_string(x_dim) + " + the recurrent input's " + std::to_string(R) + " columns");
+      }
+      const MatF &Wh = net.components[hp.component].m.at("<LinearParams>");
+      if (Wh.rows != C || Wh.cols != x_dim) refuse(b.hp, "its weights are " + std::to_string(Wh.rows) + " x " + std::to_string(Wh.cols) + ", not cell-dim x the feed-forward input's dim");
+      if (proj) {
+        const MatF &Wy = net.components[nodes[b.wy].component].m.at("<LinearParams>");
+        if (Wy.cols != C || Wy.rows < R) refuse(b.wy, "W_y is " + std::to_string(Wy.rows) + " x " + std::to_string(Wy.cols) + ", the block needs cell-dim columns and at least the recurrent dim's rows");
+      }
+      // only what has a buffer may be read from outside the block: the nonlinearity, c_t, W_y's node, its dim-range and the state
+      for (int n = 0; n < N; n++) {
+        if (std::binary_search(b.members.begin(), b.members.end(), n) || index[n] < 0) continue;
+        std::vector<int> d;
+        deps(n, &d);
+        for (int m : d)
+          if (m == b.wa || m == b.wo || m == b.zs || m == b.os || m == b.zd || m == b.od || m == b.nm || (m == b.hp && n != b.nl))
+            refuse(m, "the node is read from outside the block, by " + nodes[n].name);
+      }
+      b.members.push_back(b.hp);
+      std::sort(b.members.begin(), b.members.end());
+      for (int n : b.members) (*block_of)[n] = (int)blocks->size();
+      blocks->push_back(std::move(b));
+      continue;
+    }
     if (gru_cycle) {
       b.gru = true;
       b.nl = -1;
-      for (int n : scc) {
-        if (comp_type(n) == "GruNonlinearityComponent")
-          refuse(n, "a GruNonlinearityComponent (fast-gru-layer, fast-pgru-layer, fast-norm-pgru-layer): its h needs a third serial matrix product, which "
-                    "the HIP kernel does not have");
+      for (int n : scc)
         if (comp_type(n) == "OutputGruNonlinearityComponent") {
           if (b.nl >= 0) refuse(n, "a second OutputGruNonlinearityComponent in one cycle");
           b.nl = n;
         }
-      }
-      auto only_input = [&](int n) { const NnetNode &nd = nodes[n]; return nd.input.parts.size() == 1 && plain_part(nd.input.parts[0]) ? nd.input.parts[0].terms[0].node : -1; };
-      auto is_affine = [&](int n) { const std::string t = comp_type(n); return t == "AffineComponent" || t == "NaturalGradientAffineComponent"; };
       // the nonlinearity: Append(z_t, hpart_t, IfDefined(Offset(c_t, -d)))
       const NnetNode &nl = nodes[b.nl];
       const int C = b.cell = nl.dim / 2;
@@ -1321,17 +1475,6 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
       // the feed-forward input: the same descriptor in front of both gates and under hpart_t
       const NnetNode &wz = nodes[b.wa], &wo = nodes[b.wo], &hp = nodes[b.hp];
       b.x_parts.assign(wz.input.parts.begin(), wz.input.parts.end() - 1);
-      auto same_parts = [&](const std::vector<DescPart> &a, size_t na, const std::vector<DescPart> &c) {
-        if (na != c.size()) return false;
-        for (size_t i = 0; i < na; i++) {
-          if (a[i].dim != c[i].dim || a[i].terms.size() != c[i].terms.size()) return false;
-          for (size_t j = 0; j < a[i].terms.size(); j++) {
-            const DescTerm &s = a[i].terms[j], &t = c[i].terms[j];
-            if (s.node != t.node || s.offset != t.offset || s.scale != t.scale || s.const_t != t.const_t || s.optional != t.optional) return false;
-          }
-        }
-        return true;
-      };
       if (!same_parts(wo.input.parts, wo.input.parts.size() - 1, b.x_parts)) refuse(b.wo, "the two gates do not read the same feed-forward input");
       if (!is_affine(b.hp) || !same_parts(hp.input.parts, hp.input.parts.size(), b.x_parts))
         refuse(b.hp, "hpart_t is not an affine component node over the gates' feed-forward input");
@@ -1459,8 +1602,8 @@ void Nnet::Compile() {
   int out_node = FindNode("output");
   int in_node = FindNode("input"), iv_node = FindNode("ivector");
   const int N = (int)nodes.size();
-  // recurrent blocks: the cycles of the node graph, each of which has to be what fast-lstmp-layer / fast-lstm-layer or
-  // fast-opgru-layer / fast-norm-opgru-layer emit
+  // recurrent blocks: the cycles of the node graph, each of which has to be what fast-lstmp-layer / fast-lstm-layer,
+  // fast-opgru-layer / fast-norm-opgru-layer or fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer emit
   std::vector<BlockNodes> blocks;
   std::vector<int> block_of(N, -1);
   FindBlocks(*this, out_node, &blocks, &block_of);
@@ -1653,6 +1796,82 @@ void Nnet::Compile() {
     if (block_of[n] >= 0) {
       // ---- a recurrent block: the feed-forward columns of W_all as a layer GEMM over all rows (bias included), then the walk
       const BlockNodes &b = blocks[block_of[n]];
+      if (b.pgru) {
+        // ---- a block around a GruNonlinearityComponent: the x-columns of W_z, W_r and W_hpart stacked to one layer GEMM of
+        // cell + R + cell rows with their three biases (each element's sum over k is what its own affine would compute), then the walk
+        const bool proj = b.wy >= 0;
+        const int C = b.cell, R = b.rec_dim, l = lext[b.wa], r = rext[b.wa];
+        const Component *aff[3] = {&components[nodes[b.wa].component], &components[nodes[b.wo].component], &components[nodes[b.hp].component]};
+        const int aff_node[3] = {b.wa, b.wo, b.hp}, aff_rows[3] = {C, R, C}, aff_row0[3] = {0, C, C + R};
+        const int in_dim = aff[2]->m.at("<LinearParams>").cols, pre_dim = 2 * C + R;
+        LayerOp g;
+        g.kind = LayerOp::kGemm;
+        g.name = nodes[b.nl].name + ".x";
+        g.out_dim = pre_dim;
+        g.W.Resize(pre_dim, in_dim);
+        g.bias.assign(pre_dim, 0.0f);
+        LayerOp w;
+        w.kind = LayerOp::kPgru;
+        w.name = nodes[b.nl].name;
+        w.out_dim = 2 * C;
+        PgruBlock &k = w.pgru;
+        k.W_zs.Resize(C, R);
+        k.W_rs.Resize(R, R);
+        for (int a = 0; a < 3; a++) {
+          const MatF &W = aff[a]->m.at("<LinearParams>");
+          for (int row = 0; row < aff_rows[a]; row++) {
+            for (int c = 0; c < in_dim; c++) g.W(aff_row0[a] + row, c) = W(row, c);
+            if (a == 0) for (int c = 0; c < R; c++) k.W_zs(row, c) = W(row, in_dim + c);
+            if (a == 1) for (int c = 0; c < R; c++) k.W_rs(row, c) = W(row, in_dim + c);
+          }
+          auto bit = aff[a]->v.find("<BiasParams>");
+          if (bit != aff[a]->v.end() && !bit->second.empty()) {
+            if ((int)bit->second.size() != aff_rows[a]) Fail("nnet3: bias dim mismatch in node " + nodes[aff_node[a]].name);
+            std::copy(bit->second.begin(), bit->second.end(), g.bias.begin() + aff_row0[a]);
+          }
+        }
+        const int wcol = add_gemm_segs(&g, b.x_parts, b.wa, {0});
+        if (wcol != in_dim) Fail("nnet3: internal error, the feed-forward input of recurrent block " + w.name + " does not cover its weights' columns");
+        g.out_buf = new_buf(pre_dim, l, r);
+        ops.push_back(g);
+        k.in_dim = in_dim; k.cell = C;
+        k.rec = proj ? R : 0;
+        k.nonrec = proj ? nodes[b.wy].dim - R : 0;
+        k.delay = b.delay;
+        k.scale = TruncationScale(components[nodes[b.tr].component]);
+        k.norm = b.nm >= 0;
+        if (k.norm) { const Component &nc = components[nodes[b.nm].component]; k.target_rms = nc.f.count("<TargetRms>") ? (float)nc.f.at("<TargetRms>")[0] : 1.0f; }
+        k.dropout = b.zd >= 0;
+        {
+          // <w_h>: cell x R (the recogniser checked the shape; a one-row text matrix is in the vector map)
+          const Component &nc = components[nodes[b.nl].component];
+          auto mit = nc.m.find("<w_h>");
+          if (mit != nc.m.end()) k.W_h = mit->second;
+          else { k.W_h.Resize(1, R); const std::vector<float> &v = nc.v.at("<w_h>"); for (int c = 0; c < R; c++) k.W_h(0, c) = v[c]; }
+        }
+        if (proj) {
+          const Component &wy = components[nodes[b.wy].component];
+          k.W_y = wy.m.at("<LinearParams>");
+          auto yb = wy.v.find("<BiasParams>");
+          k.b_y = yb != wy.v.end() && !yb->second.empty() ? yb->second : std::vector<float>(k.W_y.rows, 0.0f);
+          if ((int)k.b_y.size() != k.W_y.rows) Fail("nnet3: bias dim mismatch in node " + nodes[b.wy].name);
+        }
+        k.need_lext = b.need_lext;
+        k.pre_buf = g.out_buf;
+        k.hc_buf = new_buf(2 * C, l, r);
+        if (proj) k.y_buf = new_buf(R + k.nonrec, l, r);
+        k.s_buf = new_buf(R, l, r);
+        node_buf[b.hp] = k.pre_buf;
+        node_col[b.hp] = C + R;
+        node_buf[b.nl] = node_buf[b.sc] = k.hc_buf;
+        node_col[b.sc] = C;
+        if (proj) node_buf[b.wy] = node_buf[b.sp] = k.y_buf;
+        node_buf[b.tr] = k.s_buf;
+        w.out_buf = k.hc_buf;
+        w.terms.push_back({k.pre_buf, 0, 0, 1.0f});
+        ops.push_back(w);
+        continue;
+      }
       if (b.gru) {
         // ---- a GRU block: the x-columns of W_z, W_o and W_hpart stacked to one layer GEMM of 3 cell rows with their biases (each
         // element's sum over k is what its own affine would compute), then the walk
@@ -2003,6 +2222,14 @@ void Nnet::SetSubsampling(int factor) {
       for (int round = 0; round < factor; round++)
         for (int r = 0; r < factor; r++) if (all >> r & 1u) all |= 1u << mod(r - k.delay);
       need[k.hc_buf] = need[k.y_buf] = need[k.s_buf] = all;
+    }
+    if (it->kind == LayerOp::kPgru) {      // (... and for a block around a GruNonlinearityComponent; no y buffer without a projection)
+      const PgruBlock &k = it->pgru;
+      unsigned all = need[k.hc_buf] | need[k.s_buf] | (k.y_buf >= 0 ? need[k.y_buf] : 0u);
+      for (int round = 0; round < factor; round++)
+        for (int r = 0; r < factor; r++) if (all >> r & 1u) all |= 1u << mod(r - k.delay);
+      need[k.hc_buf] = need[k.s_buf] = all;
+      if (k.y_buf >= 0) need[k.y_buf] = all;
     }
     const unsigned out = need[it->out_buf];
     auto reads = [&](int src, int off) {

@@ -249,6 +249,35 @@ struct GruBlock {
   int StateDim() const { return cell + rec; }      // a parked state row: [c | s]
 };
 
+// A recurrent block of the (projected) GRU with a reset gate: what nnet3's fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer
+// emit (xconfig/gru.py) around a GruNonlinearityComponent, recognised as a unit (Nnet::Compile).  With s the recurrent state
+// (scaled), c the cell state (read back unscaled), zero where the chain has not started, d the delay, R = RecDim(), per row t:
+//   z = Sigmoid(pre_z[t] + W_z,s s[t - d])  (cell),  r = Sigmoid(pre_r[t] + W_r,s s[t - d])  (R)     pre = [W_z,x; W_r,x; W_hpart] x + b, a kGemm op
+//   sdotr = r . s[t - d];  h = Tanh(pre_h[t] + W_h sdotr);  c = h - z . h + z . c[t - d]             GruNonlinearityComponent::Propagate
+//   y = W_y c + b_y;  s[t] = scale y[0:rec]   or, norm,   scale Normalize(y[0:rec])                  affine, BackpropTruncationComponent
+// Without a projection (fast-gru-layer: rec = nonrec = 0) R = cell, there is no W_y, s[t] = scale c, and c[t - d] IS s[t - d].
+struct PgruBlock {
+  int in_dim = 0, cell = 0, rec = 0, nonrec = 0;   // rec / nonrec: W_y's dims, 0 / 0 without a projection
+  int delay = 0;                  // frames towards the past, 1 .. kLstmMaxDelay
+  float scale = 1.0f;
+  bool norm = false;              // fast-norm-pgru-layer: a NormalizeComponent between y[0:rec] and the truncation component
+  float target_rms = 1.0f;        // its <TargetRms>
+  bool dropout = false;           // the norm variant's two DropoutComponents behind the sigmoids: copies in test mode
+  MatF W_zs;                      // cell x RecDim(): the recurrent columns of W_z
+  MatF W_rs;                      // RecDim() x RecDim(): those of W_r
+  MatF W_h;                       // cell x RecDim(): the nonlinearity's <w_h>
+  MatF W_y;                       // (rec + nonrec) x cell; empty without a projection
+  std::vector<float> b_y;
+  // buffers: pre-activations [z | r | hpart] (2 cell + RecDim()), the nonlinearity's output [h | c], y (rec + nonrec; -1 without a
+  // projection), the state s (RecDim())
+  int pre_buf = -1, hc_buf = -1, y_buf = -1, s_buf = -1;
+  int need_lext = 0;              // as LstmBlock::need_lext
+  bool proj() const { return rec > 0; }
+  int RecDim() const { return rec > 0 ? rec : cell; }
+  int OutDim() const { return rec > 0 ? rec + nonrec : cell; }
+  int StateDim() const { return rec > 0 ? cell + rec : cell; }      // a parked state row: [c | s], without a projection [s]
+};
+
 // RestrictedAttentionComponent (nnet3/nnet-attention-component.h, attention.h): an input row is `heads` blocks of
 // [key(K) | value(V) | query(K + C)], C = left + 1 + right; an output row is `heads` blocks of [value(V) | c(C) if output_context].
 // Per frame t and head, o = 0 .. C-1:  b[o] = key_scale <query_key(t), key(t + (o - left) stride)> + query_context(t)[o],
@@ -268,8 +297,9 @@ struct AttentionGeom {
 struct LayerOp {
   // kConv: out = stages(bias + conv(terms)); kGather: out[:, i] = part(gather_part[i])[:, gather_col[i]] (PermuteComponent over an Append)
   // kLstm: the serial part of a recurrent block (lstm); out_buf = lstm.cm_buf.  kGru: the same of a GRU block (gru); out_buf = gru.hc_buf
+  // kPgru: the same of a block around a GruNonlinearityComponent (pgru); out_buf = pgru.hc_buf
   // kAttention: out = attention(terms[0]), no fused stage (the result matrix of the op is the component's output): one term, the source; the rows it reads are terms[0].offset + attention.TimeOffset(o)
-  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm, kGru, kAttention } kind = kGemm;
+  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm, kGru, kAttention, kPgru } kind = kGemm;
   std::string name;
   int out_buf = -1, out_dim = 0;
   // kGemm
@@ -290,6 +320,7 @@ struct LayerOp {
   LstmBlock lstm;                             // kLstm
   GruBlock gru;                               // kGru
   AttentionGeom attention;                    // kAttention
+  PgruBlock pgru;                             // kPgru
 };
 struct BufferInfo {
   int dim = 0, lext = 0, rext = 0;   // rows cover t in [-lext, T + rext)
@@ -308,7 +339,7 @@ struct Nnet {
   std::vector<BufferInfo> bufs;
   int input_buf = -1, output_buf = -1;
   int left_context = 0, right_context = 0;
-  bool recurrent = false;      // has at least one recurrent block (kLstm or kGru op)
+  bool recurrent = false;      // has at least one recurrent block (kLstm, kGru or kPgru op)
   // What the reference's binaries do to the network before the first frame (nnet3_setup.h): the network is the one
   // CollapseModel leaves behind, and rand() has been called `setup_rand_calls` times (the dither seeds follow from that).
   long setup_rand_calls = 0;

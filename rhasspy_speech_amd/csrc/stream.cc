@@ -292,6 +292,9 @@ StreamPool *Model::Pool() {
     } else if (nn.ops[i].kind == LayerOp::kGru) {      // (a GRU block's rows are [c | s]: gru_plan.h)
       const GruBlock &k = nn.ops[i].gru;
       p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * k.StateDim() * 4));
+    } else if (nn.ops[i].kind == LayerOp::kPgru) {     // ([c | s], without a projection [s]: pgru_plan.h)
+      const PgruBlock &k = nn.ops[i].pgru;
+      p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * k.StateDim() * 4));
     }
   if (fc_.ie.present) {
     const int Di = fc_.ie.ivector_dim(), usz = Di * (Di + 1) / 2;

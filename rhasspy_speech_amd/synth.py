@@ -226,6 +226,13 @@ class ModelSpec:
     # in the recurrence and a BatchNorm on the output, default False), dropout (norm variant only: the shared DropoutComponent
     # behind the two sigmoids, default False).
     gru_layers: Tuple[Dict[str, object], ...] = ()
+    # Recurrent blocks around a GruNonlinearityComponent (nnet3's fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer,
+    # xconfig/gru.py), placed like lstm_layers (behind the OPGRU blocks of the same `after`).  One dict per block: after, cell, rec,
+    # nonrec (rec = 0 with nonrec = 0: the plain fast-gru-layer, whose state and output are the cell), delay (default 3), scale
+    # (the BackpropTruncationComponent's <Scale>, default 1), norm (fast-norm-pgru-layer: a NormalizeComponent in the recurrence and a
+    # BatchNorm on the output, default False), dropout (norm variant only: the two DropoutComponents behind the sigmoids, default
+    # False).
+    pgru_layers: Tuple[Dict[str, object], ...] = ()
     # Time-restricted self-attention layers between the TDNN layers (xconfig/attention.py), placed like lstm_layers (behind the
     # recurrent blocks of the same `after`).  One dict per layer: after, heads, key_dim, value_dim, left, right (num-left-inputs,
     # num-right-inputs), stride (time-stride); optional left_required, right_required (default -1: all of them), key_scale (default
@@ -800,6 +807,101 @@ def _attention_layer(cfg: List[str], comps: List[Tuple[str, object]], rng: np.ra
     return cur, dim
 
 
+def _w_gru_nonlinearity(w: KaldiWriter, w_h: np.ndarray) -> None:
+    # nnet-combined-component.cc:1726-1767 (GruNonlinearityComponent::Write), behind WriteUpdatableCommon; w_h is cell x recurrent
+    cell, rec = w_h.shape
+    _updatable_open(w, "GruNonlinearityComponent")
+    w.token("<CellDim>").i32(cell).token("<RecurrentDim>").i32(rec).token("<w_h>").matrix(w_h)
+    w.token("<ValueAvg>").vector(np.zeros(cell, np.float32)).token("<DerivAvg>").vector(np.zeros(cell, np.float32))
+    w.token("<SelfRepairTotal>").f64(0.0).token("<Count>").f64(0.0)
+    w.token("<SelfRepairThreshold>").f32(0.2).token("<SelfRepairScale>").f32(1e-5)
+    w.token("<Alpha>").f32(4.0).token("<RankInOut>").i32(8).i32(8).token("<UpdatePeriod>").i32(10)
+    w.token("</GruNonlinearityComponent>")
+
+
+def pgru_layer_dims(layer: Dict[str, object]) -> Tuple[int, int, int, int]:
+    """(cell, recurrent, non-recurrent, output) dims of a ModelSpec.pgru_layers entry; without a projection (rec = nonrec = 0) the
+    recurrent and the output dim are the cell dim."""
+    C, R, P = int(layer["cell"]), int(layer.get("rec", 0)), int(layer.get("nonrec", 0))
+    if C <= 0 or R < 0 or P < 0 or (R == 0) != (P == 0):
+        raise ValueError("pgru layer: cell is positive; rec and nonrec are both positive or both 0 (fast-gru-layer)")
+    if layer.get("norm", False) and R == 0:
+        raise ValueError("pgru layer: there is no norm variant of fast-gru-layer")
+    if layer.get("dropout", False) and not layer.get("norm", False):
+        raise ValueError("pgru layer: only the norm variant has the dropout components")
+    return (C, R, P, R + P) if R > 0 else (C, C, 0, C)
+
+
+def _pgru_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.Generator, name: str, layer: Dict[str, object],
+                prev: str, prev_dim: int) -> Tuple[str, int]:
+    """The components and nodes XconfigFastGruLayer / XconfigFastPgruLayer / XconfigFastNormPgruLayer emit (xconfig/gru.py:1160-1197,
+    1367-1407, 1587-1653), in their order.  Returns the node the next layer reads and its dim."""
+    C, R, P, out_dim = pgru_layer_dims(layer)
+    proj = int(layer.get("rec", 0)) > 0
+    d, scale = int(layer.get("delay", 3)), float(layer.get("scale", 1.0))
+    norm, dropout = bool(layer.get("norm", False)), bool(layer.get("dropout", False))
+    xs = "xs" if proj else "xh"
+
+    def randn(o, i):
+        return (rng.standard_normal((o, i)) / math.sqrt(i)).astype(np.float32)
+
+    def randb(n):
+        return (rng.standard_normal(n) * 0.1).astype(np.float32)
+
+    def affine(W, b):
+        return lambda w, W=W, b=b: _w_affine(w, "NaturalGradientAffineComponent", W, b)
+
+    W_z, b_z = np.concatenate([randn(C, prev_dim), randn(C, R)], axis=1), randb(C)
+    W_r, b_r = np.concatenate([randn(R, prev_dim), randn(R, R)], axis=1), randb(R)
+    W_hp, b_hp = randn(C, prev_dim), randb(C)
+    w_h = randn(C, R)
+    comps.append((f"{name}.W_z.{xs}", affine(W_z, b_z)))
+    comps.append((f"{name}.W_r.{xs}", affine(W_r, b_r)))
+    comps.append((f"{name}.W_hpart.x", affine(W_hp, b_hp)))
+    comps.append((f"{name}.z", lambda w: _w_nonlinear(w, "SigmoidComponent", C)))
+    comps.append((f"{name}.r", lambda w: _w_nonlinear(w, "SigmoidComponent", R)))
+    if dropout:
+        comps.append((f"{name}.dropout_z", lambda w: _w_dropout(w, C)))
+        comps.append((f"{name}.dropout_r", lambda w: _w_dropout(w, R)))
+    rec = f"IfDefined(Offset({name}.s_t, {-d}))"
+    for g in ("z", "r"):
+        cfg.append(f"component-node name={name}.{g}_t_pre component={name}.W_{g}.{xs} input=Append({prev}, {rec})")
+        if dropout:
+            cfg.append(f"component-node name={name}.{g}_t_predrop component={name}.{g} input={name}.{g}_t_pre")
+            cfg.append(f"component-node name={name}.{g}_t component={name}.dropout_{g} input={name}.{g}_t_predrop")
+        else:
+            cfg.append(f"component-node name={name}.{g}_t component={name}.{g} input={name}.{g}_t_pre")
+    cfg.append(f"component-node name={name}.hpart_t component={name}.W_hpart.x input={prev}")
+    comps.append((f"{name}.gru_nonlin", lambda w: _w_gru_nonlinearity(w, w_h)))
+    if not proj:
+        cfg.append(f"component-node name={name}.gru_nonlin_t component={name}.gru_nonlin "
+                   f"input=Append({name}.z_t, {name}.r_t, {name}.hpart_t, {rec})")
+        cfg.append(f"dim-range-node name={name}.y_t input-node={name}.gru_nonlin_t dim-offset={C} dim={C}")
+        comps.append((f"{name}.s_r", lambda w: _w_backprop_truncation(w, C, scale, d)))
+        cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.y_t")
+        return f"{name}.y_t", out_dim
+    cfg.append(f"component-node name={name}.gru_nonlin_t component={name}.gru_nonlin "
+               f"input=Append({name}.z_t, {name}.r_t, {name}.hpart_t, IfDefined(Offset({name}.c_t, {-d})), {rec})")
+    cfg.append(f"dim-range-node name={name}.c_t input-node={name}.gru_nonlin_t dim-offset={C} dim={C}")
+    W_y, b_y = randn(R + P, C), randb(R + P)
+    comps.append((f"{name}.W_y.c", affine(W_y, b_y)))
+    y = f"{name}.y_t_tmp" if norm else f"{name}.y_t"
+    cfg.append(f"component-node name={y} component={name}.W_y.c input={name}.c_t")
+    if norm:
+        comps.append((f"{name}.renorm", lambda w: _w_normalize(w, R)))
+    comps.append((f"{name}.s_r", lambda w: _w_backprop_truncation(w, R, scale, d)))
+    cfg.append(f"dim-range-node name={name}.s_t_pre input-node={y} dim-offset=0 dim={R}")
+    if norm:
+        cfg.append(f"component-node name={name}.s_t_renorm component={name}.renorm input={name}.s_t_pre")
+        cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.s_t_renorm")
+        mean, var = (0.1 * rng.standard_normal(out_dim)).astype(np.float32), rng.uniform(0.05, 0.2, out_dim).astype(np.float32)
+        comps.append((f"{name}.batchnorm", lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+        cfg.append(f"component-node name={name}.y_t component={name}.batchnorm input={y}")
+    else:
+        cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.s_t_pre")
+    return f"{name}.y_t", out_dim
+
+
 def _append_desc(src: str, offsets: Sequence[int]) -> str:
     parts = [src if o == 0 else f"Offset({src}, {o})" for o in offsets]
     return parts[0] if len(parts) == 1 else "Append(" + ", ".join(parts) + ")"
@@ -886,6 +988,9 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
         for k, layer in enumerate(spec.gru_layers, start=1):
             if int(layer["after"]) == n_layers:
                 prev, prev_dim = _gru_block(cfg, comps, rng, f"gru{k}", layer, prev, prev_dim)
+        for k, layer in enumerate(spec.pgru_layers, start=1):
+            if int(layer["after"]) == n_layers:
+                prev, prev_dim = _pgru_block(cfg, comps, rng, f"pgru{k}", layer, prev, prev_dim)
         for k, layer in enumerate(spec.attention_layers, start=1):
             if int(layer["after"]) == n_layers:
                 prev, prev_dim = _attention_layer(cfg, comps, rng, f"attention{k}", layer, prev, prev_dim)
@@ -897,6 +1002,9 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
     for layer in spec.gru_layers:
         if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
             raise ValueError("gru layer: 'after' counts the TDNN layers in front of the block, 1 .. len(layer_offsets)")
+    for layer in spec.pgru_layers:
+        if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
+            raise ValueError("pgru layer: 'after' counts the TDNN layers in front of the block, 1 .. len(layer_offsets)")
     for layer in spec.attention_layers:
         if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
             raise ValueError("attention layer: 'after' counts the TDNN layers in front of the layer, 1 .. len(layer_offsets)")
