@@ -109,8 +109,16 @@ const char *rs_last_error(void);
  * optionally the projection W_rp over m, and one BackpropTruncationComponent (its <Scale> is honoured, here and anywhere else) whose
  * dim-ranges are the state; one delay d for both connections, 1 <= d <= 8, towards the past.  Limits: cell dim <= 2048, recurrent +
  * non-recurrent projection dim <= 4096, and 64 * (2 * recurrent input dim + cell dim [with a projection] + 12) bytes <= 144 KiB of
- * LDS.  Any other cycle -- lstmp-layer's Sigmoid / Tanh / ElementwiseProduct cell, lstmb-layer, a positive delay, two
- * delays in one block, a block that reads another block's state at a future time -- is refused with the node and the reason.  A
+ * LDS.  A cycle without an LstmNonlinearityComponent may be the same cell spelled out, as lstmp-layer / lstmp-batchnorm-layer /
+ * lstm-layer emit it: four affines of cell-dim rows over Append(x, IfDefined(Offset(r_t, -d))) with one x; the peepholes w_i.c and
+ * w_f.c ((NaturalGradient)PerElementScaleComponent) over IfDefined(Offset(c_t, -d)), w_o.c over c_t; i_t, f_t, o_t SigmoidComponent
+ * nodes over Sum(affine, peephole) [behind one shared DropoutComponent, a copy in test mode], g_t a TanhComponent over its affine,
+ * h_t one over c_t; the ElementwiseProductComponents c1_t = Append(f_t, IfDefined(Offset(c_t, -d))), c2_t = Append(i_t, g_t), m_t =
+ * Append(o_t, h_t); c_t a BackpropTruncationComponent (or ClipGradientComponent: scale 1) over Sum(c1_t, c2_t); r_t one over the
+ * dim-range [0, R) of the affine W_rp.m over m_t, or over m_t; the two <Scale>s are honoured separately; the same delays and
+ * limits; only rp_t and m_t may be read from outside the block.  Any other cycle -- an incomplete or differently wired cell of
+ * that kind, lstmb-layer, a positive delay, two delays in one block, a block that reads another block's state at a future time --
+ * is refused with the node and the reason.  A
  * cycle may instead be what fast-opgru-layer / fast-norm-opgru-layer emit (TDNN-OPGRU recipes, the output-gate projected GRU): two
  * affines W_z, W_o of cell-dim rows over Append(x, IfDefined(Offset(s_t, -d))), each behind a SigmoidComponent [and one shared
  * DropoutComponent, a copy in test mode], an affine W_hpart over the same x, an OutputGruNonlinearityComponent over Append(z_t,
@@ -130,7 +138,7 @@ const char *rs_last_error(void);
  * cell dim of 752 at most).  Anything else in a cycle that holds a GruNonlinearityComponent is refused in that sentence, extended
  * by these three layers.  The non-fast
  * gru-layer / pgru-layer / opgru-layer and their norm forms (cells of Sigmoid / Tanh / ElementwiseProduct components without either
- * nonlinearity) are refused like lstmp-layer.  The
+ * nonlinearity) are refused in the LSTM sentence: they are no complete lstmp-layer block.  The
  * rand() calls of a recurrent compilation are not replayed, so such a model loads only with --dither=0 in its mfcc.conf / fbank.conf
  * (rs_nnet3_setup below: certain = 0).  Parses on the host only;
  * the device copy is made on first use or by rs_model_to_device().  Immutable afterwards, shareable
@@ -150,7 +158,12 @@ void rs_model_free(rs_model *model);
  * kernel instantiation chosen at load, frames / pixel tiles / LDS bytes per workgroup, filter chunks, grid.  Then one `lstm:` line per
  * recurrent block: name, input dim, cell / recurrent / non-recurrent dims (0 / 0: no projection), delay, the truncation component's
  * scale, dropout_mask=0|1, the kernel instantiation, chains (rows) per workgroup, LDS bytes, the split of W_all's columns into
- * feed-forward + recurrent, cell and projection tiles, the grid rule.  Then one `gru:` line per GRU block: name, input dim, cell /
+ * feed-forward + recurrent, cell and projection tiles, the grid rule.  Then one `lstmp:` line per block in the composed form
+ * (lstmp-layer / lstm-layer), named after its node c_t: input dim, cell / recurrent / non-recurrent dims (0 / 0: lstm-layer), delay,
+ * scale_c and scale_r (the two truncation components'), dropout=0|1 (the shared DropoutComponent), the kernel instantiation, chains
+ * per workgroup, LDS bytes, the feed-forward (w_x) and recurrent (w_r) columns of each of the four affines, cell and projection
+ * tiles, the grid rule; its `op: lstmp` line follows the `op: gemm <c_t>.x` of the four affines' stacked feed-forward columns
+ * (4 x cell dim rows, gate order i, f, c, o).  Then one `gru:` line per GRU block: name, input dim, cell /
  * recurrent / non-recurrent dims, delay, the truncation component's scale, norm=0|1 (a NormalizeComponent in the recurrence),
  * dropout=0|1, the kernel instantiation, chains per workgroup, LDS bytes, the split of W_z's and W_o's columns, cell and output tiles,
  * the grid rule; its `op: gru` line follows the `op: gemm` of the stacked feed-forward columns (3 x cell dim rows).  Then one `pgru:` line per
@@ -453,8 +466,8 @@ int rs_bind_host_thread(int32_t device_id);
 /* Parity taps (only with opts.keep_intermediates): kind 0 = nnet input features (T x C), 1 = iVector
  * (n x D_iv: one row offline, one row per nnet chunk for streams), 2 = log-likelihoods (T x P); 3 + k = the output of the
  * model's k-th convolution (T x heights * filters, ReLU and BatchNorm applied; batch calls only); 64 + k = the output rows of the
- * model's k-th recurrent block of any kind, in network order, what the layers above it read (an LSTM block: T x (recurrent +
- * non-recurrent) dim: rp, before any BatchNorm; or T x cell dim: m, without a projection; an OPGRU or PGRU block: T x (recurrent +
+ * model's k-th recurrent block of any kind, in network order, what the layers above it read (an LSTM block of either form: T x (recurrent +
+ * non-recurrent) dim: rp / rp_t, before any BatchNorm; or T x cell dim: m / m_t, without a projection; an OPGRU or PGRU block: T x (recurrent +
  * non-recurrent) dim: W_y's rows, before any BatchNorm; a fast-gru-layer block: T x cell dim: c; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
  * hold anything); 128 + k = the output rows of the model's k-th RestrictedAttentionComponent, in network order (T x heads *
  * (value-dim [+ num-left-inputs + 1 + num-right-inputs with output-context]): per head the weighted values, then the softmax

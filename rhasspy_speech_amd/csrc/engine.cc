@@ -278,7 +278,7 @@ Model::Model(const std::string &final_mdl, const std::string &hclg, const std::s
   // ... and the recurrent blocks: a cell or projection dim beyond the kernel's limits fails the load (lstm_plan.h)
   lstm_plans_.assign(am_.nnet.ops.size(), LstmLaunchPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++)
-    if (am_.nnet.ops[i].kind == LayerOp::kLstm) lstm_plans_[i] = PlanLstm(am_.nnet.ops[i].lstm, am_.nnet.ops[i].name);
+    if (am_.nnet.ops[i].kind == LayerOp::kLstm || am_.nnet.ops[i].kind == LayerOp::kLstmp) lstm_plans_[i] = PlanLstm(am_.nnet.ops[i].lstm, am_.nnet.ops[i].name);
   gru_plans_.assign(am_.nnet.ops.size(), GruLaunchPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++)
     if (am_.nnet.ops[i].kind == LayerOp::kGru) gru_plans_[i] = PlanGru(am_.nnet.ops[i].gru, am_.nnet.ops[i].name);
@@ -429,7 +429,7 @@ template <typename T> T *Model::Upload(const std::vector<T> &v) { return static_
 
 void Model::BuildGemmPlan(const LayerOp &op, GemmPlan *plan) {
   plan->op = &op;
-  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm || op.kind == LayerOp::kGru || op.kind == LayerOp::kPgru || op.kind == LayerOp::kAttention) {      // (their own operands: ToDevice; here the bias and the fused stages)
+  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm || op.kind == LayerOp::kLstmp || op.kind == LayerOp::kGru || op.kind == LayerOp::kPgru || op.kind == LayerOp::kAttention) {      // (their own operands: ToDevice; here the bias and the fused stages)
     plan->d_bias = op.bias.empty() ? nullptr : Upload(op.bias);
     plan->d_stage.clear();
     for (auto &st : op.stages) {
@@ -742,7 +742,7 @@ void Model::ToDevice() {
   lstm_dev_.assign(am_.nnet.ops.size(), LstmOperands());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++) {
     const LayerOp &op = am_.nnet.ops[i];
-    if (op.kind != LayerOp::kLstm) continue;
+    if (op.kind != LayerOp::kLstm && op.kind != LayerOp::kLstmp) continue;      // (the composed form shares the images)
     std::vector<float> wr_t, wrp_t;
     LstmWeightImages(op.lstm, lstm_plans_[i], &wr_t, &wrp_t);
     lstm_dev_[i].wr_t = Upload(wr_t);
@@ -953,7 +953,7 @@ std::string Model::Describe() const {
      << " left_context=" << n.left_context << " right_context=" << n.right_context << " priors=" << n.priors.size()
      << " components=" << n.components.size() << " ops=" << n.ops.size() << "\n";
   for (auto &op : n.ops) {
-    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm", "gru", "attention", "pgru"};
+    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm", "gru", "attention", "pgru", "lstmp"};
     os << "op: " << kinds[op.kind] << " " << op.name << " out_dim=" << op.out_dim;
     if (op.kind == LayerOp::kGemm) {
       os << " k=" << op.W.cols << " segs=";
@@ -970,6 +970,8 @@ std::string Model::Describe() const {
     if (n.ops[i].kind == LayerOp::kConv) os << "conv: " << DescribeConv(n.ops[i].name, n.ops[i].conv, conv_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)      // (one line per recurrent block)
     if (n.ops[i].kind == LayerOp::kLstm) os << "lstm: " << DescribeLstm(n.ops[i].name, n.ops[i].lstm, lstm_plans_[i]) << "\n";
+  for (size_t i = 0; i < n.ops.size(); i++)      // (... in its composed form: lstmp-layer / lstm-layer)
+    if (n.ops[i].kind == LayerOp::kLstmp) os << "lstmp: " << DescribeLstmp(n.ops[i].name, n.ops[i].lstm, lstm_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)
     if (n.ops[i].kind == LayerOp::kGru) os << "gru: " << DescribeGru(n.ops[i].name, n.ops[i].gru, gru_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)
@@ -1404,7 +1406,7 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       } else {
         LaunchConv(d, rows, s);
       }
-    } else if (op.kind == LayerOp::kLstm) {
+    } else if (op.kind == LayerOp::kLstm || op.kind == LayerOp::kLstmp) {
       if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
       const LstmBlock &k = op.lstm;
       const BufferInfo &ob = nn.bufs[op.out_buf];
@@ -1423,14 +1425,15 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       if (k.rp_buf >= 0) { d.rp = bufp[k.rp_buf]; d.ld_rp = buf_ld[k.rp_buf]; }
       d.wr_t = lstm_dev_[i].wr_t; d.wrp_t = lstm_dev_[i].wrp_t; d.b_rp = lstm_dev_[i].b_rp; d.params = lstm_dev_[i].params;
       d.cell = k.cell; d.rec_dim = k.RecDim(); d.out_dim = k.proj() ? k.rec + k.nonrec : 0; d.rec = k.rec;
-      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale;
+      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale; d.scale_r = k.scale_r;
       d.n_utts = lstm->n_utts; d.L = L_; d.lext = ob.lext; d.rext = ob.rext;
       d.num_frames = lstm->num_frames; d.row_base = lstm->row_base;
       d.t0 = lstm->t0; d.slot = lstm->slot; d.lext_cont = k.need_lext;
       d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
       if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
       d.plan = lstm_plans_[i];
-      LaunchLstm(d, s);
+      if (op.kind == LayerOp::kLstmp) LaunchLstmp(d, s);      // (the composed form: a kernel of its own on the same descriptor)
+      else LaunchLstm(d, s);
       // operand images of what the split-fp16 layers above read: the rows the walk wrote
       if (images_on)
         for (int b : outs)
@@ -2204,7 +2207,7 @@ void Model::BatchIntermediates(const BatchCall &b, const float *ll, int ll_ld, U
     ur.lstm_out.clear();
     ur.lstm_dim.clear();
     for (auto &op : nn.ops) {
-      if (op.kind != LayerOp::kLstm && op.kind != LayerOp::kGru && op.kind != LayerOp::kPgru) continue;
+      if (op.kind != LayerOp::kLstm && op.kind != LayerOp::kLstmp && op.kind != LayerOp::kGru && op.kind != LayerOp::kPgru) continue;
       const LstmBlock &k = op.lstm;
       const bool gru = op.kind == LayerOp::kGru, pgru = op.kind == LayerOp::kPgru;
       // (a block around a GruNonlinearityComponent: W_y's rows, without a projection the c columns of [h | c])

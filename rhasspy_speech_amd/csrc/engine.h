@@ -104,7 +104,7 @@ struct ConvOperands {     // one LayerOp of kind kConv (W in the kernel's order,
   int *tab0 = nullptr, *tab1 = nullptr;
 };
 
-struct LstmOperands {     // one LayerOp of kind kLstm: LstmWeightImages' two matrices, the projection's bias, the nonlinearity's <Params>
+struct LstmOperands {     // one LayerOp of kind kLstm or kLstmp: LstmWeightImages' two matrices, the projection's bias, the nonlinearity's <Params>
   float *wr_t = nullptr, *wrp_t = nullptr, *b_rp = nullptr, *params = nullptr;
 };
 struct GruOperands {      // one LayerOp of kind kGru: GruWeightImages' two matrices, W_y's bias, the nonlinearity's <w_h>

@@ -180,6 +180,8 @@ void LaunchGather(const GatherDev &d, int rows, hipStream_t s);
 void LaunchAttention(const AttentionDev &d, int rows, hipStream_t s);
 // The walk of a recurrent block over the chains of a call (nnet_lstm.hip; the descriptor and the load-time plan: lstm_plan.h)
 void LaunchLstm(const LstmDev &d, hipStream_t s);
+// The same walk of a block in its composed form, lstmp-layer / lstm-layer (nnet_lstmp.hip; the same descriptor and plan)
+void LaunchLstmp(const LstmDev &d, hipStream_t s);
 // ... of a GRU block (nnet_gru.hip; gru_plan.h)
 void LaunchGru(const GruDev &d, hipStream_t s);
 // ... of a block around a GruNonlinearityComponent (nnet_pgru.hip; pgru_plan.h)

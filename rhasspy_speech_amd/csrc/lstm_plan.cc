@@ -54,4 +54,13 @@ std::string DescribeLstm(const std::string &name, const LstmBlock &b, const Lstm
   return os.str();
 }
 
+std::string DescribeLstmp(const std::string &name, const LstmBlock &b, const LstmLaunchPlan &p) {
+  std::ostringstream os;
+  os << name << " input=" << b.in_dim << " cell=" << b.cell << " rec=" << b.rec << " nonrec=" << b.nonrec << " delay=" << b.delay << " scale_c=" << b.scale
+     << " scale_r=" << b.scale_r << " dropout=" << (b.dropout ? 1 : 0) << " kernel=lstmp16x16x4<w" << kLstmWaves << "> rows_per_block=" << p.rows_per_block
+     << " lds=" << p.lds_bytes << " w_x=" << p.x_cols << " w_r=" << p.r_cols << " cell_tiles=" << p.cell_tiles << " out_tiles=" << p.out_tiles
+     << " grid=chains/" << p.rows_per_block;
+  return os.str();
+}
+
 }  // namespace rs

@@ -1,7 +1,8 @@
 // Recurrent blocks (nnet3's fast-lstmp-layer / fast-lstm-layer) on the device (nnet_lstm.hip): the descriptor the kernel takes by
 // value and the host-only planner that decides, when the model loads, which instantiation walks a block, how many chains a
 // workgroup owns, what it keeps in LDS and on which grid.  Nothing here includes a HIP header (tests/host/lstm_plan_check.cc compiles
-// it with g++).
+// it with g++).  The composed form of the same cell (lstmp-layer / lstm-layer, model.h: LstmBlock::composed) shares the descriptor, the
+// planner and the weight images; it is walked by a kernel of its own (nnet_lstmp.hip) in that form's arithmetic order.
 //
 // A block (model.h: LstmBlock) per row t, with the delay d:
 //   gates = pre[t] + W_r s_r[t - d];  (c, m) = LstmNonlinearity(gates, s_c[t - d]);  rp = W_rp m + b;  s_c[t] = scale c, s_r[t] = scale rp[0:rec]
@@ -54,6 +55,9 @@ constexpr int LstmGridX(int n_utts, int delay, int stride) { return (n_utts * Ls
 void LstmWeightImages(const LstmBlock &b, const LstmLaunchPlan &p, std::vector<float> *wr_t, std::vector<float> *wrp_t);
 // "name input=32 cell=32 rec=8 nonrec=8 delay=3 scale=1 dropout_mask=0 kernel=lstm16x16x4<w8> rows_per_block=16 lds=... grid=chains/16"
 std::string DescribeLstm(const std::string &name, const LstmBlock &b, const LstmLaunchPlan &p);
+// the line of a block in its composed form (lstmp-layer / lstm-layer; the same plan, walked by nnet_lstmp.hip):
+// "name input=32 cell=32 rec=8 nonrec=8 delay=3 scale_c=1 scale_r=1 dropout=0 kernel=lstmp16x16x4<w8> rows_per_block=16 lds=... grid=chains/16"
+std::string DescribeLstmp(const std::string &name, const LstmBlock &b, const LstmLaunchPlan &p);
 
 struct LstmDev {
   // frame buffers (row 0 of the call's layout, kernels.h) and their pitches
@@ -66,6 +70,7 @@ struct LstmDev {
   int cell, rec_dim, out_dim, rec;                // rec_dim: width of s_r; out_dim / rec: rp's width and its recurrent part (0 without a projection)
   int delay, stride;
   float scale;
+  float scale_r;         // the composed form only (nnet_lstmp.hip): `scale` is the cell's truncation component's, this the recurrent state's
   // geometry: utterance u has frames [0, T_u) at rows row_base[u] + L + t; the walk covers t in [-lext, T_u + rext) (nothing where T_u = 0)
   int n_utts, L, lext, rext;
   const int *num_frames, *row_base;

@@ -627,7 +627,9 @@ static Component ReadComponent(KaldiReader &r) {
           // vector or matrix: decide by row count
           MatF m;
           r.ReadMatrix(&m);
-          if (m.rows <= 1 && tok != "<LinearParams>" && tok != "<Params>") c.v[tok] = m.d;
+          // (<Params> is a matrix in a LinearComponent or an LstmNonlinearityComponent, a vector in the per-element scales)
+          const bool scales = c.type == "PerElementScaleComponent" || c.type == "NaturalGradientPerElementScaleComponent";
+          if (m.rows <= 1 && tok != "<LinearParams>" && (tok != "<Params>" || scales)) c.v[tok] = m.d;
           else c.m[tok] = m;
           continue;
         }
@@ -893,7 +895,7 @@ int ComponentOutputDim(const Component &c, const std::string &name) {
     return d + (add ? 1 : 0);
   }
   if (c.i.count("<Dim>")) return c.Int("<Dim>");
-  if (c.type == "PerElementScaleComponent" || c.type == "FixedScaleComponent") {
+  if (c.type == "PerElementScaleComponent" || c.type == "NaturalGradientPerElementScaleComponent" || c.type == "FixedScaleComponent") {
     auto it = c.v.find(c.type == "FixedScaleComponent" ? "<Scales>" : "<Params>");
     if (it != c.v.end()) return (int)it->second.size();
   }
@@ -1153,6 +1155,11 @@ struct BlockNodes {
   bool pgru = false;
   int wo = -1, zs = -1, os = -1, zd = -1, od = -1;   // o_t_pre, the two SigmoidComponent nodes, with dropout the two DropoutComponent nodes
   int hp = -1, cd = -1, wy = -1, sp = -1, nm = -1;   // hpart_t (not part of the cycle), cdoto, y_t / y_t_tmp, its dim-range, s_t_renorm (norm variant)
+  // the composed LSTM(P) cell (xconfig/lstm.py: XconfigLstmpLayer, XconfigLstmLayer): tr = sc = c_t, sr = r_t, wa = i1_t (where the
+  // block is placed); ga: the affine nodes i1_t, f1_t, g1_t, o1_t; pe: the peephole nodes i2_t, f2_t, o2_t; m = m_t; with a
+  // projection rp = rp_t and r = r_t_preclip; cdrop: the shared DropoutComponent behind i, f and o is there
+  bool composed = false, cdrop = false;
+  int ga[4] = {-1, -1, -1, -1}, pe[3] = {-1, -1, -1};
   std::vector<int> members;                          // the cycle's nodes (a GRU block: and hpart_t)
   std::vector<DescPart> x_parts;                     // W_all's input without its recurrent part
 };
@@ -1240,8 +1247,8 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
         if (b.nl >= 0) refuse(n, "a second LstmNonlinearityComponent in one cycle");
         b.nl = n;
       }
-    if (b.nl < 0 && !gru_cycle)
-      refuse(scc[0], "the cycle has no LstmNonlinearityComponent; lstmp-layer (Sigmoid / Tanh / ElementwiseProduct components), lstmb-layer and GRU layers are not supported");
+    // (a cycle without any of the three nonlinearities has to be the same cell spelled out: lstmp-layer / lstm-layer, below)
+    const bool composed_cycle = b.nl < 0 && !gru_cycle;
     // a recurrent part: one optional term, Offset(x, -d) with 1 <= d <= kLstmMaxDelay
     auto recurrent_part = [&](int at, const DescPart &p, int *node) {
       if (p.terms.size() != 1 || p.terms[0].const_t || p.terms[0].scale != 1.0f) refuse(at, "its recurrent input is not IfDefined(Offset(node, -delay))");
@@ -1268,6 +1275,165 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
       }
       return true;
     };
+    if (composed_cycle) {
+      // ---- the composed LSTM(P) cell (xconfig/lstm.py: XconfigLstmpLayer :440-565, XconfigLstmLayer :160-255)
+      auto no = [&](int n, const std::string &why) {
+        refuse(n, "the cycle has no LstmNonlinearityComponent and is no complete lstmp-layer / lstm-layer block (four affines, three peepholes, Sigmoid / Tanh / "
+                  "ElementwiseProduct components, two truncation components) either; lstmb-layer and the non-fast GRU layers are not supported: " + why);
+      };
+      auto is_trunc = [&](int n) { const std::string t = comp_type(n); return t == "BackpropTruncationComponent" || t == "ClipGradientComponent"; };
+      auto is_peephole = [&](int n) { const std::string t = comp_type(n); return t == "NaturalGradientPerElementScaleComponent" || t == "PerElementScaleComponent"; };
+      auto two_plain = [&](int n, int *x, int *y) {      // Append(x, y) of two plain nodes
+        const NnetNode &nd = nodes[n];
+        if (nd.input.parts.size() != 2 || !plain_part(nd.input.parts[0]) || !plain_part(nd.input.parts[1])) return false;
+        *x = nd.input.parts[0].terms[0].node;
+        *y = nd.input.parts[1].terms[0].node;
+        return true;
+      };
+      auto two_sum = [&](int n, int *x, int *y) {        // Sum(x, y) of two plain nodes
+        const NnetNode &nd = nodes[n];
+        if (nd.input.parts.size() != 1 || nd.input.parts[0].terms.size() != 2) return false;
+        for (auto &t : nd.input.parts[0].terms) if (t.const_t || t.optional || t.offset != 0 || t.scale != 1.0f) return false;
+        *x = nd.input.parts[0].terms[0].node;
+        *y = nd.input.parts[0].terms[1].node;
+        return true;
+      };
+      b.composed = true;
+      // the two truncation nodes: c_t over Sum(c1_t, c2_t), r_t over one node
+      int c_t = -1, r_t = -1, c1 = -1, c2 = -1;
+      for (int n : scc) {
+        if (!is_trunc(n)) continue;
+        int x, y;
+        if (two_sum(n, &x, &y)) {
+          if (c_t >= 0) no(n, "a second truncation node over a Sum() in one cycle");
+          c_t = n; c1 = x; c2 = y;
+        } else {
+          if (r_t >= 0) no(n, "a second truncation node over one node in one cycle");
+          r_t = n;
+        }
+      }
+      if (c_t < 0) no(scc[0], "it has no cell node c_t, a BackpropTruncationComponent / ClipGradientComponent over Sum(c1_t, c2_t)");
+      if (r_t < 0) no(c_t, "it has no recurrent state node r_t, a BackpropTruncationComponent / ClipGradientComponent over r_t_preclip or m_t");
+      const int C = b.cell = nodes[c_t].dim;
+      b.tr = b.sc = c_t;
+      b.sr = r_t;
+      b.delay = 0;
+      // a recurrent input of the block: IfDefined(Offset(want, -d)), one d
+      auto state_part = [&](int at, const DescPart &p, int want, const char *role) {
+        int node = -1;
+        const int d2 = recurrent_part(at, p, &node);
+        if (b.delay == 0) b.delay = d2;
+        if (d2 != b.delay) refuse(at, "two different delays in one block, " + std::to_string(d2) + " and " + std::to_string(b.delay));
+        if (node != want) no(at, std::string(role) + " reads " + nodes[node].name + ", not " + nodes[want].name);
+      };
+      auto is_product = [&](int n) { return comp_type(n) == "ElementwiseProductComponent" && nodes[n].dim == C && nodes[n].input.dim == 2 * C; };
+      // c1_t = Append(f_t, IfDefined(Offset(c_t, -d))), c2_t = Append(i_t, g_t)
+      if (!is_product(c1) || !is_product(c2)) no(c_t, "its input is not the Sum() of two ElementwiseProductComponent nodes of the cell's dim");
+      const NnetNode &c1n = nodes[c1];
+      if (c1n.input.parts.size() != 2 || !plain_part(c1n.input.parts[0])) no(c1, "its input is not Append(f_t, IfDefined(Offset(c_t, -delay)))");
+      const int f_t = c1n.input.parts[0].terms[0].node;
+      state_part(c1, c1n.input.parts[1], c_t, "the product c1_t");
+      int i_t = -1, g_t = -1;
+      if (!two_plain(c2, &i_t, &g_t)) no(c2, "its input is not Append(i_t, g_t)");
+      // the recurrent state: r_t over the dim-range of W_rp.m's node, or over m_t
+      int m_t = only_input(r_t);
+      if (m_t < 0) no(r_t, "its input is not one node");
+      if (nodes[m_t].kind == NnetNode::kDimRange) {
+        b.r = m_t;
+        b.rp = nodes[b.r].range_node;
+        b.rec_dim = nodes[b.r].dim;
+        if (!is_affine(b.rp) || !range_of(b.r, b.rp, 0, b.rec_dim) || nodes[r_t].dim != b.rec_dim) no(b.r, "the recurrent state is not the first columns of an affine component node");
+        m_t = only_input(b.rp);
+        if (m_t < 0) no(b.rp, "the projection's input is not m_t");
+      } else {
+        b.rec_dim = C;
+        if (nodes[r_t].dim != C) no(r_t, "without a projection the recurrent state is m_t, of the cell's dim");
+      }
+      b.m = m_t;
+      int o_t = -1, h_t = -1;
+      if (!is_product(m_t) || !two_plain(m_t, &o_t, &h_t)) no(m_t, "m_t is not an ElementwiseProductComponent node over Append(o_t, h_t)");
+      if (comp_type(h_t) != "TanhComponent" || only_input(h_t) != c_t) no(h_t, "h_t is not a TanhComponent node over the cell " + nodes[c_t].name);
+      if (comp_type(g_t) != "TanhComponent") no(g_t, "g_t is not a TanhComponent node");
+      b.ga[2] = only_input(g_t);
+      if (b.ga[2] < 0 || !is_affine(b.ga[2])) no(g_t, "g_t's input is not an affine component node");
+      // a gate: [the shared DropoutComponent over] a SigmoidComponent over Sum(affine node, peephole node)
+      int drop[3] = {-1, -1, -1}, sig[3] = {-1, -1, -1};
+      auto gate = [&](int g, int which, const char *gname) {
+        if (comp_type(g) == "DropoutComponent") {
+          drop[which] = g;
+          g = only_input(g);
+          if (g < 0) no(drop[which], "the dropout's input is not one node");
+        }
+        if (comp_type(g) != "SigmoidComponent") no(g, std::string(gname) + " is not a SigmoidComponent node [behind a DropoutComponent]");
+        sig[which] = g;
+        int a = -1, pe = -1;
+        if (!two_sum(g, &a, &pe) || !is_affine(a) || !is_peephole(pe)) no(g, "its input is not Sum(affine node, peephole node)");
+        b.ga[which == 2 ? 3 : which] = a;
+        b.pe[which] = pe;
+        const NnetNode &pn = nodes[pe];
+        if (pn.dim != C || pn.input.parts.size() != 1) no(pe, "the peephole is not of the cell's dim over one input");
+        if (which == 2) {      // w_o.c reads the current, already scaled cell
+          if (only_input(pe) != c_t) no(pe, "the output gate's peephole does not read the current cell " + nodes[c_t].name);
+        } else {
+          if (plain_part(pn.input.parts[0])) no(pe, "the peephole reads " + nodes[pn.input.parts[0].terms[0].node].name + " of the current row, not IfDefined(Offset(" + nodes[c_t].name + ", -delay))");
+          state_part(pe, pn.input.parts[0], c_t, "the peephole");
+        }
+      };
+      gate(i_t, 0, "i_t");
+      gate(f_t, 1, "f_t");
+      gate(o_t, 2, "o_t");
+      if ((drop[0] >= 0) != (drop[1] >= 0) || (drop[0] >= 0) != (drop[2] >= 0) ||
+          (drop[0] >= 0 && (nodes[drop[0]].component != nodes[drop[1]].component || nodes[drop[0]].component != nodes[drop[2]].component)))
+        no(drop[0] >= 0 ? drop[0] : drop[1] >= 0 ? drop[1] : drop[2], "the three gates do not share one DropoutComponent");
+      b.cdrop = drop[0] >= 0;
+      // the four affines: Append(x, IfDefined(Offset(r_t, -d))) over one feed-forward input
+      for (int a = 0; a < 4; a++) {
+        const NnetNode &an = nodes[b.ga[a]];
+        if (an.input.parts.size() < 2) no(b.ga[a], "its input is not Append(x, IfDefined(Offset(r_t, -delay)))");
+        state_part(b.ga[a], an.input.parts.back(), r_t, "the affine");
+        if (an.dim != C) no(b.ga[a], "the affine has " + std::to_string(an.dim) + " rows, not the cell's dim " + std::to_string(C));
+        if (a == 0) b.x_parts.assign(an.input.parts.begin(), an.input.parts.end() - 1);
+        else if (!same_parts(an.input.parts, an.input.parts.size() - 1, b.x_parts)) no(b.ga[a], "the four gates do not read the same feed-forward input");
+      }
+      b.wa = b.ga[0];
+      for (auto &p : b.x_parts) for (auto &t : p.terms) if (in_scc(t.node)) no(b.wa, "its feed-forward input reads " + nodes[t.node].name + ", a node of the cycle");
+      b.members = {c_t, r_t, c1, c2, m_t, h_t, g_t, b.ga[0], b.ga[1], b.ga[2], b.ga[3], b.pe[0], b.pe[1], b.pe[2], sig[0], sig[1], sig[2]};
+      for (int n : {drop[0], drop[1], drop[2], b.rp, b.r}) if (n >= 0) b.members.push_back(n);
+      std::sort(b.members.begin(), b.members.end());
+      if (std::adjacent_find(b.members.begin(), b.members.end()) != b.members.end()) no(c_t, "a node has two roles in the block");
+      for (int n : scc) if (!std::binary_search(b.members.begin(), b.members.end(), n)) no(n, "the node is part of the cycle but not of such a block");
+      for (int n : b.members) if (!in_scc(n)) no(n, "the node is not part of the cycle");
+      // dims against the weights
+      int x_dim = 0;
+      for (auto &p : b.x_parts) x_dim += p.dim;
+      for (int a = 0; a < 4; a++) {
+        const MatF &W = net.components[nodes[b.ga[a]].component].m.at("<LinearParams>");
+        if (W.rows != C || W.cols != x_dim + b.rec_dim)
+          no(b.ga[a], "its weights are " + std::to_string(W.rows) + " x " + std::to_string(W.cols) + ", the block needs cell-dim rows and the feed-forward input's " +
+                          std::to_string(x_dim) + " + the recurrent input's " + std::to_string(b.rec_dim) + " columns");
+      }
+      for (int g = 0; g < 3; g++) {
+        const Component &pc = net.components[nodes[b.pe[g]].component];
+        auto pit = pc.v.find("<Params>");
+        if (pit == pc.v.end() || (int)pit->second.size() != C) no(b.pe[g], "the peephole's <Params> are not a vector of the cell's dim " + std::to_string(C));
+      }
+      if (b.rp >= 0) {
+        const MatF &Wrp = net.components[nodes[b.rp].component].m.at("<LinearParams>");
+        if (Wrp.cols != C || Wrp.rows < b.rec_dim) no(b.rp, "W_rp is " + std::to_string(Wrp.rows) + " x " + std::to_string(Wrp.cols) + ", the block needs cell-dim columns and at least the recurrent dim's rows");
+      }
+      // only the output has a buffer the layers above may read: rp_t, or m_t (without a projection; with one, where the collapser
+      // has folded a W_rp.m that does not reduce the dim into the affine above, which then reads m_t)
+      for (int n = 0; n < N; n++) {
+        if (std::binary_search(b.members.begin(), b.members.end(), n) || index[n] < 0) continue;
+        std::vector<int> d;
+        deps(n, &d);
+        for (int m : d)
+          if (m != b.rp && m != m_t && std::binary_search(b.members.begin(), b.members.end(), m)) no(m, "the node is read from outside the block, by " + nodes[n].name);
+      }
+      for (int n : b.members) (*block_of)[n] = (int)blocks->size();
+      blocks->push_back(std::move(b));
+      continue;
+    }
     if (pgru_cycle) {
       // ---- a block around a GruNonlinearityComponent (xconfig/gru.py: XconfigFastGruLayer, XconfigFastPgruLayer, XconfigFastNormPgruLayer)
       const std::string kWhat = "a GruNonlinearityComponent (fast-gru-layer, fast-pgru-layer, fast-norm-pgru-layer) ";
@@ -1602,7 +1768,7 @@ void Nnet::Compile() {
   int out_node = FindNode("output");
   int in_node = FindNode("input"), iv_node = FindNode("ivector");
   const int N = (int)nodes.size();
-  // recurrent blocks: the cycles of the node graph, each of which has to be what fast-lstmp-layer / fast-lstm-layer,
+  // recurrent blocks: the cycles of the node graph, each of which has to be what fast-lstmp-layer / fast-lstm-layer, lstmp-layer / lstm-layer,
   // fast-opgru-layer / fast-norm-opgru-layer or fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer emit
   std::vector<BlockNodes> blocks;
   std::vector<int> block_of(N, -1);
@@ -1868,6 +2034,74 @@ void Nnet::Compile() {
         if (proj) node_buf[b.wy] = node_buf[b.sp] = k.y_buf;
         node_buf[b.tr] = k.s_buf;
         w.out_buf = k.hc_buf;
+        w.terms.push_back({k.pre_buf, 0, 0, 1.0f});
+        ops.push_back(w);
+        continue;
+      }
+      if (b.composed) {
+        // ---- the composed LSTM(P) cell: the x-columns of W_i, W_f, W_c and W_o stacked to one layer GEMM of 4 cell rows with their
+        // biases, in the gate order the kernel's weight image takes (each element's sum over k is what its own affine would compute),
+        // their recurrent columns as W_r, the three peephole vectors as params, then the walk
+        const int C = b.cell, R = b.rec_dim, l = lext[b.wa], r = rext[b.wa];
+        const int in_dim = components[nodes[b.ga[0]].component].m.at("<LinearParams>").cols - R;
+        LayerOp g;
+        g.kind = LayerOp::kGemm;
+        g.name = nodes[b.tr].name + ".x";
+        g.out_dim = 4 * C;
+        g.W.Resize(4 * C, in_dim);
+        g.bias.assign(4 * C, 0.0f);
+        LayerOp w;
+        w.kind = LayerOp::kLstmp;
+        w.name = nodes[b.tr].name;
+        w.out_dim = 2 * C;
+        LstmBlock &k = w.lstm;
+        k.composed = true;
+        k.W_r.Resize(4 * C, R);
+        for (int a = 0; a < 4; a++) {
+          const Component &ac = components[nodes[b.ga[a]].component];
+          const MatF &W = ac.m.at("<LinearParams>");
+          for (int row = 0; row < C; row++) {
+            for (int c = 0; c < in_dim; c++) g.W(a * C + row, c) = W(row, c);
+            for (int c = 0; c < R; c++) k.W_r(a * C + row, c) = W(row, in_dim + c);
+          }
+          auto bit = ac.v.find("<BiasParams>");
+          if (bit != ac.v.end() && !bit->second.empty()) {
+            if ((int)bit->second.size() != C) Fail("nnet3: bias dim mismatch in node " + nodes[b.ga[a]].name);
+            std::copy(bit->second.begin(), bit->second.end(), g.bias.begin() + a * C);
+          }
+        }
+        const int wcol = add_gemm_segs(&g, b.x_parts, b.wa, {0});
+        if (wcol != in_dim) Fail("nnet3: internal error, the feed-forward input of recurrent block " + w.name + " does not cover its weights' columns");
+        g.out_buf = new_buf(4 * C, l, r);
+        ops.push_back(g);
+        k.params.Resize(3, C);
+        for (int p = 0; p < 3; p++) {
+          const std::vector<float> &v = components[nodes[b.pe[p]].component].v.at("<Params>");
+          for (int c = 0; c < C; c++) k.params(p, c) = v[c];
+        }
+        k.in_dim = in_dim; k.cell = C; k.rec = b.rp >= 0 ? R : 0; k.nonrec = b.rp >= 0 ? nodes[b.rp].dim - R : 0;
+        k.delay = b.delay;
+        k.scale = TruncationScale(components[nodes[b.tr].component]);        // (a ClipGradientComponent has no <Scale>: 1)
+        k.scale_r = TruncationScale(components[nodes[b.sr].component]);
+        k.dropout = b.cdrop;
+        k.need_lext = b.need_lext;
+        k.pre_buf = g.out_buf;
+        k.cm_buf = new_buf(2 * C, l, r);           // [sc | m]
+        k.st_buf = new_buf(C + R, l, r);           // [sc | sr]
+        node_buf[b.m] = k.cm_buf;
+        node_col[b.m] = C;
+        node_buf[b.tr] = node_buf[b.sr] = k.st_buf;
+        node_col[b.sr] = C;
+        if (b.rp >= 0) {
+          const Component &rp = components[nodes[b.rp].component];
+          k.W_rp = rp.m.at("<LinearParams>");
+          auto rb = rp.v.find("<BiasParams>");
+          k.b_rp = rb != rp.v.end() && !rb->second.empty() ? rb->second : std::vector<float>(k.W_rp.rows, 0.0f);
+          if ((int)k.b_rp.size() != k.W_rp.rows) Fail("nnet3: bias dim mismatch in node " + nodes[b.rp].name);
+          k.rp_buf = new_buf(k.rec + k.nonrec, l, r);
+          node_buf[b.rp] = node_buf[b.r] = k.rp_buf;
+        }
+        w.out_buf = k.cm_buf;
         w.terms.push_back({k.pre_buf, 0, 0, 1.0f});
         ops.push_back(w);
         continue;
@@ -2206,7 +2440,7 @@ void Nnet::SetSubsampling(int factor) {
   // a layer X that feeds a Sum dense while its own input W stayed strided: X's GEMM ran over all rows and read rows of W nobody
   // had written in that call.)
   for (auto it = ops.rbegin(); it != ops.rend(); ++it) {
-    if (it->kind == LayerOp::kLstm) {
+    if (it->kind == LayerOp::kLstm || it->kind == LayerOp::kLstmp) {
       // a block's buffers hold the same rows: every residue one of them is read at, and every residue the chains of those rows
       // pass through (delay 3 under factor 3 stays in its class; delay 2 visits all three)
       const LstmBlock &k = it->lstm;

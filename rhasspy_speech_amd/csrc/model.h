@@ -210,6 +210,11 @@ struct LstmBlock {
   int delay = 0;                  // frames towards the past, 1 .. kLstmMaxDelay
   float scale = 1.0f;
   bool dropout_mask = false;      // use-dropout=true with its DropoutMaskComponent node: all ones in test mode
+  // the composed form (LayerOp::kLstmp, below): `scale` is the <Scale> of the truncation component `c`, scale_r that of `r`;
+  // dropout: the shared DropoutComponent behind i, f and o is present (a copy in test mode); cm_buf holds [sc | m]
+  bool composed = false;
+  float scale_r = 1.0f;
+  bool dropout = false;
   MatF W_r;                       // 4 cell x RecDim(): W_all's recurrent columns
   MatF params;                    // 3 x cell: w_ic, w_fc, w_oc
   MatF W_rp;                      // (rec + nonrec) x cell
@@ -224,6 +229,15 @@ struct LstmBlock {
   int OutDim() const { return rec > 0 ? rec + nonrec : cell; }
 };
 constexpr int kLstmMaxDelay = 8;
+// The same cell spelled out as separate components: what nnet3's lstmp-layer / lstmp-batchnorm-layer / lstm-layer emit
+// (xconfig/lstm.py: XconfigLstmpLayer, XconfigLstmLayer), recognised as a unit and held in an LstmBlock with composed = true.  Four
+// affines over Append(x, IfDefined(Offset(r_t, -d))) stacked in gate order i, f, c(g), o (pre = W_x x + b a kGemm op, W_r their
+// recurrent columns), three NaturalGradientPerElementScaleComponent peepholes (params), Sigmoid / Tanh nodes, three
+// ElementwiseProductComponents, two truncation components.  With sc, sr the outputs of c_t and r_t, per row t, every product and
+// sum a rounding of its own:
+//   i = Sigmoid((pre_i + W_ri sr[t - d]) + w_ic . sc[t - d]),  f likewise,  g = Tanh(pre_g + W_rg sr[t - d])
+//   sc[t] = scale (f . sc[t - d] + i . g);  o = Sigmoid((pre_o + W_ro sr[t - d]) + w_oc . sc[t]);  m = o . Tanh(sc[t])
+//   rp = W_rp m + b_rp,  sr[t] = scale_r rp[0:rec]     or, without a projection,     sr[t] = scale_r m
 
 // A recurrent block of the output-gate projected GRU: what nnet3's fast-opgru-layer / fast-norm-opgru-layer emit (xconfig/gru.py),
 // recognised as a unit (Nnet::Compile).  With s the recurrent state (scaled), c the cell state (read back unscaled), zero where the
@@ -298,8 +312,9 @@ struct LayerOp {
   // kConv: out = stages(bias + conv(terms)); kGather: out[:, i] = part(gather_part[i])[:, gather_col[i]] (PermuteComponent over an Append)
   // kLstm: the serial part of a recurrent block (lstm); out_buf = lstm.cm_buf.  kGru: the same of a GRU block (gru); out_buf = gru.hc_buf
   // kPgru: the same of a block around a GruNonlinearityComponent (pgru); out_buf = pgru.hc_buf
+  // kLstmp: the same of an LSTM block in its composed form (lstm, with lstm.composed); out_buf = lstm.cm_buf
   // kAttention: out = attention(terms[0]), no fused stage (the result matrix of the op is the component's output): one term, the source; the rows it reads are terms[0].offset + attention.TimeOffset(o)
-  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm, kGru, kAttention, kPgru } kind = kGemm;
+  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm, kGru, kAttention, kPgru, kLstmp } kind = kGemm;
   std::string name;
   int out_buf = -1, out_dim = 0;
   // kGemm
@@ -317,7 +332,7 @@ struct LayerOp {
   std::vector<EltStage> stages; // applied after the gemm/sum, in order
   ConvGeom conv;                           // kConv
   std::vector<int> gather_part, gather_col;   // kGather, per output column: the term and the column inside it
-  LstmBlock lstm;                             // kLstm
+  LstmBlock lstm;                             // kLstm, kLstmp
   GruBlock gru;                               // kGru
   AttentionGeom attention;                    // kAttention
   PgruBlock pgru;                             // kPgru
@@ -339,7 +354,7 @@ struct Nnet {
   std::vector<BufferInfo> bufs;
   int input_buf = -1, output_buf = -1;
   int left_context = 0, right_context = 0;
-  bool recurrent = false;      // has at least one recurrent block (kLstm, kGru or kPgru op)
+  bool recurrent = false;      // has at least one recurrent block (kLstm, kLstmp, kGru or kPgru op)
   // What the reference's binaries do to the network before the first frame (nnet3_setup.h): the network is the one
   // CollapseModel leaves behind, and rand() has been called `setup_rand_calls` times (the dither seeds follow from that).
   long setup_rand_calls = 0;

@@ -286,7 +286,7 @@ StreamPool *Model::Pool() {
   p->dec_ctr = static_cast<long long *>(dalloc((size_t)p->max_slots * 64));
   p->lstm_ring.assign(nn.ops.size(), nullptr);
   for (size_t i = 0; i < nn.ops.size(); i++)
-    if (nn.ops[i].kind == LayerOp::kLstm) {
+    if (nn.ops[i].kind == LayerOp::kLstm || nn.ops[i].kind == LayerOp::kLstmp) {      // (the composed form parks [sc | sr] the same way)
       const LstmBlock &k = nn.ops[i].lstm;
       p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * (k.cell + k.RecDim()) * 4));
     } else if (nn.ops[i].kind == LayerOp::kGru) {      // (a GRU block's rows are [c | s]: gru_plan.h)

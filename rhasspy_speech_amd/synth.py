@@ -219,6 +219,9 @@ class ModelSpec:
     # projection dims; 0 and 0: no projection, fast-lstm-layer), delay (frames towards the past, default 3), scale (the
     # BackpropTruncationComponent's <Scale>, 1 - delay / decay-time in a recipe; default 1), dropout (use-dropout=true with its
     # DropoutMaskComponent node, default False), batchnorm (a BatchNorm on the block's output, default False).
+    # form="composed" writes the same cell as separate components, what lstmp-layer / lstmp-batchnorm-layer (batchnorm=True) /
+    # lstm-layer (rec = nonrec = 0) emit: dropout is then the shared DropoutComponent behind i, f and o, scale the <Scale> of both
+    # truncation components (scale_c / scale_r set them apart), clipgrad=True makes them ClipGradientComponents as older models have.
     lstm_layers: Tuple[Dict[str, object], ...] = ()
     # Recurrent blocks of the output-gate projected GRU (nnet3's fast-opgru-layer / fast-norm-opgru-layer, xconfig/gru.py), placed
     # like lstm_layers (behind the LSTM blocks of the same `after`).  One dict per block: after, cell, rec, nonrec (both positive),
@@ -584,6 +587,10 @@ def _lstm_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.
                 prev: str, prev_dim: int) -> Tuple[str, int]:
     """The components and nodes XconfigFastLstmpLayer / XconfigFastLstmLayer emit (xconfig/lstm.py:1120-1198, 706-753), in their
     order.  Returns the node the next layer reads and its dim."""
+    if layer.get("form", "fast") == "composed":
+        return _lstmp_block(cfg, comps, rng, name, layer, prev, prev_dim)
+    if layer.get("form", "fast") != "fast":
+        raise ValueError("lstm layer: form is 'fast' (the default) or 'composed'")
     C, R, P, out_dim = lstm_layer_dims(layer)
     d, scale = int(layer.get("delay", 3)), float(layer.get("scale", 1.0))
     dropout, proj = bool(layer.get("dropout", False)), R > 0
@@ -628,6 +635,102 @@ def _lstm_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.
         cfg.append(f"dim-range-node name={name}.c_trunc input-node={name}.cm_trunc dim-offset=0 dim={C}")
         cfg.append(f"dim-range-node name={name}.m_trunc input-node={name}.cm_trunc dim-offset={C} dim={C}")
         out = f"{name}.m"
+    if layer.get("batchnorm", False):
+        bn = out + "_batchnorm"
+        mean, var = (0.1 * rng.standard_normal(out_dim)).astype(np.float32), rng.uniform(0.05, 0.2, out_dim).astype(np.float32)
+        comps.append((bn, lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+        cfg.append(f"component-node name={bn} component={bn} input={out}")
+        out = bn
+    return out, out_dim
+
+
+def _w_ng_per_element_scale(w: KaldiWriter, scales: np.ndarray) -> None:
+    # nnet-simple-component.cc:3840-3856 (NaturalGradientPerElementScaleComponent::Write), behind WriteUpdatableCommon
+    _updatable_open(w, "NaturalGradientPerElementScaleComponent")
+    w.token("<Params>").vector(scales).token("<IsGradient>").boolean(False)
+    w.token("<Rank>").i32(8).token("<UpdatePeriod>").i32(10).token("<NumSamplesHistory>").f32(2000.0).token("<Alpha>").f32(4.0)
+    w.token("</NaturalGradientPerElementScaleComponent>")
+
+
+def _w_clip_gradient(w: KaldiWriter, dim: int) -> None:
+    # nnet-simple-component.cc:577-600
+    w.token("<ClipGradientComponent>").token("<Dim>").i32(dim).token("<ClippingThreshold>").f32(30.0)
+    w.token("<NormBasedClipping>").boolean(True)
+    w.token("<SelfRepairClippedProportionThreshold>").f32(0.01).token("<SelfRepairTarget>").f32(0.0).token("<SelfRepairScale>").f32(1.0)
+    w.token("<NumElementsClipped>").i32(0).token("<NumElementsProcessed>").i32(0)
+    w.token("<NumSelfRepaired>").i32(0).token("<NumBackpropped>").i32(0)
+    w.token("</ClipGradientComponent>")
+
+
+def _lstmp_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.Generator, name: str, layer: Dict[str, object],
+                 prev: str, prev_dim: int) -> Tuple[str, int]:
+    """The components and nodes XconfigLstmpLayer / XconfigLstmLayer emit (xconfig/lstm.py:440-565, 160-255), under their names.
+    Returns the node the next layer reads and its dim."""
+    C, R, P, out_dim = lstm_layer_dims(layer)
+    d, scale = int(layer.get("delay", 3)), float(layer.get("scale", 1.0))
+    scale_c, scale_r = float(layer.get("scale_c", scale)), float(layer.get("scale_r", scale))
+    dropout, proj, clipgrad = bool(layer.get("dropout", False)), R > 0, bool(layer.get("clipgrad", False))
+    rec_dim = R if proj else C
+    if clipgrad and (scale_c != 1.0 or scale_r != 1.0):
+        raise ValueError("lstm layer: a ClipGradientComponent has no scale")
+
+    def randn(o, i):
+        return (rng.standard_normal((o, i)) / math.sqrt(i)).astype(np.float32)
+
+    def randb(n):
+        return (rng.standard_normal(n) * 0.1).astype(np.float32)
+
+    def affine(W, b):
+        return lambda w, W=W, b=b: _w_affine(w, "NaturalGradientAffineComponent", W, b)
+
+    def trunc(n, s):
+        if clipgrad:
+            return lambda w, n=n: _w_clip_gradient(w, n)
+        return lambda w, n=n, s=s: _w_backprop_truncation(w, n, s, d)
+
+    for g in ("i", "f", "o"):
+        W, b = np.concatenate([randn(C, prev_dim), randn(C, rec_dim)], axis=1), randb(C)
+        comps.append((f"{name}.W_{g}.xr", affine(W, b)))
+        comps.append((f"{name}.w_{g}.c", lambda w, v=randb(C): _w_ng_per_element_scale(w, v)))
+    W, b = np.concatenate([randn(C, prev_dim), randn(C, rec_dim)], axis=1), randb(C)
+    comps.append((f"{name}.W_c.xr", affine(W, b)))
+    for g in ("i", "f", "o"):
+        comps.append((f"{name}.{g}", lambda w: _w_nonlinear(w, "SigmoidComponent", C)))
+    for g in ("g", "h"):
+        comps.append((f"{name}.{g}", lambda w: _w_nonlinear(w, "TanhComponent", C)))
+    if dropout:
+        comps.append((f"{name}.dropout", lambda w: _w_dropout(w, C)))
+    for g in ("c1", "c2", "m"):
+        comps.append((f"{name}.{g}", lambda w: _w_elementwise_product(w, 2 * C, C)))
+    comps.append((f"{name}.c", trunc(C, scale_c)))
+    rec = f"IfDefined(Offset({name}.r_t, {-d}))"
+    c_del = f"IfDefined(Offset({name}.c_t, {-d}))"
+    cfg.append(f"component-node name={name}.c_t component={name}.c input=Sum({name}.c1_t, {name}.c2_t)")
+    for g in ("i", "f", "o"):
+        cfg.append(f"component-node name={name}.{g}1_t component={name}.W_{g}.xr input=Append({prev}, {rec})")
+        cfg.append(f"component-node name={name}.{g}2_t component={name}.w_{g}.c input={c_del if g != 'o' else name + '.c_t'}")
+        if dropout:
+            cfg.append(f"component-node name={name}.{g}_t_predrop component={name}.{g} input=Sum({name}.{g}1_t, {name}.{g}2_t)")
+            cfg.append(f"component-node name={name}.{g}_t component={name}.dropout input={name}.{g}_t_predrop")
+        else:
+            cfg.append(f"component-node name={name}.{g}_t component={name}.{g} input=Sum({name}.{g}1_t, {name}.{g}2_t)")
+    cfg.append(f"component-node name={name}.h_t component={name}.h input={name}.c_t")
+    cfg.append(f"component-node name={name}.g1_t component={name}.W_c.xr input=Append({prev}, {rec})")
+    cfg.append(f"component-node name={name}.g_t component={name}.g input={name}.g1_t")
+    cfg.append(f"component-node name={name}.c1_t component={name}.c1 input=Append({name}.f_t, {c_del})")
+    cfg.append(f"component-node name={name}.c2_t component={name}.c2 input=Append({name}.i_t, {name}.g_t)")
+    cfg.append(f"component-node name={name}.m_t component={name}.m input=Append({name}.o_t, {name}.h_t)")
+    if proj:
+        comps.append((f"{name}.W_rp.m", affine(randn(R + P, C), randb(R + P))))
+        comps.append((f"{name}.r", trunc(R, scale_r)))
+        cfg.append(f"component-node name={name}.rp_t component={name}.W_rp.m input={name}.m_t")
+        cfg.append(f"dim-range-node name={name}.r_t_preclip input-node={name}.rp_t dim-offset=0 dim={R}")
+        cfg.append(f"component-node name={name}.r_t component={name}.r input={name}.r_t_preclip")
+        out = f"{name}.rp_t"
+    else:
+        comps.append((f"{name}.r", trunc(C, scale_r)))
+        cfg.append(f"component-node name={name}.r_t component={name}.r input={name}.m_t")
+        out = f"{name}.m_t"
     if layer.get("batchnorm", False):
         bn = out + "_batchnorm"
         mean, var = (0.1 * rng.standard_normal(out_dim)).astype(np.float32), rng.uniform(0.05, 0.2, out_dim).astype(np.float32)
