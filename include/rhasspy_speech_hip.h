@@ -117,8 +117,16 @@ const char *rs_last_error(void);
  * Append(o_t, h_t); c_t a BackpropTruncationComponent (or ClipGradientComponent: scale 1) over Sum(c1_t, c2_t); r_t one over the
  * dim-range [0, R) of the affine W_rp.m over m_t, or over m_t; the two <Scale>s are honoured separately; the same delays and
  * limits; only rp_t and m_t may be read from outside the block.  Any other cycle -- an incomplete or differently wired cell of
- * that kind, lstmb-layer, a positive delay, two delays in one block, a block that reads another block's state at a future time --
- * is refused with the node and the reason.  A
+ * that kind, a positive delay, two delays in one block, a block that reads another block's state at a future time --
+ * is refused with the node and the reason.  A cycle around an LstmNonlinearityComponent may also be what lstmb-layer emits, the
+ * cell behind a bottleneck: the LinearComponents W_all_a (bottleneck rows) over Append(x, IfDefined(Offset([Scale(s,)] m_trunc, -d)))
+ * and W_all_b (4 x cell dim rows) over it, the ScaleAndOffsetComponent W_all_b_so of 4 x cell dim with vectors of that length
+ * (applied as the component does: the scales through EnsureNonzero, multiply, then add), the nonlinearity over Append(W_all_b_so,
+ * IfDefined(Offset(c_trunc, -d))) without a dropout mask, one BackpropTruncationComponent over its whole output whose dim-ranges
+ * c_trunc / m_trunc are the state; Scale(s, ...) is accepted on this block's recurrent input only; only m, the nonlinearity's second
+ * cell-dim columns, may be read from outside.  Limits: cell dim <= 2048, bottleneck dim <= 2048, 64 * (cell dim + bottleneck dim + 8)
+ * bytes <= 144 KiB of LDS (dims rounded up to 16).  Outside a cycle a ScaleAndOffsetComponent is an ordinary scale / offset layer,
+ * its block form (<Dim> a multiple of the vectors' length) included.  A
  * cycle may instead be what fast-opgru-layer / fast-norm-opgru-layer emit (TDNN-OPGRU recipes, the output-gate projected GRU): two
  * affines W_z, W_o of cell-dim rows over Append(x, IfDefined(Offset(s_t, -d))), each behind a SigmoidComponent [and one shared
  * DropoutComponent, a copy in test mode], an affine W_hpart over the same x, an OutputGruNonlinearityComponent over Append(z_t,
@@ -163,7 +171,11 @@ void rs_model_free(rs_model *model);
  * scale_c and scale_r (the two truncation components'), dropout=0|1 (the shared DropoutComponent), the kernel instantiation, chains
  * per workgroup, LDS bytes, the feed-forward (w_x) and recurrent (w_r) columns of each of the four affines, cell and projection
  * tiles, the grid rule; its `op: lstmp` line follows the `op: gemm <c_t>.x` of the four affines' stacked feed-forward columns
- * (4 x cell dim rows, gate order i, f, c, o).  Then one `gru:` line per GRU block: name, input dim, cell /
+ * (4 x cell dim rows, gate order i, f, c, o).  Then one `lstmb:` line per block behind a bottleneck (lstmb-layer), named after its
+ * nonlinearity's node: input dim, cell and bottleneck dims, delay, the truncation component's scale, self_scale (the Scale() on the
+ * recurrent input), the kernel instantiation, chains per workgroup, LDS bytes, the split of W_all_a's columns (w_a), cell and
+ * bottleneck tiles, the grid rule; its `op: lstmb` line follows the `op: gemm <W_all_a>.x` of W_all_a's feed-forward columns
+ * (bottleneck rows, no bias).  Then one `gru:` line per GRU block: name, input dim, cell /
  * recurrent / non-recurrent dims, delay, the truncation component's scale, norm=0|1 (a NormalizeComponent in the recurrence),
  * dropout=0|1, the kernel instantiation, chains per workgroup, LDS bytes, the split of W_z's and W_o's columns, cell and output tiles,
  * the grid rule; its `op: gru` line follows the `op: gemm` of the stacked feed-forward columns (3 x cell dim rows).  Then one `pgru:` line per
@@ -467,7 +479,8 @@ int rs_bind_host_thread(int32_t device_id);
  * (n x D_iv: one row offline, one row per nnet chunk for streams), 2 = log-likelihoods (T x P); 3 + k = the output of the
  * model's k-th convolution (T x heights * filters, ReLU and BatchNorm applied; batch calls only); 64 + k = the output rows of the
  * model's k-th recurrent block of any kind, in network order, what the layers above it read (an LSTM block of either form: T x (recurrent +
- * non-recurrent) dim: rp / rp_t, before any BatchNorm; or T x cell dim: m / m_t, without a projection; an OPGRU or PGRU block: T x (recurrent +
+ * non-recurrent) dim: rp / rp_t, before any BatchNorm; or T x cell dim: m / m_t, without a projection; an lstmb-layer block: T x cell
+ * dim: m, before m_batchnorm; an OPGRU or PGRU block: T x (recurrent +
  * non-recurrent) dim: W_y's rows, before any BatchNorm; a fast-gru-layer block: T x cell dim: c; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
  * hold anything); 128 + k = the output rows of the model's k-th RestrictedAttentionComponent, in network order (T x heads *
  * (value-dim [+ num-left-inputs + 1 + num-right-inputs with output-context]): per head the weighted values, then the softmax

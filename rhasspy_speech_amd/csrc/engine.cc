@@ -279,6 +279,9 @@ Model::Model(const std::string &final_mdl, const std::string &hclg, const std::s
   lstm_plans_.assign(am_.nnet.ops.size(), LstmLaunchPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++)
     if (am_.nnet.ops[i].kind == LayerOp::kLstm || am_.nnet.ops[i].kind == LayerOp::kLstmp) lstm_plans_[i] = PlanLstm(am_.nnet.ops[i].lstm, am_.nnet.ops[i].name);
+  lstmb_plans_.assign(am_.nnet.ops.size(), LstmbLaunchPlan());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++)
+    if (am_.nnet.ops[i].kind == LayerOp::kLstmb) lstmb_plans_[i] = PlanLstmb(am_.nnet.ops[i].lstm, am_.nnet.ops[i].name);
   gru_plans_.assign(am_.nnet.ops.size(), GruLaunchPlan());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++)
     if (am_.nnet.ops[i].kind == LayerOp::kGru) gru_plans_[i] = PlanGru(am_.nnet.ops[i].gru, am_.nnet.ops[i].name);
@@ -429,7 +432,7 @@ template <typename T> T *Model::Upload(const std::vector<T> &v) { return static_
 
 void Model::BuildGemmPlan(const LayerOp &op, GemmPlan *plan) {
   plan->op = &op;
-  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm || op.kind == LayerOp::kLstmp || op.kind == LayerOp::kGru || op.kind == LayerOp::kPgru || op.kind == LayerOp::kAttention) {      // (their own operands: ToDevice; here the bias and the fused stages)
+  if (op.kind == LayerOp::kConv || op.kind == LayerOp::kGather || op.kind == LayerOp::kLstm || op.kind == LayerOp::kLstmp || op.kind == LayerOp::kLstmb || op.kind == LayerOp::kGru || op.kind == LayerOp::kPgru || op.kind == LayerOp::kAttention) {      // (their own operands: ToDevice; here the bias and the fused stages)
     plan->d_bias = op.bias.empty() ? nullptr : Upload(op.bias);
     plan->d_stage.clear();
     for (auto &st : op.stages) {
@@ -750,6 +753,18 @@ void Model::ToDevice() {
     lstm_dev_[i].b_rp = Upload(op.lstm.b_rp);
     lstm_dev_[i].params = Upload(op.lstm.params.d);
   }
+  lstmb_dev_.assign(am_.nnet.ops.size(), LstmbOperands());
+  for (size_t i = 0; i < am_.nnet.ops.size(); i++) {
+    const LayerOp &op = am_.nnet.ops[i];
+    if (op.kind != LayerOp::kLstmb) continue;
+    std::vector<float> wam_t, wb_t;
+    LstmbWeightImages(op.lstm, lstmb_plans_[i], &wam_t, &wb_t);
+    lstmb_dev_[i].wam_t = Upload(wam_t);
+    lstmb_dev_[i].wb_t = Upload(wb_t);
+    lstmb_dev_[i].so_scale = Upload(op.lstm.so_scale);
+    lstmb_dev_[i].so_offset = Upload(op.lstm.so_offset);
+    lstmb_dev_[i].params = Upload(op.lstm.params.d);
+  }
   gru_dev_.assign(am_.nnet.ops.size(), GruOperands());
   for (size_t i = 0; i < am_.nnet.ops.size(); i++) {
     const LayerOp &op = am_.nnet.ops[i];
@@ -953,7 +968,7 @@ std::string Model::Describe() const {
      << " left_context=" << n.left_context << " right_context=" << n.right_context << " priors=" << n.priors.size()
      << " components=" << n.components.size() << " ops=" << n.ops.size() << "\n";
   for (auto &op : n.ops) {
-    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm", "gru", "attention", "pgru", "lstmp"};
+    static const char *const kinds[] = {"gemm", "eltwise", "conv", "gather", "lstm", "gru", "attention", "pgru", "lstmp", "lstmb"};
     os << "op: " << kinds[op.kind] << " " << op.name << " out_dim=" << op.out_dim;
     if (op.kind == LayerOp::kGemm) {
       os << " k=" << op.W.cols << " segs=";
@@ -972,6 +987,8 @@ std::string Model::Describe() const {
     if (n.ops[i].kind == LayerOp::kLstm) os << "lstm: " << DescribeLstm(n.ops[i].name, n.ops[i].lstm, lstm_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)      // (... in its composed form: lstmp-layer / lstm-layer)
     if (n.ops[i].kind == LayerOp::kLstmp) os << "lstmp: " << DescribeLstmp(n.ops[i].name, n.ops[i].lstm, lstm_plans_[i]) << "\n";
+  for (size_t i = 0; i < n.ops.size(); i++)      // (... behind a bottleneck: lstmb-layer)
+    if (n.ops[i].kind == LayerOp::kLstmb) os << "lstmb: " << DescribeLstmb(n.ops[i].name, n.ops[i].lstm, lstmb_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)
     if (n.ops[i].kind == LayerOp::kGru) os << "gru: " << DescribeGru(n.ops[i].name, n.ops[i].gru, gru_plans_[i]) << "\n";
   for (size_t i = 0; i < n.ops.size(); i++)
@@ -1438,6 +1455,36 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       if (images_on)
         for (int b : outs)
           if (b >= 0 && (*imgs)[b].base)
+            LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
+      continue;
+    } else if (op.kind == LayerOp::kLstmb) {
+      if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
+      const LstmBlock &k = op.lstm;
+      const BufferInfo &ob = nn.bufs[op.out_buf];
+      const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride);
+      const int outs[2] = {k.cm_buf, k.st_buf};
+      // (as for a fast block: the rows of a stream advance the walk does not reach hold zeros, not what the arena held)
+      if (!rm)
+        for (int b : outs) RS_HIP(hipMemsetAsync(bufp[b], 0, sizeof(float) * (size_t)rows * buf_ld[b], s));
+      LstmbDev d;
+      std::memset(&d, 0, sizeof(d));
+      d.pre = bufp[k.pre_buf]; d.ld_pre = buf_ld[k.pre_buf];
+      d.cm = bufp[k.cm_buf]; d.ld_cm = buf_ld[k.cm_buf];
+      d.st = bufp[k.st_buf]; d.ld_st = buf_ld[k.st_buf];
+      d.wam_t = lstmb_dev_[i].wam_t; d.wb_t = lstmb_dev_[i].wb_t;
+      d.so_scale = lstmb_dev_[i].so_scale; d.so_offset = lstmb_dev_[i].so_offset; d.params = lstmb_dev_[i].params;
+      d.cell = k.cell; d.bottleneck = k.bottleneck;
+      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale; d.self_scale = k.self_scale;
+      d.n_utts = lstm->n_utts; d.L = L_; d.lext = ob.lext; d.rext = ob.rext;
+      d.num_frames = lstm->num_frames; d.row_base = lstm->row_base;
+      d.t0 = lstm->t0; d.slot = lstm->slot; d.lext_cont = k.need_lext;
+      d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
+      if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
+      d.plan = lstmb_plans_[i];
+      LaunchLstmb(d, s);
+      if (images_on)
+        for (int b : outs)
+          if ((*imgs)[b].base)
             LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
       continue;
     } else if (op.kind == LayerOp::kGru) {
@@ -2207,7 +2254,7 @@ void Model::BatchIntermediates(const BatchCall &b, const float *ll, int ll_ld, U
     ur.lstm_out.clear();
     ur.lstm_dim.clear();
     for (auto &op : nn.ops) {
-      if (op.kind != LayerOp::kLstm && op.kind != LayerOp::kLstmp && op.kind != LayerOp::kGru && op.kind != LayerOp::kPgru) continue;
+      if (op.kind != LayerOp::kLstm && op.kind != LayerOp::kLstmp && op.kind != LayerOp::kLstmb && op.kind != LayerOp::kGru && op.kind != LayerOp::kPgru) continue;
       const LstmBlock &k = op.lstm;
       const bool gru = op.kind == LayerOp::kGru, pgru = op.kind == LayerOp::kPgru;
       // (a block around a GruNonlinearityComponent: W_y's rows, without a projection the c columns of [h | c])

@@ -107,6 +107,9 @@ struct ConvOperands {     // one LayerOp of kind kConv (W in the kernel's order,
 struct LstmOperands {     // one LayerOp of kind kLstm or kLstmp: LstmWeightImages' two matrices, the projection's bias, the nonlinearity's <Params>
   float *wr_t = nullptr, *wrp_t = nullptr, *b_rp = nullptr, *params = nullptr;
 };
+struct LstmbOperands {    // one LayerOp of kind kLstmb: LstmbWeightImages' two matrices, the scale / offset vectors, the nonlinearity's <Params>
+  float *wam_t = nullptr, *wb_t = nullptr, *so_scale = nullptr, *so_offset = nullptr, *params = nullptr;
+};
 struct GruOperands {      // one LayerOp of kind kGru: GruWeightImages' two matrices, W_y's bias, the nonlinearity's <w_h>
   float *ws_t = nullptr, *wy_t = nullptr, *b_y = nullptr, *w_h = nullptr;
 };
@@ -394,6 +397,8 @@ class Model {
   std::vector<ConvOperands> conv_dev_;       // indexed like am_.nnet.ops: the convolutions' and gathers' device operands
   std::vector<LstmLaunchPlan> lstm_plans_;   // indexed like am_.nnet.ops: what the planner chose at load for the recurrent blocks
   std::vector<LstmOperands> lstm_dev_;       // indexed like am_.nnet.ops: their device operands
+  std::vector<LstmbLaunchPlan> lstmb_plans_; // ... and for the blocks behind a bottleneck (lstmb-layer)
+  std::vector<LstmbOperands> lstmb_dev_;
   std::vector<GruLaunchPlan> gru_plans_;     // the same for the GRU blocks
   std::vector<AttentionLaunchPlan> attention_plans_;   // the same for the attention ops
   std::vector<GruOperands> gru_dev_;

@@ -12,6 +12,7 @@
 #include "gemm_launch.h"
 #include "gru_plan.h"
 #include "lstm_plan.h"
+#include "lstmb_plan.h"
 #include "pgru_plan.h"
 #include "search_plan.h"
 
@@ -182,6 +183,8 @@ void LaunchAttention(const AttentionDev &d, int rows, hipStream_t s);
 void LaunchLstm(const LstmDev &d, hipStream_t s);
 // The same walk of a block in its composed form, lstmp-layer / lstm-layer (nnet_lstmp.hip; the same descriptor and plan)
 void LaunchLstmp(const LstmDev &d, hipStream_t s);
+// ... of a block behind a bottleneck, lstmb-layer (nnet_lstmb.hip; lstmb_plan.h)
+void LaunchLstmb(const LstmbDev &d, hipStream_t s);
 // ... of a GRU block (nnet_gru.hip; gru_plan.h)
 void LaunchGru(const GruDev &d, hipStream_t s);
 // ... of a block around a GruNonlinearityComponent (nnet_pgru.hip; pgru_plan.h)

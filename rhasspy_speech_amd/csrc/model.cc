@@ -1064,6 +1064,20 @@ float TruncationScale(const Component &c) {
   return it == c.f.end() || it->second.empty() ? 1.0f : (float)it->second[0];
 }
 
+// A ScaleAndOffsetComponent's two vectors as PropagateInternal applies them (nnet-simple-component.cc:2474-2485): the scales through
+// cu::EnsureNonzero with the component's epsilon 1e-4 (|s| < 1e-4 becomes +-1e-4 with the sign of s, +1e-4 at 0), the offsets as read
+void ScaleAndOffsetVectors(const Component &c, const std::string &name, std::vector<float> *scales, std::vector<float> *offsets) {
+  auto sit = c.v.find("<Scales>"), oit = c.v.find("<Offsets>");
+  if (!c.i.count("<Dim>") || sit == c.v.end() || oit == c.v.end() || sit->second.empty() || sit->second.size() != oit->second.size() ||
+      c.Int("<Dim>") <= 0 || c.Int("<Dim>") % (int)sit->second.size() != 0)
+    Fail("nnet3: ScaleAndOffsetComponent '" + name + "' needs a <Dim> that is a multiple of the length of its <Scales> and <Offsets> vectors");
+  const float eps = 1.0e-4f;
+  *scales = sit->second;
+  for (float &x : *scales)
+    if (!(x <= -eps || x >= eps)) x = x >= 0.0f ? eps : -eps;
+  *offsets = oit->second;
+}
+
 // Elementwise component -> stages (empty = identity).  false if the type is not elementwise.
 bool EltStagesFor(const Component &c, const std::string &name, std::vector<EltStage> *st) {
   st->clear();
@@ -1136,6 +1150,19 @@ bool EltStagesFor(const Component &c, const std::string &name, std::vector<EltSt
     st->push_back(s);
     return true;
   }
+  if (c.type == "ScaleAndOffsetComponent") {
+    std::vector<float> sc, of;
+    ScaleAndOffsetVectors(c, name, &sc, &of);
+    // the block form: <Dim> is a multiple of the vectors' length and they repeat along the row
+    const int dim = c.Int("<Dim>"), block = (int)sc.size();
+    EltStage s;
+    s.kind = EltStage::kScaleOffset;
+    s.scale.resize(dim);
+    s.offset.resize(dim);
+    for (int i = 0; i < dim; i++) { s.scale[i] = sc[i % block]; s.offset[i] = of[i % block]; }
+    st->push_back(s);
+    return true;
+  }
   return false;
 }
 
@@ -1160,6 +1187,11 @@ struct BlockNodes {
   // projection rp = rp_t and r = r_t_preclip; cdrop: the shared DropoutComponent behind i, f and o is there
   bool composed = false, cdrop = false;
   int ga[4] = {-1, -1, -1, -1}, pe[3] = {-1, -1, -1};
+  // the cell behind a bottleneck (xconfig/lstm.py: XconfigLstmbLayer): wa = W_all_a (where the block is placed), wb = W_all_b, so =
+  // W_all_b_so, nl, tr = cm_trunc, sc / sr = c_trunc / m_trunc; self_scale: the Scale() on the recurrent input
+  bool lstmb = false;
+  int wb = -1, so = -1;
+  float self_scale = 1.0f;
   std::vector<int> members;                          // the cycle's nodes (a GRU block: and hpart_t)
   std::vector<DescPart> x_parts;                     // W_all's input without its recurrent part
 };
@@ -1250,8 +1282,10 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
     // (a cycle without any of the three nonlinearities has to be the same cell spelled out: lstmp-layer / lstm-layer, below)
     const bool composed_cycle = b.nl < 0 && !gru_cycle;
     // a recurrent part: one optional term, Offset(x, -d) with 1 <= d <= kLstmMaxDelay
-    auto recurrent_part = [&](int at, const DescPart &p, int *node) {
-      if (p.terms.size() != 1 || p.terms[0].const_t || p.terms[0].scale != 1.0f) refuse(at, "its recurrent input is not IfDefined(Offset(node, -delay))");
+    // (self_scale: where given, the term may be Offset(Scale(s, node), -d) and s is returned there -- an lstmb-layer block only)
+    auto recurrent_part = [&](int at, const DescPart &p, int *node, float *self_scale = nullptr) {
+      if (p.terms.size() != 1 || p.terms[0].const_t || (p.terms[0].scale != 1.0f && !self_scale)) refuse(at, "its recurrent input is not IfDefined(Offset(node, -delay))");
+      if (self_scale) *self_scale = p.terms[0].scale;
       const DescTerm &t = p.terms[0];
       if (!t.optional) refuse(at, "its recurrent input " + nodes[t.node].name + " is not inside IfDefined()");
       if (t.offset > 0) refuse(at, "a positive delay, Offset(" + nodes[t.node].name + ", " + std::to_string(t.offset) + "): a recurrence towards the future is not supported");
@@ -1279,7 +1313,7 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
       // ---- the composed LSTM(P) cell (xconfig/lstm.py: XconfigLstmpLayer :440-565, XconfigLstmLayer :160-255)
       auto no = [&](int n, const std::string &why) {
         refuse(n, "the cycle has no LstmNonlinearityComponent and is no complete lstmp-layer / lstm-layer block (four affines, three peepholes, Sigmoid / Tanh / "
-                  "ElementwiseProduct components, two truncation components) either; lstmb-layer and the non-fast GRU layers are not supported: " + why);
+                  "ElementwiseProduct components, two truncation components) either; the non-fast GRU layers are not supported: " + why);
       };
       auto is_trunc = [&](int n) { const std::string t = comp_type(n); return t == "BackpropTruncationComponent" || t == "ClipGradientComponent"; };
       auto is_peephole = [&](int n) { const std::string t = comp_type(n); return t == "NaturalGradientPerElementScaleComponent" || t == "PerElementScaleComponent"; };
@@ -1698,6 +1732,67 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
       const bool continuous = dm.b.count("<Continuous>") != 0;
       if (!continuous && dm.f.count("<DropoutProportion>") && dm.f.at("<DropoutProportion>")[0] != 0.0)
         refuse(b.dm, "a non-continuous dropout mask with dropout-proportion " + std::to_string(dm.f.at("<DropoutProportion>")[0]) + " is not all ones in test mode");
+    }
+    if (in_scc(b.wa) && comp_type(b.wa) == "ScaleAndOffsetComponent") {
+      // ---- the cell behind a bottleneck (xconfig/lstm.py: XconfigLstmbLayer :860-950): the nonlinearity's first input is W_all_b_so, a
+      // ScaleAndOffsetComponent over the LinearComponent W_all_b over the LinearComponent W_all_a, which reads
+      // Append(x ..., IfDefined(Offset([Scale(s,)] m_trunc, -d)))
+      b.lstmb = true;
+      b.so = b.wa;
+      if (b.dm >= 0) refuse(b.nl, "an lstmb-layer block's nonlinearity takes no third input, but this one reads the dropout mask " + nodes[b.dm].name);
+      const Component &so = net.components[nodes[b.so].component];
+      {
+        auto sit = so.v.find("<Scales>"), oit = so.v.find("<Offsets>");
+        if (nodes[b.so].dim != 4 * C || sit == so.v.end() || oit == so.v.end() || (int)sit->second.size() != 4 * C || (int)oit->second.size() != 4 * C)
+          refuse(b.so, "the ScaleAndOffsetComponent in front of the nonlinearity does not have <Scales> and <Offsets> vectors of 4 x cell-dim = " + std::to_string(4 * C) +
+                           " elements (its block form is not supported inside a recurrent block)");
+      }
+      b.wb = only_input(b.so);
+      if (b.wb < 0 || !in_scc(b.wb) || comp_type(b.wb) != "LinearComponent") refuse(b.so, "its input is not a LinearComponent node of the cycle (W_all_b)");
+      b.wa = only_input(b.wb);
+      if (b.wa < 0 || !in_scc(b.wa) || comp_type(b.wa) != "LinearComponent") refuse(b.wb, "its input is not a LinearComponent node of the cycle (W_all_a)");
+      const NnetNode &wa = nodes[b.wa];
+      if (wa.input.parts.size() < 2) refuse(b.wa, "its input is not Append(x, IfDefined(Offset(m_trunc, -delay)))");
+      const int d2 = recurrent_part(b.wa, wa.input.parts.back(), &b.sr, &b.self_scale);
+      if (d2 != b.delay) refuse(b.wa, "two different delays in one block, " + std::to_string(d2) + " and " + std::to_string(b.delay));
+      b.rec_dim = wa.input.parts.back().dim;
+      b.x_parts.assign(wa.input.parts.begin(), wa.input.parts.end() - 1);
+      for (auto &p : b.x_parts) for (auto &t : p.terms) if (in_scc(t.node)) refuse(b.wa, "its feed-forward input reads " + nodes[t.node].name + ", a node of the cycle");
+      // the state: the two column ranges of one BackpropTruncationComponent node over the nonlinearity
+      if (nodes[b.sc].kind != NnetNode::kDimRange) refuse(b.sc, "the cell state is not a dim-range of a BackpropTruncationComponent node");
+      b.tr = nodes[b.sc].range_node;
+      if (comp_type(b.tr) != "BackpropTruncationComponent") refuse(b.tr, "the state does not come through a BackpropTruncationComponent");
+      if (only_input(b.tr) != b.nl) refuse(b.tr, "its input is not the nonlinearity: an lstmb-layer block has no projection");
+      if (b.rec_dim != C || !range_of(b.sc, b.tr, 0, C) || !range_of(b.sr, b.tr, C, C) || nodes[b.tr].dim != 2 * C)
+        refuse(b.tr, "c_trunc and m_trunc are not the two cell-dim column ranges of one BackpropTruncationComponent node");
+      b.members = {b.wa, b.wb, b.so, b.nl, b.tr, b.sc, b.sr};
+      std::sort(b.members.begin(), b.members.end());
+      if (std::adjacent_find(b.members.begin(), b.members.end()) != b.members.end()) refuse(b.nl, "a node has two roles in the block");
+      for (int n : scc) if (!std::binary_search(b.members.begin(), b.members.end(), n)) refuse(n, "the node is part of the cycle but not of such a block");
+      for (int n : b.members) if (!in_scc(n)) refuse(n, "the node is not part of the cycle");
+      auto params_of = [&](int n) -> const MatF * { const Component &c = net.components[nodes[n].component]; auto it = c.m.find("<Params>"); return it == c.m.end() ? nullptr : &it->second; };
+      const MatF *Wa = params_of(b.wa), *Wb = params_of(b.wb);
+      int x_dim = 0;
+      for (auto &p : b.x_parts) x_dim += p.dim;
+      if (!Wa || Wa->rows <= 0 || Wa->cols != x_dim + C)
+        refuse(b.wa, "W_all_a is " + std::to_string(Wa ? Wa->rows : 0) + " x " + std::to_string(Wa ? Wa->cols : 0) + ", the block needs the feed-forward input's " + std::to_string(x_dim) +
+                         " + the cell's " + std::to_string(C) + " columns");
+      if (!Wb || Wb->rows != 4 * C || Wb->cols != Wa->rows)
+        refuse(b.wb, "W_all_b is " + std::to_string(Wb ? Wb->rows : 0) + " x " + std::to_string(Wb ? Wb->cols : 0) + ", the block needs 4 x cell-dim rows and the bottleneck's " +
+                         std::to_string(Wa->rows) + " columns");
+      if (nl.input.dim != 5 * C) refuse(b.nl, "its input dim is not 5 x cell-dim");
+      // only m, the second cell-dim columns of the nonlinearity, may be read from outside the block
+      for (int n = 0; n < N; n++) {
+        if (std::binary_search(b.members.begin(), b.members.end(), n) || index[n] < 0) continue;
+        std::vector<int> d;
+        deps(n, &d);
+        for (int m : d)
+          if (std::binary_search(b.members.begin(), b.members.end(), m) && !(m == b.nl && range_of(n, b.nl, C, C)))
+            refuse(m, "the node is read from outside the block, by " + nodes[n].name);
+      }
+      for (int n : b.members) (*block_of)[n] = (int)blocks->size();
+      blocks->push_back(std::move(b));
+      continue;
     }
     // W_all: Append(x ..., IfDefined(Offset(r_trunc, -d)))
     const std::string wt = comp_type(b.wa);
@@ -2168,6 +2263,49 @@ void Nnet::Compile() {
         ops.push_back(w);
         continue;
       }
+      if (b.lstmb) {
+        // ---- the cell behind a bottleneck: the x-columns of W_all_a as a layer GEMM of bottleneck rows (a LinearComponent: no
+        // bias), its m-columns, W_all_b and the scale / offset vectors as the walk's operands
+        const MatF &Wa = components[nodes[b.wa].component].m.at("<Params>"), &Wb = components[nodes[b.wb].component].m.at("<Params>");
+        const int C = b.cell, B = Wa.rows, in_dim = Wa.cols - C, l = lext[b.wa], r = rext[b.wa];
+        LayerOp g;
+        g.kind = LayerOp::kGemm;
+        g.name = nodes[b.wa].name + ".x";
+        g.out_dim = B;
+        g.W.Resize(B, in_dim);
+        LayerOp w;
+        w.kind = LayerOp::kLstmb;
+        w.name = nodes[b.nl].name;
+        w.out_dim = 2 * C;
+        LstmBlock &k = w.lstm;
+        k.W_r.Resize(B, C);
+        for (int row = 0; row < B; row++) {
+          for (int c = 0; c < in_dim; c++) g.W(row, c) = Wa(row, c);
+          for (int c = 0; c < C; c++) k.W_r(row, c) = Wa(row, in_dim + c);
+        }
+        const int wcol = add_gemm_segs(&g, b.x_parts, b.wa, {0});
+        if (wcol != in_dim) Fail("nnet3: internal error, the feed-forward input of recurrent block " + w.name + " does not cover its weights' columns");
+        g.out_buf = new_buf(B, l, r);
+        ops.push_back(g);
+        k.W_b = Wb;
+        ScaleAndOffsetVectors(components[nodes[b.so].component], component_names[nodes[b.so].component], &k.so_scale, &k.so_offset);
+        k.in_dim = in_dim; k.cell = C; k.bottleneck = B;
+        k.delay = b.delay;
+        k.scale = TruncationScale(components[nodes[b.tr].component]);
+        k.self_scale = b.self_scale;
+        k.params = components[nodes[b.nl].component].m.at("<Params>");
+        k.need_lext = b.need_lext;
+        k.pre_buf = g.out_buf;
+        k.cm_buf = new_buf(2 * C, l, r);           // [c | m]
+        k.st_buf = new_buf(2 * C, l, r);           // [sc | sm]
+        node_buf[b.nl] = k.cm_buf;
+        node_buf[b.tr] = node_buf[b.sc] = node_buf[b.sr] = k.st_buf;
+        node_col[b.sr] = C;
+        w.out_buf = k.cm_buf;
+        w.terms.push_back({k.pre_buf, 0, 0, 1.0f});
+        ops.push_back(w);
+        continue;
+      }
       const Component &wa = components[nodes[b.wa].component];
       const MatF &W = wa.m.at("<LinearParams>");
       const int C = b.cell, rec = b.rec_dim, in_dim = W.cols - rec, l = lext[b.wa], r = rext[b.wa];
@@ -2440,7 +2578,7 @@ void Nnet::SetSubsampling(int factor) {
   // a layer X that feeds a Sum dense while its own input W stayed strided: X's GEMM ran over all rows and read rows of W nobody
   // had written in that call.)
   for (auto it = ops.rbegin(); it != ops.rend(); ++it) {
-    if (it->kind == LayerOp::kLstm || it->kind == LayerOp::kLstmp) {
+    if (it->kind == LayerOp::kLstm || it->kind == LayerOp::kLstmp || it->kind == LayerOp::kLstmb) {
       // a block's buffers hold the same rows: every residue one of them is read at, and every residue the chains of those rows
       // pass through (delay 3 under factor 3 stays in its class; delay 2 visits all three)
       const LstmBlock &k = it->lstm;

@@ -215,6 +215,13 @@ struct LstmBlock {
   bool composed = false;
   float scale_r = 1.0f;
   bool dropout = false;
+  // the bottleneck form (LayerOp::kLstmb, below): bottleneck > 0, rec = nonrec = 0; W_r is W_all_a's recurrent columns
+  // (bottleneck x cell), W_b is W_all_b (4 cell x bottleneck), so_scale / so_offset W_all_b_so's vectors (4 cell, EnsureNonzero
+  // applied), self_scale the Scale() on the recurrent input; pre_buf is bottleneck wide, st_buf holds [sc | sm]
+  int bottleneck = 0;
+  float self_scale = 1.0f;
+  MatF W_b;
+  std::vector<float> so_scale, so_offset;
   MatF W_r;                       // 4 cell x RecDim(): W_all's recurrent columns
   MatF params;                    // 3 x cell: w_ic, w_fc, w_oc
   MatF W_rp;                      // (rec + nonrec) x cell
@@ -238,6 +245,14 @@ constexpr int kLstmMaxDelay = 8;
 //   i = Sigmoid((pre_i + W_ri sr[t - d]) + w_ic . sc[t - d]),  f likewise,  g = Tanh(pre_g + W_rg sr[t - d])
 //   sc[t] = scale (f . sc[t - d] + i . g);  o = Sigmoid((pre_o + W_ro sr[t - d]) + w_oc . sc[t]);  m = o . Tanh(sc[t])
 //   rp = W_rp m + b_rp,  sr[t] = scale_r rp[0:rec]     or, without a projection,     sr[t] = scale_r m
+// The cell with its affine factorised through a bottleneck: what nnet3's lstmb-layer emits (xconfig/lstm.py: XconfigLstmbLayer),
+// recognised as a unit and held in an LstmBlock with bottleneck > 0.  Two LinearComponents (no bias) and a ScaleAndOffsetComponent in
+// front of the LstmNonlinearityComponent, one BackpropTruncationComponent over [c | m], Scale(self_scale, m_trunc) on the recurrent
+// input.  With sc, sm the state rows, per row t, every line a rounding of its own:
+//   b = pre_b[t] + W_a,m sm[t - d]          pre_b = W_a,x x, a kGemm op over all rows
+//   g = W_b b;  g' = g * so_scale;  g' = g' + so_offset                     ScaleAndOffsetComponent::PropagateInternal
+//   (c, m) = LstmNonlinearity(g', sc[t - d]; params)
+//   sc[t] = scale c;  sm[t] = self_scale (scale m)                          the second product only where self_scale is not 1
 
 // A recurrent block of the output-gate projected GRU: what nnet3's fast-opgru-layer / fast-norm-opgru-layer emit (xconfig/gru.py),
 // recognised as a unit (Nnet::Compile).  With s the recurrent state (scaled), c the cell state (read back unscaled), zero where the
@@ -313,8 +328,9 @@ struct LayerOp {
   // kLstm: the serial part of a recurrent block (lstm); out_buf = lstm.cm_buf.  kGru: the same of a GRU block (gru); out_buf = gru.hc_buf
   // kPgru: the same of a block around a GruNonlinearityComponent (pgru); out_buf = pgru.hc_buf
   // kLstmp: the same of an LSTM block in its composed form (lstm, with lstm.composed); out_buf = lstm.cm_buf
+  // kLstmb: the same of an LSTM block in its bottleneck form (lstm, with lstm.bottleneck > 0); out_buf = lstm.cm_buf
   // kAttention: out = attention(terms[0]), no fused stage (the result matrix of the op is the component's output): one term, the source; the rows it reads are terms[0].offset + attention.TimeOffset(o)
-  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm, kGru, kAttention, kPgru, kLstmp } kind = kGemm;
+  enum Kind { kGemm, kEltwise, kConv, kGather, kLstm, kGru, kAttention, kPgru, kLstmp, kLstmb } kind = kGemm;
   std::string name;
   int out_buf = -1, out_dim = 0;
   // kGemm
@@ -332,7 +348,7 @@ struct LayerOp {
   std::vector<EltStage> stages; // applied after the gemm/sum, in order
   ConvGeom conv;                           // kConv
   std::vector<int> gather_part, gather_col;   // kGather, per output column: the term and the column inside it
-  LstmBlock lstm;                             // kLstm, kLstmp
+  LstmBlock lstm;                             // kLstm, kLstmp, kLstmb
   GruBlock gru;                               // kGru
   AttentionGeom attention;                    // kAttention
   PgruBlock pgru;                             // kPgru
@@ -354,7 +370,7 @@ struct Nnet {
   std::vector<BufferInfo> bufs;
   int input_buf = -1, output_buf = -1;
   int left_context = 0, right_context = 0;
-  bool recurrent = false;      // has at least one recurrent block (kLstm, kLstmp, kGru or kPgru op)
+  bool recurrent = false;      // has at least one recurrent block (kLstm, kLstmp, kLstmb, kGru or kPgru op)
   // What the reference's binaries do to the network before the first frame (nnet3_setup.h): the network is the one
   // CollapseModel leaves behind, and rand() has been called `setup_rand_calls` times (the dither seeds follow from that).
   long setup_rand_calls = 0;

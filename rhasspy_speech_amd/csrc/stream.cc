@@ -289,6 +289,8 @@ StreamPool *Model::Pool() {
     if (nn.ops[i].kind == LayerOp::kLstm || nn.ops[i].kind == LayerOp::kLstmp) {      // (the composed form parks [sc | sr] the same way)
       const LstmBlock &k = nn.ops[i].lstm;
       p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * (k.cell + k.RecDim()) * 4));
+    } else if (nn.ops[i].kind == LayerOp::kLstmb) {    // (the bottleneck form parks [sc | sm]: lstmb_plan.h)
+      p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * nn.ops[i].lstm.delay * 2 * nn.ops[i].lstm.cell * 4));
     } else if (nn.ops[i].kind == LayerOp::kGru) {      // (a GRU block's rows are [c | s]: gru_plan.h)
       const GruBlock &k = nn.ops[i].gru;
       p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * k.StateDim() * 4));

@@ -222,7 +222,14 @@ class ModelSpec:
     # form="composed" writes the same cell as separate components, what lstmp-layer / lstmp-batchnorm-layer (batchnorm=True) /
     # lstm-layer (rec = nonrec = 0) emit: dropout is then the shared DropoutComponent behind i, f and o, scale the <Scale> of both
     # truncation components (scale_c / scale_r set them apart), clipgrad=True makes them ClipGradientComponents as older models have.
+    # bottleneck=B (with rec = nonrec = 0 and the default form) writes what lstmb-layer emits: the LinearComponents W_all_a (B rows)
+    # and W_all_b, the ScaleAndOffsetComponent W_all_b_so, the nonlinearity, cm_trunc and m_batchnorm; self_scale is the Scale() on
+    # the recurrent input (default 1); for tests so_scales / so_offsets (tuples, repeated along the 4 cell entries) replace the drawn
+    # vectors and wb_gain (default 1) is a factor on W_all_b.
     lstm_layers: Tuple[Dict[str, object], ...] = ()
+    # ScaleAndOffsetComponents between the TDNN layers, placed like lstm_layers (behind everything else of the same `after`).  One
+    # dict per component: after, block (the length of its vectors; the layer's dim is a multiple of it, default the dim itself).
+    scale_offset_layers: Tuple[Dict[str, object], ...] = ()
     # Recurrent blocks of the output-gate projected GRU (nnet3's fast-opgru-layer / fast-norm-opgru-layer, xconfig/gru.py), placed
     # like lstm_layers (behind the LSTM blocks of the same `after`).  One dict per block: after, cell, rec, nonrec (both positive),
     # delay (default 3), scale (the BackpropTruncationComponent's <Scale>, default 1), norm (the norm variant: a NormalizeComponent
@@ -574,6 +581,15 @@ def _w_dropout_mask(w: KaldiWriter, output_dim: int, proportion: float = 0.0) ->
     w.token("</DropoutMaskComponent>")
 
 
+def _w_scale_and_offset(w: KaldiWriter, scales: np.ndarray, offsets: np.ndarray, dim: Optional[int] = None) -> None:
+    """dim: the component's width where it is a multiple of the vectors' length (its block form)."""
+    # nnet-simple-component.cc:2381-2394 (ScaleAndOffsetComponent::Write), behind WriteUpdatableCommon
+    _updatable_open(w, "ScaleAndOffsetComponent")
+    w.token("<Dim>").i32(scales.shape[0] if dim is None else dim).token("<Scales>").vector(scales).token("<Offsets>").vector(offsets)
+    w.token("<UseNaturalGradient>").boolean(True).token("<Rank>").i32(20)
+    w.token("</ScaleAndOffsetComponent>")
+
+
 def lstm_layer_dims(layer: Dict[str, object]) -> Tuple[int, int, int, int]:
     """(cell, recurrent, non-recurrent, output) dims of a ModelSpec.lstm_layers entry; without a projection the recurrent
     input and the output are the cell-wide m."""
@@ -587,10 +603,14 @@ def _lstm_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.
                 prev: str, prev_dim: int) -> Tuple[str, int]:
     """The components and nodes XconfigFastLstmpLayer / XconfigFastLstmLayer emit (xconfig/lstm.py:1120-1198, 706-753), in their
     order.  Returns the node the next layer reads and its dim."""
+    if "bottleneck" in layer and (layer.get("form", "fast") != "fast" or int(layer.get("rec", 0)) or int(layer.get("nonrec", 0))):
+        raise ValueError("lstm layer: a bottleneck (lstmb-layer) goes with the default form and without a projection")
     if layer.get("form", "fast") == "composed":
         return _lstmp_block(cfg, comps, rng, name, layer, prev, prev_dim)
     if layer.get("form", "fast") != "fast":
         raise ValueError("lstm layer: form is 'fast' (the default) or 'composed'")
+    if "bottleneck" in layer:
+        return _lstmb_block(cfg, comps, rng, name, layer, prev, prev_dim)
     C, R, P, out_dim = lstm_layer_dims(layer)
     d, scale = int(layer.get("delay", 3)), float(layer.get("scale", 1.0))
     dropout, proj = bool(layer.get("dropout", False)), R > 0
@@ -642,6 +662,51 @@ def _lstm_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.
         cfg.append(f"component-node name={bn} component={bn} input={out}")
         out = bn
     return out, out_dim
+
+
+def _lstmb_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.Generator, name: str, layer: Dict[str, object],
+                 prev: str, prev_dim: int) -> Tuple[str, int]:
+    """The components and nodes XconfigLstmbLayer emits (xconfig/lstm.py:901-949), in their order, m_batchnorm included.  Returns
+    the node the next layer reads and its dim."""
+    C, B = int(layer["cell"]), int(layer["bottleneck"])
+    if C <= 0 or B <= 0:
+        raise ValueError("lstm layer: cell and bottleneck are positive")
+    d, scale, self_scale = int(layer.get("delay", 3)), float(layer.get("scale", 1.0)), float(layer.get("self_scale", 1.0))
+
+    def randn(o, i):
+        return (rng.standard_normal((o, i)) / math.sqrt(i)).astype(np.float32)
+
+    def pinned(drawn, key):
+        if key not in layer:
+            return drawn
+        v = np.asarray(layer[key], np.float32)
+        return np.resize(v, drawn.shape[0]).astype(np.float32)
+
+    W_a = np.concatenate([randn(B, prev_dim), randn(B, C)], axis=1)
+    W_b = randn(4 * C, B) * np.float32(layer.get("wb_gain", 1.0))
+    scales = pinned(rng.uniform(0.5, 1.5, 4 * C).astype(np.float32), "so_scales")
+    offsets = pinned((rng.standard_normal(4 * C) * 0.1).astype(np.float32), "so_offsets")
+    params = (rng.standard_normal((3, C)) * 0.1).astype(np.float32)
+    mean, var = (0.1 * rng.standard_normal(C)).astype(np.float32), rng.uniform(0.05, 0.2, C).astype(np.float32)
+    comps.append((f"{name}.W_all_a", lambda w, W=W_a: _w_linear(w, W)))
+    comps.append((f"{name}.W_all_b", lambda w, W=W_b: _w_linear(w, W)))
+    comps.append((f"{name}.W_all_b_so", lambda w, s=scales, o=offsets: _w_scale_and_offset(w, s, o)))
+    comps.append((f"{name}.lstm_nonlin", lambda w, p=params: _w_lstm_nonlinearity(w, p, False)))
+    comps.append((f"{name}.cm_trunc", lambda w, n=2 * C, s=scale, i=d: _w_backprop_truncation(w, n, s, i)))
+    comps.append((f"{name}.m_batchnorm", lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+    # (a written model holds the descriptor as nnet3 normalises it: Scale() innermost, and none where the scale is 1)
+    m_trunc = f"{name}.m_trunc" if self_scale == 1.0 else f"Scale({self_scale:g}, {name}.m_trunc)"
+    cfg.append(f"component-node name={name}.W_all_a component={name}.W_all_a input=Append({prev}, IfDefined(Offset({m_trunc}, {-d})))")
+    cfg.append(f"component-node name={name}.W_all_b component={name}.W_all_b input={name}.W_all_a")
+    cfg.append(f"component-node name={name}.W_all_b_so component={name}.W_all_b_so input={name}.W_all_b")
+    cfg.append(f"component-node name={name}.lstm_nonlin component={name}.lstm_nonlin "
+               f"input=Append({name}.W_all_b_so, IfDefined(Offset({name}.c_trunc, {-d})))")
+    cfg.append(f"dim-range-node name={name}.m input-node={name}.lstm_nonlin dim-offset={C} dim={C}")
+    cfg.append(f"component-node name={name}.cm_trunc component={name}.cm_trunc input={name}.lstm_nonlin")
+    cfg.append(f"dim-range-node name={name}.c_trunc input-node={name}.cm_trunc dim-offset=0 dim={C}")
+    cfg.append(f"dim-range-node name={name}.m_trunc input-node={name}.cm_trunc dim-offset={C} dim={C}")
+    cfg.append(f"component-node name={name}.m_batchnorm component={name}.m_batchnorm input={name}.m")
+    return f"{name}.m_batchnorm", C
 
 
 def _w_ng_per_element_scale(w: KaldiWriter, scales: np.ndarray) -> None:
@@ -1097,6 +1162,15 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
         for k, layer in enumerate(spec.attention_layers, start=1):
             if int(layer["after"]) == n_layers:
                 prev, prev_dim = _attention_layer(cfg, comps, rng, f"attention{k}", layer, prev, prev_dim)
+        for k, layer in enumerate(spec.scale_offset_layers, start=1):
+            if int(layer["after"]) == n_layers:
+                block = int(layer.get("block", prev_dim))
+                if block <= 0 or prev_dim % block != 0:
+                    raise ValueError("scale-offset layer: the layer's dim is a multiple of 'block'")
+                sc, of = rng.uniform(0.5, 1.5, block).astype(np.float32), (rng.standard_normal(block) * 0.1).astype(np.float32)
+                comps.append((f"so{k}", lambda w, s=sc, o=of, n=prev_dim: _w_scale_and_offset(w, s, o, n)))
+                cfg.append(f"component-node name=so{k} component=so{k} input={prev}")
+                prev = f"so{k}"
         return prev, prev_dim
 
     for layer in spec.lstm_layers:
@@ -1108,6 +1182,9 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
     for layer in spec.pgru_layers:
         if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
             raise ValueError("pgru layer: 'after' counts the TDNN layers in front of the block, 1 .. len(layer_offsets)")
+    for layer in spec.scale_offset_layers:
+        if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
+            raise ValueError("scale-offset layer: 'after' counts the TDNN layers in front of the component, 1 .. len(layer_offsets)")
     for layer in spec.attention_layers:
         if not 1 <= int(layer["after"]) <= len(spec.layer_offsets):
             raise ValueError("attention layer: 'after' counts the TDNN layers in front of the layer, 1 .. len(layer_offsets)")
