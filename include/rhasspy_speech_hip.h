@@ -144,9 +144,19 @@ const char *rs_last_error(void);
  * truncation component over the nonlinearity's second cell-dim columns.  The same delays; cell dim <= 2048, R + P <= 4096,
  * 64 * (3 * R + cell dim + 16) bytes <= 144 KiB of LDS, without a projection 64 * (3 * cell dim + 12) bytes (dims rounded up to 16: a
  * cell dim of 752 at most).  Anything else in a cycle that holds a GruNonlinearityComponent is refused in that sentence, extended
- * by these three layers.  The non-fast
- * gru-layer / pgru-layer / opgru-layer and their norm forms (cells of Sigmoid / Tanh / ElementwiseProduct components without either
- * nonlinearity) are refused in the LSTM sentence: they are no complete lstmp-layer block.  The
+ * by these three layers.  A cycle without any nonlinearity component but with a NoOpComponent node may be the GRU cell spelled
+ * out, as the non-fast gru-layer / pgru-layer / norm-pgru-layer / opgru-layer / norm-opgru-layer emit it: y_t = NoOp(Sum(y1_t,
+ * y2_t)) with the ElementwiseProductComponents y1_t = Append(h_t, Sum(Scale(-1.0, z_t), Const(1.0, cell-dim))) and y2_t =
+ * Append(IfDefined(Offset(y_t, -d)), z_t) (gru-layer: Offset(s_t, -d)); z_t a SigmoidComponent [behind a DropoutComponent] over the
+ * affine W_z.xs_z over Append(x, IfDefined(Offset(s_t, -d))); either h_t = Tanh(W_h.UW over Append(x, h1_t)), h1_t =
+ * Append(r_t, IfDefined(Offset(s_t, -d))), r_t a gate of R rows (W_z.xs_r), or h_t = Tanh(Sum(W_h.UW over x, W_h.UW_elementwise over
+ * IfDefined(Offset(y_t, -d)))), o_t a gate of cell-dim rows (W_z.xs_o), y_o_t = Append(o_t, y_t); s_t a BackpropTruncationComponent (or
+ * ClipGradientComponent) over [a NormalizeComponent over] the dim-range [0, R) of the affine W_s.ys over y_t / y_o_t, in gru-layer
+ * over y_t itself.  The same delays and limits as the fast blocks (a gru-layer: cell dim of 752 at most); only y_t, W_s.ys' node,
+ * its dim-range and s_t may be read from outside the block; the cell is computed in that form's order, y = h (1 - z) + y[t-d] z
+ * with every product and sum a rounding of its own.  Anything else in such a cycle is refused with the node and the reason in a
+ * sentence that names the five layers; a Const() anywhere else is refused by name.  A cell of Sigmoid / Tanh / ElementwiseProduct
+ * components without a NoOpComponent node is refused in the LSTM sentence: it is no complete lstmp-layer block.  The
  * rand() calls of a recurrent compilation are not replayed, so such a model loads only with --dither=0 in its mfcc.conf / fbank.conf
  * (rs_nnet3_setup below: certain = 0).  Parses on the host only;
  * the device copy is made on first use or by rs_model_to_device().  Immutable afterwards, shareable
@@ -181,7 +191,9 @@ void rs_model_free(rs_model *model);
  * the grid rule; its `op: gru` line follows the `op: gemm` of the stacked feed-forward columns (3 x cell dim rows).  Then one `pgru:` line per
  * block around a GruNonlinearityComponent: the same fields (rec=0 nonrec=0: fast-gru-layer), the split of W_z's and W_r's columns
  * (w_zr), cell, recurrent and output tiles; its `op: pgru` line follows the `op: gemm` of the stacked feed-forward columns (2 x cell
- * dim + R rows).  Two lines are state, not structure: `layer_gemm:` and
+ * dim + R rows).  A GRU block in its composed form (opgru-layer / norm-opgru-layer; gru-layer / pgru-layer / norm-pgru-layer) prints as
+ * its family's `gru:` / `pgru:` line, named after its node y_t, with kernel=gruc16x16x4<w8> / kernel=pgruc16x16x4<w8> and ` form=composed`
+ * appended; a fast block's line is unchanged.  Two lines are state, not structure: `layer_gemm:` and
  *   arenas: device blocks=B bytes=N allocations=A; host blocks=B bytes=N allocations=A
  * summed over the model's decode contexts: the blocks and bytes their per-call arenas hold now, and the hipMalloc / hipHostMalloc
  * calls they have made since the model was loaded.  `allocations` stands still once every context has seen its largest call twice.
@@ -480,8 +492,8 @@ int rs_bind_host_thread(int32_t device_id);
  * model's k-th convolution (T x heights * filters, ReLU and BatchNorm applied; batch calls only); 64 + k = the output rows of the
  * model's k-th recurrent block of any kind, in network order, what the layers above it read (an LSTM block of either form: T x (recurrent +
  * non-recurrent) dim: rp / rp_t, before any BatchNorm; or T x cell dim: m / m_t, without a projection; an lstmb-layer block: T x cell
- * dim: m, before m_batchnorm; an OPGRU or PGRU block: T x (recurrent +
- * non-recurrent) dim: W_y's rows, before any BatchNorm; a fast-gru-layer block: T x cell dim: c; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
+ * dim: m, before m_batchnorm; an OPGRU or PGRU block of either form: T x (recurrent +
+ * non-recurrent) dim: W_y's / W_s.ys' rows, before any BatchNorm; a fast-gru-layer or gru-layer block: T x cell dim: c / y_t; batch calls only; under --frame-subsampling-factor only the rows the block was walked on
  * hold anything); 128 + k = the output rows of the model's k-th RestrictedAttentionComponent, in network order (T x heads *
  * (value-dim [+ num-left-inputs + 1 + num-right-inputs with output-context]): per head the weighted values, then the softmax
  * weights; before the ReLU / BatchNorm / Normalize nodes behind it; batch calls only; under --frame-subsampling-factor only the rows

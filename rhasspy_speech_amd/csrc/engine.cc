@@ -1512,7 +1512,8 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
       if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
       d.plan = gru_plans_[i];
-      LaunchGru(d, s);
+      if (k.composed) LaunchGruc(d, s);      // (opgru-layer / norm-opgru-layer: a kernel of its own on the same descriptor)
+      else LaunchGru(d, s);
       if (images_on)
         for (int b : outs)
           if ((*imgs)[b].base)
@@ -1544,7 +1545,8 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
       if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
       d.plan = pgru_plans_[i];
-      LaunchPgru(d, s);
+      if (k.composed) LaunchPgruc(d, s);      // (gru-layer / pgru-layer / norm-pgru-layer: likewise)
+      else LaunchPgru(d, s);
       if (images_on)
         for (int b : outs)
           if (b >= 0 && (*imgs)[b].base)

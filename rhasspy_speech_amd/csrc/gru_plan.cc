@@ -48,9 +48,10 @@ void GruWeightImages(const GruBlock &b, const GruLaunchPlan &p, std::vector<floa
 std::string DescribeGru(const std::string &name, const GruBlock &b, const GruLaunchPlan &p) {
   std::ostringstream os;
   os << name << " input=" << b.in_dim << " cell=" << b.cell << " rec=" << b.rec << " nonrec=" << b.nonrec << " delay=" << b.delay << " scale=" << b.scale
-     << " norm=" << (b.norm ? 1 : 0) << " dropout=" << (b.dropout ? 1 : 0) << " kernel=gru16x16x4<w" << kGruWaves << "> rows_per_block=" << p.rows_per_block
+     << " norm=" << (b.norm ? 1 : 0) << " dropout=" << (b.dropout ? 1 : 0) << " kernel=" << (b.composed ? "gruc" : "gru") << "16x16x4<w" << kGruWaves << "> rows_per_block=" << p.rows_per_block
      << " lds=" << p.lds_bytes << " w_zo=" << p.x_cols << "+" << p.s_cols << " cell_tiles=" << p.cell_tiles << " out_tiles=" << p.out_tiles << " grid=chains/"
      << p.rows_per_block;
+  if (b.composed) os << " form=composed";      // (opgru-layer / norm-opgru-layer: walked by nnet_gruc.hip on the same plan)
   return os.str();
 }
 

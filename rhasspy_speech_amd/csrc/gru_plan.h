@@ -18,6 +18,10 @@
 // lane + 64, ... and then over the wave's 64 lanes in a fixed tree, an order that is a function of rec alone.  Both products are
 // exact FP32 with FP32 accumulation, k in the weight's column order, four per MFMA, whatever the chain's place in the tile, the
 // workgroup or the batch -- a row's result is a function of its inputs alone.
+//
+// The composed form of the same cell (opgru-layer / norm-opgru-layer, model.h: GruBlock::composed; w_h is then the <Params> of
+// W_h.UW_elementwise) shares the descriptor, the planner, the weight images and the limits; it is walked by a kernel of its own
+// (nnet_gruc.hip: GrucKernel), the same step with c = h . (1 - z) + c[t - d] . z in that form's roundings.
 #pragma once
 #include <string>
 #include <vector>

@@ -189,6 +189,10 @@ void LaunchLstmb(const LstmbDev &d, hipStream_t s);
 void LaunchGru(const GruDev &d, hipStream_t s);
 // ... of a block around a GruNonlinearityComponent (nnet_pgru.hip; pgru_plan.h)
 void LaunchPgru(const PgruDev &d, hipStream_t s);
+// The same walks of a GRU block in its composed form (nnet_gruc.hip; the same descriptors and plans): opgru-layer / norm-opgru-layer,
+// and gru-layer / pgru-layer / norm-pgru-layer
+void LaunchGruc(const GruDev &d, hipStream_t s);
+void LaunchPgruc(const PgruDev &d, hipStream_t s);
 
 struct SumTermDev { const float *src; int ld, col0, row_off; float scale; };
 struct EltwiseDev {

@@ -819,6 +819,17 @@ struct DescParser {
       } else if (id == "IfDefined") {
         out = Parse();
         for (auto &pt : out) for (auto &tm : pt.terms) tm.optional = true;
+      } else if (id == "Const") {
+        // Const(value, dim): a term without a node; FindBlocks accepts it only as the (1 - z_t) of a composed GRU block
+        DescPart part;
+        DescTerm t;
+        t.konst = true;
+        t.scale = (float)Number();
+        Expect(',');
+        part.dim = (int)Number();
+        if (part.dim <= 0) Fail("nnet3 descriptor: Const() with a dim of " + std::to_string(part.dim) + ": " + s);
+        part.terms.push_back(t);
+        out.push_back(part);
       } else {
         Fail("nnet3 descriptor: unsupported expression '" + id + "' in: " + s);
       }
@@ -1192,7 +1203,13 @@ struct BlockNodes {
   bool lstmb = false;
   int wb = -1, so = -1;
   float self_scale = 1.0f;
-  std::vector<int> members;                          // the cycle's nodes (a GRU block: and hpart_t)
+  // a GRU cell spelled out (xconfig/gru.py: XconfigGruLayer, XconfigPgruLayer, XconfigNormPgruLayer with pgru; XconfigOpgruLayer,
+  // XconfigNormOpgruLayer with gru): the fields of the fast block, with sc = y_t (the NoOpComponent node, where the block is named),
+  // nl = -1, and the cell's own nodes: ht = h_t, y1 / y2 = y1_t / y2_t; reset-gate family: hp = h_t_pre (part of the cycle, over
+  // Append(x, h1_t)), h1 = h1_t; output-gate family: hp = h_t_pre (not part of the cycle), h2 = h_t_pre2, cd = y_o_t
+  bool gruc = false;
+  int ht = -1, y1 = -1, y2 = -1, h1 = -1, h2 = -1;
+  std::vector<int> members;                         // the cycle's nodes (a GRU block: and hpart_t)
   std::vector<DescPart> x_parts;                     // W_all's input without its recurrent part
 };
 
@@ -1207,7 +1224,7 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
     const NnetNode &nd = nodes[n];
     if (comp_type(n) == "DropoutMaskComponent") return;      // (its input is a don't-care: GetInputIndexes asks for nothing)
     if (nd.kind == NnetNode::kDimRange) out->push_back(nd.range_node);
-    for (auto &p : nd.input.parts) for (auto &t : p.terms) out->push_back(t.node);
+    for (auto &p : nd.input.parts) for (auto &t : p.terms) if (!t.konst) out->push_back(t.node);
   };
   // strongly connected components (Tarjan, iterative over an explicit stack) of what the output depends on
   std::vector<int> index(N, -1), low(N, 0), comp(N, -1), stack;
@@ -1265,7 +1282,18 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
     // (... and one that holds a GruNonlinearityComponent has to be a fast-pgru / fast-norm-pgru / fast-gru block)
     bool pgru_cycle = false;
     for (int n : scc) pgru_cycle = pgru_cycle || comp_type(n) == "GruNonlinearityComponent";
+    // (... and one that holds none of the three nonlinearities but a NoOpComponent node is a GRU cell spelled out: only gru-layer,
+    // pgru-layer, opgru-layer and their norm forms have that node, y_t; lstm.py emits none)
+    bool gruc_cycle = !gru_cycle;
+    for (int n : scc) gruc_cycle = gruc_cycle && comp_type(n) != "LstmNonlinearityComponent";
+    if (gruc_cycle) {
+      gruc_cycle = false;
+      for (int n : scc) gruc_cycle = gruc_cycle || comp_type(n) == "NoOpComponent";
+    }
     auto refuse = [&](int n, const std::string &why) {
+      if (gruc_cycle)
+        Fail("nnet3: a recurrent cycle without a nonlinearity component but with a NoOpComponent node is supported only as one gru-layer / pgru-layer / "
+             "norm-pgru-layer / opgru-layer / norm-opgru-layer block (cycle at node " + nodes[n].name + ": " + why + ")");
       if (pgru_cycle)
         Fail("nnet3: recurrent GRU networks are supported only as fast-opgru-layer / fast-norm-opgru-layer blocks and, around a GruNonlinearityComponent, as "
              "fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer blocks (cycle at node " + nodes[n].name + ": " + why + ")");
@@ -1280,11 +1308,11 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
         b.nl = n;
       }
     // (a cycle without any of the three nonlinearities has to be the same cell spelled out: lstmp-layer / lstm-layer, below)
-    const bool composed_cycle = b.nl < 0 && !gru_cycle;
+    const bool composed_cycle = b.nl < 0 && !gru_cycle && !gruc_cycle;
     // a recurrent part: one optional term, Offset(x, -d) with 1 <= d <= kLstmMaxDelay
     // (self_scale: where given, the term may be Offset(Scale(s, node), -d) and s is returned there -- an lstmb-layer block only)
     auto recurrent_part = [&](int at, const DescPart &p, int *node, float *self_scale = nullptr) {
-      if (p.terms.size() != 1 || p.terms[0].const_t || (p.terms[0].scale != 1.0f && !self_scale)) refuse(at, "its recurrent input is not IfDefined(Offset(node, -delay))");
+      if (p.terms.size() != 1 || p.terms[0].const_t || p.terms[0].konst || (p.terms[0].scale != 1.0f && !self_scale)) refuse(at, "its recurrent input is not IfDefined(Offset(node, -delay))");
       if (self_scale) *self_scale = p.terms[0].scale;
       const DescTerm &t = p.terms[0];
       if (!t.optional) refuse(at, "its recurrent input " + nodes[t.node].name + " is not inside IfDefined()");
@@ -1294,7 +1322,7 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
       *node = t.node;
       return -t.offset;
     };
-    auto plain_part = [&](const DescPart &p) { return p.terms.size() == 1 && !p.terms[0].const_t && !p.terms[0].optional && p.terms[0].offset == 0 && p.terms[0].scale == 1.0f; };
+    auto plain_part = [&](const DescPart &p) { return p.terms.size() == 1 && !p.terms[0].const_t && !p.terms[0].konst && !p.terms[0].optional && p.terms[0].offset == 0 && p.terms[0].scale == 1.0f; };
     auto range_of = [&](int n, int src, int off, int dim) { return nodes[n].kind == NnetNode::kDimRange && nodes[n].range_node == src && nodes[n].range_offset == off && nodes[n].dim == dim; };
     auto only_input = [&](int n) { const NnetNode &nd = nodes[n]; return nd.input.parts.size() == 1 && plain_part(nd.input.parts[0]) ? nd.input.parts[0].terms[0].node : -1; };
     auto is_affine = [&](int n) { const std::string t = comp_type(n); return t == "AffineComponent" || t == "NaturalGradientAffineComponent"; };
@@ -1304,11 +1332,195 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
         if (a[i].dim != c[i].dim || a[i].terms.size() != c[i].terms.size()) return false;
         for (size_t j = 0; j < a[i].terms.size(); j++) {
           const DescTerm &s = a[i].terms[j], &t = c[i].terms[j];
-          if (s.node != t.node || s.offset != t.offset || s.scale != t.scale || s.const_t != t.const_t || s.optional != t.optional) return false;
+          if (s.node != t.node || s.offset != t.offset || s.scale != t.scale || s.const_t != t.const_t || s.konst != t.konst || s.optional != t.optional) return false;
         }
       }
       return true;
     };
+    if (gruc_cycle) {
+      // ---- a GRU cell spelled out (xconfig/gru.py: XconfigGruLayer :36-169, XconfigPgruLayer :197-371, XconfigNormPgruLayer :400-605,
+      // XconfigOpgruLayer :631-806, XconfigNormOpgruLayer :834-1045), found from its NoOpComponent node y_t
+      auto is_trunc = [&](int n) { const std::string t = comp_type(n); return t == "BackpropTruncationComponent" || t == "ClipGradientComponent"; };
+      auto is_product = [&](int n, int dim) { return n >= 0 && comp_type(n) == "ElementwiseProductComponent" && nodes[n].dim == dim && nodes[n].input.dim == 2 * dim; };
+      int y_t = -1;
+      for (int n : scc)
+        if (comp_type(n) == "NoOpComponent") {
+          if (y_t >= 0) refuse(n, "a second NoOpComponent node in one cycle");
+          y_t = n;
+        }
+      b.gruc = true;
+      b.sc = y_t;
+      const int C = b.cell = nodes[y_t].dim;
+      // y_t = NoOp(Sum(y1_t, y2_t))
+      {
+        const NnetNode &yn = nodes[y_t];
+        bool ok = yn.input.parts.size() == 1 && yn.input.parts[0].terms.size() == 2;
+        if (ok) for (auto &t : yn.input.parts[0].terms) ok = ok && !t.const_t && !t.konst && !t.optional && t.offset == 0 && t.scale == 1.0f;
+        if (!ok) refuse(y_t, "its input is not Sum(y1_t, y2_t)");
+        b.y1 = yn.input.parts[0].terms[0].node;
+        b.y2 = yn.input.parts[0].terms[1].node;
+      }
+      if (!is_product(b.y1, C) || !is_product(b.y2, C)) refuse(y_t, "its input is not the Sum() of two ElementwiseProductComponent nodes of the cell's dim");
+      // y1_t = Append(h_t, Sum(Scale(-1.0, z_t), Const(1.0, cell)))
+      const NnetNode &y1n = nodes[b.y1];
+      if (y1n.input.parts.size() != 2 || !plain_part(y1n.input.parts[0]) || y1n.input.parts[1].terms.size() != 2)
+        refuse(b.y1, "its input is not Append(h_t, Sum(Scale(-1.0, z_t), Const(1.0, cell-dim)))");
+      b.ht = y1n.input.parts[0].terms[0].node;
+      const DescTerm &zt = y1n.input.parts[1].terms[0], &one = y1n.input.parts[1].terms[1];
+      if (zt.konst || zt.const_t || zt.optional || zt.offset != 0 || !one.konst)
+        refuse(b.y1, "its second input is not Sum(Scale(-1.0, z_t), Const(1.0, cell-dim)), in that order");
+      if (zt.scale != -1.0f) refuse(b.y1, "its second input scales " + nodes[zt.node].name + " by " + std::to_string(zt.scale) + ", not by -1.0: it is not 1 - z_t");
+      if (one.scale != 1.0f) refuse(b.y1, "its second input adds Const(" + std::to_string(one.scale) + "), not Const(1.0): it is not 1 - z_t");
+      const int z_t = zt.node;
+      // y2_t = Append(IfDefined(Offset(y_t, -d)), z_t); gru-layer reads s_t there
+      const NnetNode &y2n = nodes[b.y2];
+      if (y2n.input.parts.size() != 2) refuse(b.y2, "its input is not Append(IfDefined(Offset(y_t, -delay)), z_t)");
+      int y_prev = -1;
+      b.delay = recurrent_part(b.y2, y2n.input.parts[0], &y_prev);
+      if (!plain_part(y2n.input.parts[1]) || y2n.input.parts[1].terms[0].node != z_t)
+        refuse(b.y2, "its second input is not the update gate " + nodes[z_t].name + " that y1_t reads");
+      auto state_part = [&](int at, const DescPart &p, int want, const char *role) {
+        int node = -1;
+        const int d2 = recurrent_part(at, p, &node);
+        if (d2 != b.delay) refuse(at, "two different delays in one block, " + std::to_string(d2) + " and " + std::to_string(b.delay));
+        if (want >= 0 && node != want) refuse(at, std::string(role) + " reads " + nodes[node].name + ", not " + nodes[want].name);
+        return node;
+      };
+      // a gate: [DropoutComponent over] a SigmoidComponent over an affine over Append(x, IfDefined(Offset(s_t, -d)))
+      auto gate = [&](int g, int rows, const char *rows_name, int *drop, int *sig, int *aff) {
+        *drop = -1;
+        if (comp_type(g) == "DropoutComponent") {
+          *drop = g;
+          g = only_input(g);
+          if (g < 0) refuse(*drop, "the dropout's input is not one node");
+        }
+        if (comp_type(g) != "SigmoidComponent") refuse(g, "the gate is not a SigmoidComponent node [behind a DropoutComponent]");
+        *sig = g;
+        const int a = only_input(g);
+        if (a < 0 || !is_affine(a)) refuse(g, "the sigmoid's input is not an affine component node");
+        *aff = a;
+        const NnetNode &an = nodes[a];
+        if (an.input.parts.size() < 2) refuse(a, "its input is not Append(x, IfDefined(Offset(s_t, -delay)))");
+        const int state = state_part(a, an.input.parts.back(), b.tr, "the gate");
+        if (b.tr < 0) b.tr = b.sr = state;
+        if (rows > 0 && an.dim != rows) refuse(a, "the gate's affine has " + std::to_string(an.dim) + " rows, not the " + rows_name + " " + std::to_string(rows));
+      };
+      gate(z_t, C, "cell's dim", &b.zd, &b.zs, &b.wa);
+      if (!is_trunc(b.tr)) refuse(b.tr, "the recurrent state does not come through a BackpropTruncationComponent / ClipGradientComponent");
+      const int R = b.rec_dim = nodes[b.tr].dim;
+      const NnetNode &wz = nodes[b.wa];
+      b.x_parts.assign(wz.input.parts.begin(), wz.input.parts.end() - 1);
+      // h_t: a TanhComponent over the affine h_t_pre (the reset-gate family) or over Sum(h_t_pre, h_t_pre2) (the output-gate family)
+      if (comp_type(b.ht) != "TanhComponent") refuse(b.ht, "h_t is not a TanhComponent node");
+      const NnetNode &htn = nodes[b.ht];
+      const bool out_gate = htn.input.parts.size() == 1 && htn.input.parts[0].terms.size() == 2;
+      int src = only_input(b.tr);
+      bool proj = true;
+      if (!out_gate) {
+        b.pgru = true;
+        b.hp = only_input(b.ht);
+        if (b.hp < 0 || !is_affine(b.hp)) refuse(b.ht, "h_t's input is neither an affine component node nor the Sum() of one and a per-element scale");
+        const NnetNode &hp = nodes[b.hp];
+        if (hp.input.parts.size() < 2 || !plain_part(hp.input.parts.back())) refuse(b.hp, "its input is not Append(x, h1_t)");
+        b.h1 = hp.input.parts.back().terms[0].node;
+        if (!is_product(b.h1, R)) refuse(b.h1, "h1_t is not an ElementwiseProductComponent node of the recurrent state's dim " + std::to_string(R));
+        const NnetNode &h1n = nodes[b.h1];
+        if (h1n.input.parts.size() != 2 || !plain_part(h1n.input.parts[0])) refuse(b.h1, "its input is not Append(r_t, IfDefined(Offset(s_t, -delay)))");
+        state_part(b.h1, h1n.input.parts[1], b.tr, "the product h1_t");
+        gate(h1n.input.parts[0].terms[0].node, R, "recurrent dim", &b.od, &b.os, &b.wo);
+        if (!same_parts(hp.input.parts, hp.input.parts.size() - 1, b.x_parts)) refuse(b.hp, "h_t_pre does not read the gates' feed-forward input");
+        if (hp.dim != C) refuse(b.hp, "h_t_pre has " + std::to_string(hp.dim) + " rows, not the cell's dim " + std::to_string(C));
+        if (src == y_t) {      // gru-layer: s_t = s_r(y_t), and y2_t reads s_t
+          proj = false;
+          if (R != C) refuse(b.tr, "without a projection the recurrent state is of the cell's dim");
+          if (y_prev != b.tr) refuse(b.y2, "the product y2_t reads " + nodes[y_prev].name + ", not " + nodes[b.tr].name + " as in gru-layer");
+        }
+      } else {
+        b.gru = true;
+        for (auto &t : htn.input.parts[0].terms) if (t.const_t || t.konst || t.optional || t.offset != 0 || t.scale != 1.0f) refuse(b.ht, "h_t's input is not Sum(h_t_pre, h_t_pre2)");
+        b.hp = htn.input.parts[0].terms[0].node;
+        b.h2 = htn.input.parts[0].terms[1].node;
+        const std::string pt = comp_type(b.h2);
+        if (!is_affine(b.hp) || (pt != "NaturalGradientPerElementScaleComponent" && pt != "PerElementScaleComponent"))
+          refuse(b.ht, "h_t's input is not Sum(affine node, per-element scale node)");
+        const NnetNode &hp = nodes[b.hp], &h2n = nodes[b.h2];
+        if (!same_parts(hp.input.parts, hp.input.parts.size(), b.x_parts)) refuse(b.hp, "h_t_pre is not an affine component node over the gates' feed-forward input");
+        if (hp.dim != C) refuse(b.hp, "h_t_pre has " + std::to_string(hp.dim) + " rows, not the cell's dim " + std::to_string(C));
+        if (h2n.dim != C || h2n.input.parts.size() != 1) refuse(b.h2, "h_t_pre2 is not of the cell's dim over one input");
+        state_part(b.h2, h2n.input.parts[0], y_t, "the per-element scale h_t_pre2");
+      }
+      if (proj) {
+        if (y_prev != y_t) refuse(b.y2, "the product y2_t reads " + nodes[y_prev].name + ", not " + nodes[y_t].name);
+        if (src >= 0 && comp_type(src) == "NormalizeComponent") {
+          b.nm = src;
+          const Component &nmc = net.components[nodes[b.nm].component];
+          if (nmc.f.count("<AddLogStddev>") && nmc.f.at("<AddLogStddev>")[0] != 0.0) refuse(b.nm, "a NormalizeComponent with add-log-stddev=true is not supported");
+          if (nmc.f.count("<BlockDim>") && nmc.Int("<BlockDim>") != (nmc.i.count("<InputDim>") ? nmc.Int("<InputDim>") : nmc.Int("<Dim>")))
+            refuse(b.nm, "a NormalizeComponent with block-dim is not supported");
+          src = only_input(b.nm);
+        }
+        if (src < 0 || nodes[src].kind != NnetNode::kDimRange) refuse(b.tr, "the recurrent state is neither y_t nor a dim-range of W_s.ys' node [through a NormalizeComponent]");
+        b.sp = src;
+        b.wy = nodes[b.sp].range_node;
+        if (!is_affine(b.wy) || !range_of(b.sp, b.wy, 0, R)) refuse(b.sp, "the recurrent state is not the first recurrent-dim columns of an affine component node");
+        int y_in = only_input(b.wy);
+        if (out_gate) {
+          b.cd = y_in;
+          int o_t = -1;
+          if (!is_product(b.cd, C)) refuse(b.wy, "W_s.ys' input is not the ElementwiseProductComponent node y_o_t of the cell's dim");
+          const NnetNode &cd = nodes[b.cd];
+          if (cd.input.parts.size() != 2 || !plain_part(cd.input.parts[0]) || !plain_part(cd.input.parts[1]) || cd.input.parts[1].terms[0].node != y_t)
+            refuse(b.cd, "the product's input is not Append(o_t, y_t)");
+          o_t = cd.input.parts[0].terms[0].node;
+          gate(o_t, C, "cell's dim", &b.od, &b.os, &b.wo);
+        } else if (y_in != y_t) {
+          refuse(b.wy, "W_s.ys' input is not the cell " + nodes[y_t].name);
+        }
+      }
+      if ((b.zd >= 0) != (b.od >= 0)) refuse(b.zd >= 0 ? b.zd : b.od, "only one of the two gates has a DropoutComponent");
+      if (!same_parts(nodes[b.wo].input.parts, nodes[b.wo].input.parts.size() - 1, b.x_parts)) refuse(b.wo, "the two gates do not read the same feed-forward input");
+      for (auto &p : b.x_parts) for (auto &t : p.terms) if (t.konst || in_scc(t.node)) refuse(b.wa, "its feed-forward input reads a Const() or a node of the cycle");
+      b.members = {b.wa, b.wo, b.zs, b.os, b.ht, b.y1, b.y2, y_t, b.tr};
+      for (int n : {b.zd, b.od, b.nm, b.wy, b.sp, b.cd, b.h1, b.h2}) if (n >= 0) b.members.push_back(n);
+      if (b.pgru) b.members.push_back(b.hp);
+      std::sort(b.members.begin(), b.members.end());
+      if (std::adjacent_find(b.members.begin(), b.members.end()) != b.members.end()) refuse(y_t, "a node has two roles in the block");
+      for (int n : scc) if (!std::binary_search(b.members.begin(), b.members.end(), n)) refuse(n, "the node is part of the cycle but not of such a block");
+      for (int n : b.members) if (!in_scc(n)) refuse(n, "the node is not part of the cycle");
+      if (b.gru && (in_scc(b.hp) || (*block_of)[b.hp] >= 0)) refuse(b.hp, "h_t_pre is part of a cycle");
+      // dims against the weights
+      int x_dim = 0;
+      for (auto &p : b.x_parts) x_dim += p.dim;
+      for (int a : {b.wa, b.wo, b.hp}) {
+        const MatF &W = net.components[nodes[a].component].m.at("<LinearParams>");
+        const int rec_cols = a == b.hp && b.gru ? 0 : R;
+        if (W.rows != nodes[a].dim || W.cols != x_dim + rec_cols)
+          refuse(a, "its weights are " + std::to_string(W.rows) + " x " + std::to_string(W.cols) + ", the block needs " + std::to_string(nodes[a].dim) + " rows and the feed-forward input's " +
+                        std::to_string(x_dim) + " + the recurrent input's " + std::to_string(rec_cols) + " columns");
+      }
+      if (b.gru) {
+        const Component &pc = net.components[nodes[b.h2].component];
+        auto pit = pc.v.find("<Params>");
+        if (pit == pc.v.end() || (int)pit->second.size() != C) refuse(b.h2, "the per-element scale's <Params> are not a vector of the cell's dim " + std::to_string(C));
+      }
+      if (b.wy >= 0) {
+        const MatF &Wy = net.components[nodes[b.wy].component].m.at("<LinearParams>");
+        if (Wy.cols != C || Wy.rows < R || Wy.rows != nodes[b.wy].dim) refuse(b.wy, "W_s.ys is " + std::to_string(Wy.rows) + " x " + std::to_string(Wy.cols) + ", the block needs cell-dim columns and at least the recurrent dim's rows");
+      }
+      // only what has a buffer may be read from outside the block: y_t, W_s.ys' node, its dim-range and the state
+      for (int n = 0; n < N; n++) {
+        if (std::binary_search(b.members.begin(), b.members.end(), n) || index[n] < 0 || n == b.hp) continue;
+        std::vector<int> d;
+        deps(n, &d);
+        for (int m : d)
+          if ((m == b.hp || std::binary_search(b.members.begin(), b.members.end(), m)) && m != y_t && m != b.wy && m != b.sp && m != b.tr)
+            refuse(m, "the node is read from outside the block, by " + nodes[n].name);
+      }
+      if (b.gru) { b.members.push_back(b.hp); std::sort(b.members.begin(), b.members.end()); }
+      for (int n : b.members) (*block_of)[n] = (int)blocks->size();
+      blocks->push_back(std::move(b));
+      continue;
+    }
     if (composed_cycle) {
       // ---- the composed LSTM(P) cell (xconfig/lstm.py: XconfigLstmpLayer :440-565, XconfigLstmLayer :160-255)
       auto no = [&](int n, const std::string &why) {
@@ -1327,7 +1539,7 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
       auto two_sum = [&](int n, int *x, int *y) {        // Sum(x, y) of two plain nodes
         const NnetNode &nd = nodes[n];
         if (nd.input.parts.size() != 1 || nd.input.parts[0].terms.size() != 2) return false;
-        for (auto &t : nd.input.parts[0].terms) if (t.const_t || t.optional || t.offset != 0 || t.scale != 1.0f) return false;
+        for (auto &t : nd.input.parts[0].terms) if (t.const_t || t.konst || t.optional || t.offset != 0 || t.scale != 1.0f) return false;
         *x = nd.input.parts[0].terms[0].node;
         *y = nd.input.parts[0].terms[1].node;
         return true;
@@ -1841,6 +2053,15 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
     for (int n : b.members) (*block_of)[n] = (int)blocks->size();
     blocks->push_back(std::move(b));
   }
+  // a Const() term has no node: it is known only as the 1 of the (1 - z_t) in y1_t of a composed GRU block
+  for (int n = 0; n < N; n++) {
+    if (index[n] < 0) continue;
+    bool konst = false;
+    for (auto &p : nodes[n].input.parts) for (auto &t : p.terms) konst = konst || t.konst;
+    if (konst && !((*block_of)[n] >= 0 && (*blocks)[(*block_of)[n]].gruc && (*blocks)[(*block_of)[n]].y1 == n))
+      Fail("nnet3: Const() in the input of node " + nodes[n].name + " is supported only as the Sum(Scale(-1.0, z_t), Const(1.0, cell-dim)) of a gru-layer / pgru-layer / "
+           "norm-pgru-layer / opgru-layer / norm-opgru-layer block");
+  }
   // a block whose feed-forward input reads another block's state at a future time would need that block's rows before they exist
   for (const BlockNodes &b : *blocks)
     for (auto &p : b.x_parts)
@@ -1864,7 +2085,8 @@ void Nnet::Compile() {
   int in_node = FindNode("input"), iv_node = FindNode("ivector");
   const int N = (int)nodes.size();
   // recurrent blocks: the cycles of the node graph, each of which has to be what fast-lstmp-layer / fast-lstm-layer, lstmp-layer / lstm-layer,
-  // fast-opgru-layer / fast-norm-opgru-layer or fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer emit
+  // fast-opgru-layer / fast-norm-opgru-layer, fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer or gru-layer / pgru-layer /
+  // norm-pgru-layer / opgru-layer / norm-opgru-layer emit
   std::vector<BlockNodes> blocks;
   std::vector<int> block_of(N, -1);
   FindBlocks(*this, out_node, &blocks, &block_of);
@@ -2064,16 +2286,19 @@ void Nnet::Compile() {
         const int C = b.cell, R = b.rec_dim, l = lext[b.wa], r = rext[b.wa];
         const Component *aff[3] = {&components[nodes[b.wa].component], &components[nodes[b.wo].component], &components[nodes[b.hp].component]};
         const int aff_node[3] = {b.wa, b.wo, b.hp}, aff_rows[3] = {C, R, C}, aff_row0[3] = {0, C, C + R};
-        const int in_dim = aff[2]->m.at("<LinearParams>").cols, pre_dim = 2 * C + R;
+        // (the composed form, gru-layer / pgru-layer / norm-pgru-layer: the third affine is W_h.UW over Append(x, h1_t), its recurrent
+        // columns are the cell x R matrix the walk multiplies with r . s; the block is named after y_t)
+        const int in_dim = aff[2]->m.at("<LinearParams>").cols - (b.gruc ? R : 0), pre_dim = 2 * C + R;
+        const int name_node = b.gruc ? b.sc : b.nl;
         LayerOp g;
         g.kind = LayerOp::kGemm;
-        g.name = nodes[b.nl].name + ".x";
+        g.name = nodes[name_node].name + ".x";
         g.out_dim = pre_dim;
         g.W.Resize(pre_dim, in_dim);
         g.bias.assign(pre_dim, 0.0f);
         LayerOp w;
         w.kind = LayerOp::kPgru;
-        w.name = nodes[b.nl].name;
+        w.name = nodes[name_node].name;
         w.out_dim = 2 * C;
         PgruBlock &k = w.pgru;
         k.W_zs.Resize(C, R);
@@ -2103,7 +2328,12 @@ void Nnet::Compile() {
         k.norm = b.nm >= 0;
         if (k.norm) { const Component &nc = components[nodes[b.nm].component]; k.target_rms = nc.f.count("<TargetRms>") ? (float)nc.f.at("<TargetRms>")[0] : 1.0f; }
         k.dropout = b.zd >= 0;
-        {
+        k.composed = b.gruc;
+        if (b.gruc) {
+          const MatF &W = aff[2]->m.at("<LinearParams>");
+          k.W_h.Resize(C, R);
+          for (int row = 0; row < C; row++) for (int c = 0; c < R; c++) k.W_h(row, c) = W(row, in_dim + c);
+        } else {
           // <w_h>: cell x R (the recogniser checked the shape; a one-row text matrix is in the vector map)
           const Component &nc = components[nodes[b.nl].component];
           auto mit = nc.m.find("<w_h>");
@@ -2122,9 +2352,12 @@ void Nnet::Compile() {
         k.hc_buf = new_buf(2 * C, l, r);
         if (proj) k.y_buf = new_buf(R + k.nonrec, l, r);
         k.s_buf = new_buf(R, l, r);
-        node_buf[b.hp] = k.pre_buf;
-        node_col[b.hp] = C + R;
-        node_buf[b.nl] = node_buf[b.sc] = k.hc_buf;
+        if (!b.gruc) {
+          node_buf[b.hp] = k.pre_buf;
+          node_col[b.hp] = C + R;
+          node_buf[b.nl] = k.hc_buf;
+        }
+        node_buf[b.sc] = k.hc_buf;
         node_col[b.sc] = C;
         if (proj) node_buf[b.wy] = node_buf[b.sp] = k.y_buf;
         node_buf[b.tr] = k.s_buf;
@@ -2207,15 +2440,16 @@ void Nnet::Compile() {
         const int C = b.cell, R = b.rec_dim, l = lext[b.wa], r = rext[b.wa];
         const Component *aff[3] = {&components[nodes[b.wa].component], &components[nodes[b.wo].component], &components[nodes[b.hp].component]};
         const int in_dim = aff[2]->m.at("<LinearParams>").cols;
+        const int name_node = b.gruc ? b.sc : b.nl;      // (the composed form, opgru-layer / norm-opgru-layer, is named after y_t)
         LayerOp g;
         g.kind = LayerOp::kGemm;
-        g.name = nodes[b.nl].name + ".x";
+        g.name = nodes[name_node].name + ".x";
         g.out_dim = 3 * C;
         g.W.Resize(3 * C, in_dim);
         g.bias.assign(3 * C, 0.0f);
         LayerOp w;
         w.kind = LayerOp::kGru;
-        w.name = nodes[b.nl].name;
+        w.name = nodes[name_node].name;
         w.out_dim = 2 * C;
         GruBlock &k = w.gru;
         k.W_s.Resize(2 * C, R);
@@ -2242,7 +2476,8 @@ void Nnet::Compile() {
         k.norm = b.nm >= 0;
         if (k.norm) { const Component &nc = components[nodes[b.nm].component]; k.target_rms = nc.f.count("<TargetRms>") ? (float)nc.f.at("<TargetRms>")[0] : 1.0f; }
         k.dropout = b.zd >= 0;
-        k.w_h = components[nodes[b.nl].component].v.at("<w_h>");
+        k.composed = b.gruc;
+        k.w_h = b.gruc ? components[nodes[b.h2].component].v.at("<Params>") : components[nodes[b.nl].component].v.at("<w_h>");
         k.W_y = wy.m.at("<LinearParams>");
         auto yb = wy.v.find("<BiasParams>");
         k.b_y = yb != wy.v.end() && !yb->second.empty() ? yb->second : std::vector<float>(k.W_y.rows, 0.0f);
@@ -2254,7 +2489,8 @@ void Nnet::Compile() {
         k.s_buf = new_buf(R, l, r);
         node_buf[b.hp] = k.pre_buf;
         node_col[b.hp] = 2 * C;
-        node_buf[b.nl] = node_buf[b.sc] = k.hc_buf;
+        if (!b.gruc) node_buf[b.nl] = k.hc_buf;
+        node_buf[b.sc] = k.hc_buf;
         node_col[b.sc] = C;
         node_buf[b.wy] = node_buf[b.sp] = k.y_buf;
         node_buf[b.tr] = k.s_buf;

@@ -157,6 +157,7 @@ struct DescTerm {
   float scale = 1.0f;
   bool const_t = false;
   bool optional = false;   // inside IfDefined(): the recurrent connections of a block are written that way
+  bool konst = false;      // Const(value, dim): no node (node = -1), `scale` holds the value; only the (1 - z_t) of a composed GRU block
 };
 // Append(part0, part1, ...) where each part is a Sum of terms of equal dim.
 struct DescPart {
@@ -268,6 +269,10 @@ struct GruBlock {
   bool norm = false;              // fast-norm-opgru-layer: a NormalizeComponent between y[0:rec] and the truncation component
   float target_rms = 1.0f;        // its <TargetRms>
   bool dropout = false;           // the norm variant's shared DropoutComponent behind the sigmoids: a copy in test mode
+  // the composed form (opgru-layer / norm-opgru-layer: the cell spelled out as Sigmoid / Tanh / ElementwiseProduct / NoOp nodes, w_h a
+  // NaturalGradientPerElementScaleComponent's <Params>): the same operands and buffers, walked by nnet_gruc.hip in that form's order,
+  //   c = fl(fl(h . fl(1 - z)) + fl(c[t - d] . z))
+  bool composed = false;
   MatF W_s;                       // 2 cell x rec: the recurrent columns of W_z over those of W_o
   std::vector<float> w_h;         // cell
   MatF W_y;                       // (rec + nonrec) x cell
@@ -292,6 +297,10 @@ struct PgruBlock {
   bool norm = false;              // fast-norm-pgru-layer: a NormalizeComponent between y[0:rec] and the truncation component
   float target_rms = 1.0f;        // its <TargetRms>
   bool dropout = false;           // the norm variant's two DropoutComponents behind the sigmoids: copies in test mode
+  // the composed form (pgru-layer / norm-pgru-layer / gru-layer: the cell spelled out as Sigmoid / Tanh / ElementwiseProduct / NoOp
+  // nodes, W_h the recurrent columns of the affine W_h.UW): the same operands and buffers, walked by nnet_gruc.hip in that form's
+  // order, c = fl(fl(h . fl(1 - z)) + fl(c[t - d] . z))
+  bool composed = false;
   MatF W_zs;                      // cell x RecDim(): the recurrent columns of W_z
   MatF W_rs;                      // RecDim() x RecDim(): those of W_r
   MatF W_h;                       // cell x RecDim(): the nonlinearity's <w_h>

@@ -57,9 +57,10 @@ void PgruWeightImages(const PgruBlock &b, const PgruLaunchPlan &p, std::vector<f
 std::string DescribePgru(const std::string &name, const PgruBlock &b, const PgruLaunchPlan &p) {
   std::ostringstream os;
   os << name << " input=" << b.in_dim << " cell=" << b.cell << " rec=" << b.rec << " nonrec=" << b.nonrec << " delay=" << b.delay << " scale=" << b.scale
-     << " norm=" << (b.norm ? 1 : 0) << " dropout=" << (b.dropout ? 1 : 0) << " kernel=pgru16x16x4<w" << kPgruWaves << "> rows_per_block=" << p.rows_per_block
+     << " norm=" << (b.norm ? 1 : 0) << " dropout=" << (b.dropout ? 1 : 0) << " kernel=" << (b.composed ? "pgruc" : "pgru") << "16x16x4<w" << kPgruWaves << "> rows_per_block=" << p.rows_per_block
      << " lds=" << p.lds_bytes << " w_zr=" << p.x_cols << "+" << p.s_cols << " cell_tiles=" << p.cell_tiles << " rec_tiles=" << p.rec_tiles
      << " out_tiles=" << p.out_tiles << " grid=chains/" << p.rows_per_block;
+  if (b.composed) os << " form=composed";      // (gru-layer / pgru-layer / norm-pgru-layer: walked by nnet_gruc.hip on the same plan)
   return os.str();
 }
 

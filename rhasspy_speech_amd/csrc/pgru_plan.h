@@ -25,6 +25,10 @@
 //
 // LDS: two tiles of s rows, the sdotr tile (pitch k_s + 4 floats each) and, with a projection, the tile of c rows (pitch k_c + 4).
 // Without a projection the three tiles are cell wide: 64 * 3 * (k_c + 4) bytes within kPgruMaxLdsBytes lets k_c be 752 at most.
+//
+// The composed form of the same cell (gru-layer / pgru-layer / norm-pgru-layer, model.h: PgruBlock::composed; W_h is then the
+// recurrent columns of the affine W_h.UW) shares the descriptor, the planner, the weight images and the limits; it is walked by a
+// kernel of its own (nnet_gruc.hip: PgrucKernel), the same phases with c = h . (1 - z) + c[t - d] . z in that form's roundings.
 #pragma once
 #include <string>
 #include <vector>

@@ -234,14 +234,17 @@ class ModelSpec:
     # like lstm_layers (behind the LSTM blocks of the same `after`).  One dict per block: after, cell, rec, nonrec (both positive),
     # delay (default 3), scale (the BackpropTruncationComponent's <Scale>, default 1), norm (the norm variant: a NormalizeComponent
     # in the recurrence and a BatchNorm on the output, default False), dropout (norm variant only: the shared DropoutComponent
-    # behind the two sigmoids, default False).
+    # behind the two sigmoids, default False).  form="composed" (default "fast") writes the same cell as separate components, what
+    # opgru-layer / norm-opgru-layer emit: Sigmoid / Tanh / ElementwiseProduct nodes, the per-element scale W_h.UW_elementwise and
+    # the NoOpComponent y_t, under xconfig's names; the layer's output is then sn_t.
     gru_layers: Tuple[Dict[str, object], ...] = ()
     # Recurrent blocks around a GruNonlinearityComponent (nnet3's fast-pgru-layer / fast-norm-pgru-layer / fast-gru-layer,
     # xconfig/gru.py), placed like lstm_layers (behind the OPGRU blocks of the same `after`).  One dict per block: after, cell, rec,
     # nonrec (rec = 0 with nonrec = 0: the plain fast-gru-layer, whose state and output are the cell), delay (default 3), scale
     # (the BackpropTruncationComponent's <Scale>, default 1), norm (fast-norm-pgru-layer: a NormalizeComponent in the recurrence and a
     # BatchNorm on the output, default False), dropout (norm variant only: the two DropoutComponents behind the sigmoids, default
-    # False).
+    # False).  form="composed" (default "fast") writes the same cell as separate components, what pgru-layer / norm-pgru-layer /
+    # gru-layer (rec = nonrec = 0) emit, under xconfig's names; the layer's output is then sn_t, s_t for gru-layer.
     pgru_layers: Tuple[Dict[str, object], ...] = ()
     # Time-restricted self-attention layers between the TDNN layers (xconfig/attention.py), placed like lstm_layers (behind the
     # recurrent blocks of the same `after`).  One dict per layer: after, heads, key_dim, value_dim, left, right (num-left-inputs,
@@ -835,6 +838,13 @@ def _w_elementwise_product(w: KaldiWriter, input_dim: int, output_dim: int) -> N
     w.token("</ElementwiseProductComponent>")
 
 
+def _gru_form(layer: Dict[str, object]) -> str:
+    form = str(layer.get("form", "fast"))
+    if form not in ("fast", "composed"):
+        raise ValueError("gru / pgru layer: form is 'fast' (the default) or 'composed'")
+    return form
+
+
 def gru_layer_dims(layer: Dict[str, object]) -> Tuple[int, int, int, int]:
     """(cell, recurrent, non-recurrent, output) dims of a ModelSpec.gru_layers entry."""
     C, R, P = int(layer["cell"]), int(layer["rec"]), int(layer["nonrec"])
@@ -1070,6 +1080,137 @@ def _pgru_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.
     return f"{name}.y_t", out_dim
 
 
+def _gruc_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.Generator, name: str, layer: Dict[str, object],
+                prev: str, prev_dim: int) -> Tuple[str, int]:
+    """A gru_layers entry with form="composed": the components and nodes XconfigOpgruLayer / XconfigNormOpgruLayer emit
+    (xconfig/gru.py:754-806, 972-1042), in their order and under their names.  Returns the node the next layer reads and its dim."""
+    C, R, P, out_dim = gru_layer_dims(layer)
+    d, scale = int(layer.get("delay", 3)), float(layer.get("scale", 1.0))
+    norm, dropout = bool(layer.get("norm", False)), bool(layer.get("dropout", False))
+
+    def randn(o, i):
+        return (rng.standard_normal((o, i)) / math.sqrt(i)).astype(np.float32)
+
+    def randb(n):
+        return (rng.standard_normal(n) * 0.1).astype(np.float32)
+
+    def affine(W, b):
+        return lambda w, W=W, b=b: _w_affine(w, "NaturalGradientAffineComponent", W, b)
+
+    for g in ("z", "o"):
+        comps.append((f"{name}.W_z.xs_{g}", affine(np.concatenate([randn(C, prev_dim), randn(C, R)], axis=1), randb(C))))
+    comps.append((f"{name}.W_h.UW", affine(randn(C, prev_dim), randb(C))))
+    comps.append((f"{name}.W_h.UW_elementwise", lambda w, v=(rng.standard_normal(C) * 0.3).astype(np.float32): _w_ng_per_element_scale(w, v)))
+    for g in ("z", "o"):
+        comps.append((f"{name}.{g}", lambda w: _w_nonlinear(w, "SigmoidComponent", C)))
+    comps.append((f"{name}.h", lambda w: _w_nonlinear(w, "TanhComponent", C)))
+    for g in ("o1", "y1", "y2"):
+        comps.append((f"{name}.{g}", lambda w: _w_elementwise_product(w, 2 * C, C)))
+    comps.append((f"{name}.y", lambda w: _w_noop(w, C)))
+    if dropout:
+        comps.append((f"{name}.dropout", lambda w: _w_dropout(w, C)))
+    rec, rec_y = f"IfDefined(Offset({name}.s_t, {-d}))", f"IfDefined(Offset({name}.y_t, {-d}))"
+    for g in ("z", "o"):
+        cfg.append(f"component-node name={name}.{g}_t_pre component={name}.W_z.xs_{g} input=Append({prev}, {rec})")
+        if dropout:
+            cfg.append(f"component-node name={name}.{g}_predrop_t component={name}.{g} input={name}.{g}_t_pre")
+            cfg.append(f"component-node name={name}.{g}_t component={name}.dropout input={name}.{g}_predrop_t")
+        else:
+            cfg.append(f"component-node name={name}.{g}_t component={name}.{g} input={name}.{g}_t_pre")
+    cfg.append(f"component-node name={name}.h_t_pre component={name}.W_h.UW input={prev}")
+    cfg.append(f"component-node name={name}.h_t_pre2 component={name}.W_h.UW_elementwise input={rec_y}")
+    cfg.append(f"component-node name={name}.h_t component={name}.h input=Sum({name}.h_t_pre, {name}.h_t_pre2)")
+    cfg.append(f"component-node name={name}.y1_t component={name}.y1 input=Append({name}.h_t, Sum(Scale(-1, {name}.z_t), Const(1, {C})))")
+    cfg.append(f"component-node name={name}.y2_t component={name}.y2 input=Append({rec_y}, {name}.z_t)")
+    cfg.append(f"component-node name={name}.y_t component={name}.y input=Sum({name}.y1_t, {name}.y2_t)")
+    cfg.append(f"component-node name={name}.y_o_t component={name}.o1 input=Append({name}.o_t, {name}.y_t)")
+    comps.append((f"{name}.W_s.ys", affine(randn(R + P, C), randb(R + P))))
+    comps.append((f"{name}.s_r", lambda w: _w_backprop_truncation(w, R, scale, d)))
+    if not norm:
+        cfg.append(f"component-node name={name}.sn_t component={name}.W_s.ys input={name}.y_o_t")
+        cfg.append(f"dim-range-node name={name}.s_t_preclip input-node={name}.sn_t dim-offset=0 dim={R}")
+        cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.s_t_preclip")
+        return f"{name}.sn_t", out_dim
+    mean, var = (0.1 * rng.standard_normal(out_dim)).astype(np.float32), rng.uniform(0.05, 0.2, out_dim).astype(np.float32)
+    comps.append((f"{name}.batchnorm", lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+    comps.append((f"{name}.renorm", lambda w: _w_normalize(w, R)))
+    cfg.append(f"component-node name={name}.sn_nobatchnorm_t component={name}.W_s.ys input={name}.y_o_t")
+    cfg.append(f"component-node name={name}.sn_t component={name}.batchnorm input={name}.sn_nobatchnorm_t")
+    cfg.append(f"dim-range-node name={name}.s_t_preclip input-node={name}.sn_nobatchnorm_t dim-offset=0 dim={R}")
+    cfg.append(f"component-node name={name}.s_t_preclip_renorm component={name}.renorm input={name}.s_t_preclip")
+    cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.s_t_preclip_renorm")
+    return f"{name}.sn_t", out_dim
+
+
+def _pgruc_block(cfg: List[str], comps: List[Tuple[str, object]], rng: np.random.Generator, name: str, layer: Dict[str, object],
+                 prev: str, prev_dim: int) -> Tuple[str, int]:
+    """A pgru_layers entry with form="composed": the components and nodes XconfigGruLayer (rec = nonrec = 0) / XconfigPgruLayer /
+    XconfigNormPgruLayer emit (xconfig/gru.py:122-169, 320-371, 533-605), in their order and under their names.  Returns the node the
+    next layer reads and its dim."""
+    C, R, P, out_dim = pgru_layer_dims(layer)
+    proj = int(layer.get("rec", 0)) > 0
+    d, scale = int(layer.get("delay", 3)), float(layer.get("scale", 1.0))
+    norm, dropout = bool(layer.get("norm", False)), bool(layer.get("dropout", False))
+
+    def randn(o, i):
+        return (rng.standard_normal((o, i)) / math.sqrt(i)).astype(np.float32)
+
+    def randb(n):
+        return (rng.standard_normal(n) * 0.1).astype(np.float32)
+
+    def affine(W, b):
+        return lambda w, W=W, b=b: _w_affine(w, "NaturalGradientAffineComponent", W, b)
+
+    for g, rows in (("z", C), ("r", R)):
+        comps.append((f"{name}.W_z.xs_{g}", affine(np.concatenate([randn(rows, prev_dim), randn(rows, R)], axis=1), randb(rows))))
+    comps.append((f"{name}.W_h.UW", affine(np.concatenate([randn(C, prev_dim), randn(C, R)], axis=1), randb(C))))
+    if dropout:
+        comps.append((f"{name}.dropout_z", lambda w: _w_dropout(w, C)))
+        comps.append((f"{name}.dropout_r", lambda w: _w_dropout(w, R)))
+    comps.append((f"{name}.z", lambda w: _w_nonlinear(w, "SigmoidComponent", C)))
+    comps.append((f"{name}.r", lambda w: _w_nonlinear(w, "SigmoidComponent", R)))
+    comps.append((f"{name}.h", lambda w: _w_nonlinear(w, "TanhComponent", C)))
+    comps.append((f"{name}.h1", lambda w: _w_elementwise_product(w, 2 * R, R)))
+    comps.append((f"{name}.y1", lambda w: _w_elementwise_product(w, 2 * C, C)))
+    comps.append((f"{name}.y2", lambda w: _w_elementwise_product(w, 2 * C, C)))
+    comps.append((f"{name}.y", lambda w: _w_noop(w, C)))
+    rec = f"IfDefined(Offset({name}.s_t, {-d}))"
+    rec_y = f"IfDefined(Offset({name}.y_t, {-d}))" if proj else rec
+    for g in ("z", "r"):
+        cfg.append(f"component-node name={name}.{g}_t_pre component={name}.W_z.xs_{g} input=Append({prev}, {rec})")
+        if dropout:
+            cfg.append(f"component-node name={name}.{g}_predrop_t component={name}.{g} input={name}.{g}_t_pre")
+            cfg.append(f"component-node name={name}.{g}_t component={name}.dropout_{g} input={name}.{g}_predrop_t")
+        else:
+            cfg.append(f"component-node name={name}.{g}_t component={name}.{g} input={name}.{g}_t_pre")
+    cfg.append(f"component-node name={name}.h1_t component={name}.h1 input=Append({name}.r_t, {rec})")
+    cfg.append(f"component-node name={name}.h_t_pre component={name}.W_h.UW input=Append({prev}, {name}.h1_t)")
+    cfg.append(f"component-node name={name}.h_t component={name}.h input={name}.h_t_pre")
+    cfg.append(f"component-node name={name}.y1_t component={name}.y1 input=Append({name}.h_t, Sum(Scale(-1, {name}.z_t), Const(1, {C})))")
+    cfg.append(f"component-node name={name}.y2_t component={name}.y2 input=Append({rec_y}, {name}.z_t)")
+    cfg.append(f"component-node name={name}.y_t component={name}.y input=Sum({name}.y1_t, {name}.y2_t)")
+    if not proj:
+        comps.append((f"{name}.s_r", lambda w: _w_backprop_truncation(w, C, scale, d)))
+        cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.y_t")
+        return f"{name}.s_t", out_dim
+    comps.append((f"{name}.W_s.ys", affine(randn(R + P, C), randb(R + P))))
+    comps.append((f"{name}.s_r", lambda w: _w_backprop_truncation(w, R, scale, d)))
+    if not norm:
+        cfg.append(f"component-node name={name}.sn_t component={name}.W_s.ys input={name}.y_t")
+        cfg.append(f"dim-range-node name={name}.s_t_preclip input-node={name}.sn_t dim-offset=0 dim={R}")
+        cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.s_t_preclip")
+        return f"{name}.sn_t", out_dim
+    mean, var = (0.1 * rng.standard_normal(out_dim)).astype(np.float32), rng.uniform(0.05, 0.2, out_dim).astype(np.float32)
+    comps.append((f"{name}.batchnorm", lambda w, m=mean, v=var: _w_batchnorm(w, m, v)))
+    comps.append((f"{name}.renorm", lambda w: _w_normalize(w, R)))
+    cfg.append(f"component-node name={name}.sn_nobatchnorm_t component={name}.W_s.ys input={name}.y_t")
+    cfg.append(f"dim-range-node name={name}.s_t_preclip input-node={name}.sn_nobatchnorm_t dim-offset=0 dim={R}")
+    cfg.append(f"component-node name={name}.sn_t component={name}.batchnorm input={name}.sn_nobatchnorm_t")
+    cfg.append(f"component-node name={name}.s_renorm_t component={name}.renorm input={name}.s_t_preclip")
+    cfg.append(f"component-node name={name}.s_t component={name}.s_r input={name}.s_renorm_t")
+    return f"{name}.sn_t", out_dim
+
+
 def _append_desc(src: str, offsets: Sequence[int]) -> str:
     parts = [src if o == 0 else f"Offset({src}, {o})" for o in offsets]
     return parts[0] if len(parts) == 1 else "Append(" + ", ".join(parts) + ")"
@@ -1155,10 +1296,10 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
                 prev, prev_dim = _lstm_block(cfg, comps, rng, f"lstm{k}", layer, prev, prev_dim)
         for k, layer in enumerate(spec.gru_layers, start=1):
             if int(layer["after"]) == n_layers:
-                prev, prev_dim = _gru_block(cfg, comps, rng, f"gru{k}", layer, prev, prev_dim)
+                prev, prev_dim = (_gruc_block if _gru_form(layer) == "composed" else _gru_block)(cfg, comps, rng, f"gru{k}", layer, prev, prev_dim)
         for k, layer in enumerate(spec.pgru_layers, start=1):
             if int(layer["after"]) == n_layers:
-                prev, prev_dim = _pgru_block(cfg, comps, rng, f"pgru{k}", layer, prev, prev_dim)
+                prev, prev_dim = (_pgruc_block if _gru_form(layer) == "composed" else _pgru_block)(cfg, comps, rng, f"pgru{k}", layer, prev, prev_dim)
         for k, layer in enumerate(spec.attention_layers, start=1):
             if int(layer["after"]) == n_layers:
                 prev, prev_dim = _attention_layer(cfg, comps, rng, f"attention{k}", layer, prev, prev_dim)
