@@ -1377,6 +1377,37 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
   const Nnet &nn = am_.nnet;
   const bool images_on = imgs != nullptr && GemmImagesEnabled() && !tls_exact_gemm && tls_gemm_ovf_dev != nullptr;
   if (op_begin == 0 && !tls_exact_gemm) ZeroGuards(bufp, buf_ld, rows, images_on ? imgs : nullptr, s);
+  // The recurrent blocks (recurrent_walk.h).  The rows and streams of the call as a block's kernel walks them: ob is the block's
+  // output buffer, state_w the floats of a row of its parked state
+  auto rec_walk = [&](size_t i, const BufferInfo &ob, int delay, int need_lext, int state_w) {
+    if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
+    RecWalk w;
+    std::memset(&w, 0, sizeof(w));
+    w.delay = delay; w.stride = ob.stride;
+    w.n_utts = lstm->n_utts; w.L = L_; w.lext = ob.lext; w.rext = ob.rext;
+    w.num_frames = lstm->num_frames; w.row_base = lstm->row_base;
+    w.t0 = lstm->t0; w.slot = lstm->slot; w.lext_cont = need_lext;
+    w.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
+    w.state_w = state_w;
+    if (w.slot && !w.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
+    return w;
+  };
+  // (a stream advance evaluates the layers above on all rows of its segments: the rows the walk does not reach -- before the
+  // re-entry point, behind the last row its readers need -- hold zeros, not what the arena held)
+  auto zero_unreached = [&](const RowMaps::Entry *rm, const int *outs, int n) {
+    if (rm) return;
+    for (int k = 0; k < n; k++)
+      if (outs[k] >= 0) RS_HIP(hipMemsetAsync(bufp[outs[k]], 0, sizeof(float) * (size_t)rows * buf_ld[outs[k]], s));
+  };
+  // operand images of what the split-fp16 layers above read: the rows the walk wrote
+  auto image_rows_written = [&](const RowMaps::Entry *rm, const int *outs, int n) {
+    if (!images_on) return;
+    for (int k = 0; k < n; k++) {
+      const int b = outs[k];
+      if (b >= 0 && (*imgs)[b].base)
+        LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
+    }
+  };
   for (size_t i = op_begin; i < op_end; i++) {
     const LayerOp &op = nn.ops[i];
     const bool img_out = images_on && (*imgs)[op.out_buf].base != nullptr;
@@ -1424,16 +1455,11 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
         LaunchConv(d, rows, s);
       }
     } else if (op.kind == LayerOp::kLstm || op.kind == LayerOp::kLstmp) {
-      if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
       const LstmBlock &k = op.lstm;
       const BufferInfo &ob = nn.bufs[op.out_buf];
       const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride);
-      const int outs[3] = {k.cm_buf, k.st_buf, k.rp_buf};
-      // (a stream advance evaluates the layers above on all rows of its segments: the rows the walk does not reach -- before the
-      // re-entry point, behind the last row its readers need -- hold zeros, not what the arena held)
-      if (!rm)
-        for (int b : outs)
-          if (b >= 0) RS_HIP(hipMemsetAsync(bufp[b], 0, sizeof(float) * (size_t)rows * buf_ld[b], s));
+      const int outs[3] = {k.cm_buf, k.st_buf, k.rp_buf};      // (rp_buf: -1 without a projection)
+      zero_unreached(rm, outs, 3);
       LstmDev d;
       std::memset(&d, 0, sizeof(d));
       d.pre = bufp[k.pre_buf]; d.ld_pre = buf_ld[k.pre_buf];
@@ -1442,30 +1468,19 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       if (k.rp_buf >= 0) { d.rp = bufp[k.rp_buf]; d.ld_rp = buf_ld[k.rp_buf]; }
       d.wr_t = lstm_dev_[i].wr_t; d.wrp_t = lstm_dev_[i].wrp_t; d.b_rp = lstm_dev_[i].b_rp; d.params = lstm_dev_[i].params;
       d.cell = k.cell; d.rec_dim = k.RecDim(); d.out_dim = k.proj() ? k.rec + k.nonrec : 0; d.rec = k.rec;
-      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale; d.scale_r = k.scale_r;
-      d.n_utts = lstm->n_utts; d.L = L_; d.lext = ob.lext; d.rext = ob.rext;
-      d.num_frames = lstm->num_frames; d.row_base = lstm->row_base;
-      d.t0 = lstm->t0; d.slot = lstm->slot; d.lext_cont = k.need_lext;
-      d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
-      if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
+      d.scale = k.scale; d.scale_r = k.scale_r;
+      d.walk = rec_walk(i, ob, k.delay, k.need_lext, k.StateDim());
       d.plan = lstm_plans_[i];
       if (op.kind == LayerOp::kLstmp) LaunchLstmp(d, s);      // (the composed form: a kernel of its own on the same descriptor)
       else LaunchLstm(d, s);
-      // operand images of what the split-fp16 layers above read: the rows the walk wrote
-      if (images_on)
-        for (int b : outs)
-          if (b >= 0 && (*imgs)[b].base)
-            LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
+      image_rows_written(rm, outs, 3);
       continue;
     } else if (op.kind == LayerOp::kLstmb) {
-      if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
       const LstmBlock &k = op.lstm;
       const BufferInfo &ob = nn.bufs[op.out_buf];
       const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride);
       const int outs[2] = {k.cm_buf, k.st_buf};
-      // (as for a fast block: the rows of a stream advance the walk does not reach hold zeros, not what the arena held)
-      if (!rm)
-        for (int b : outs) RS_HIP(hipMemsetAsync(bufp[b], 0, sizeof(float) * (size_t)rows * buf_ld[b], s));
+      zero_unreached(rm, outs, 2);
       LstmbDev d;
       std::memset(&d, 0, sizeof(d));
       d.pre = bufp[k.pre_buf]; d.ld_pre = buf_ld[k.pre_buf];
@@ -1474,28 +1489,18 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       d.wam_t = lstmb_dev_[i].wam_t; d.wb_t = lstmb_dev_[i].wb_t;
       d.so_scale = lstmb_dev_[i].so_scale; d.so_offset = lstmb_dev_[i].so_offset; d.params = lstmb_dev_[i].params;
       d.cell = k.cell; d.bottleneck = k.bottleneck;
-      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale; d.self_scale = k.self_scale;
-      d.n_utts = lstm->n_utts; d.L = L_; d.lext = ob.lext; d.rext = ob.rext;
-      d.num_frames = lstm->num_frames; d.row_base = lstm->row_base;
-      d.t0 = lstm->t0; d.slot = lstm->slot; d.lext_cont = k.need_lext;
-      d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
-      if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
+      d.scale = k.scale; d.self_scale = k.self_scale;
+      d.walk = rec_walk(i, ob, k.delay, k.need_lext, k.StateDim());
       d.plan = lstmb_plans_[i];
       LaunchLstmb(d, s);
-      if (images_on)
-        for (int b : outs)
-          if ((*imgs)[b].base)
-            LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
+      image_rows_written(rm, outs, 2);
       continue;
     } else if (op.kind == LayerOp::kGru) {
-      if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
       const GruBlock &k = op.gru;
       const BufferInfo &ob = nn.bufs[op.out_buf];
       const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride);
       const int outs[3] = {k.hc_buf, k.s_buf, k.y_buf};
-      // (as for an LSTM block: the rows of a stream advance the walk does not reach hold zeros, not what the arena held)
-      if (!rm)
-        for (int b : outs) RS_HIP(hipMemsetAsync(bufp[b], 0, sizeof(float) * (size_t)rows * buf_ld[b], s));
+      zero_unreached(rm, outs, 3);
       GruDev d;
       std::memset(&d, 0, sizeof(d));
       d.pre = bufp[k.pre_buf]; d.ld_pre = buf_ld[k.pre_buf];
@@ -1504,31 +1509,20 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       d.st = bufp[k.s_buf]; d.ld_st = buf_ld[k.s_buf];
       d.ws_t = gru_dev_[i].ws_t; d.wy_t = gru_dev_[i].wy_t; d.b_y = gru_dev_[i].b_y; d.w_h = gru_dev_[i].w_h;
       d.cell = k.cell; d.rec = k.rec; d.out_dim = k.rec + k.nonrec;
-      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale;
+      d.scale = k.scale;
       d.norm = k.norm ? 1 : 0; d.norm_alpha = 1.0f / ((float)k.rec * k.target_rms * k.target_rms);
-      d.n_utts = lstm->n_utts; d.L = L_; d.lext = ob.lext; d.rext = ob.rext;
-      d.num_frames = lstm->num_frames; d.row_base = lstm->row_base;
-      d.t0 = lstm->t0; d.slot = lstm->slot; d.lext_cont = k.need_lext;
-      d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
-      if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
+      d.walk = rec_walk(i, ob, k.delay, k.need_lext, k.StateDim());
       d.plan = gru_plans_[i];
       if (k.composed) LaunchGruc(d, s);      // (opgru-layer / norm-opgru-layer: a kernel of its own on the same descriptor)
       else LaunchGru(d, s);
-      if (images_on)
-        for (int b : outs)
-          if ((*imgs)[b].base)
-            LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
+      image_rows_written(rm, outs, 3);
       continue;
     } else if (op.kind == LayerOp::kPgru) {
-      if (!lstm) Fail("internal error: a recurrent block without the call's utterances");
       const PgruBlock &k = op.pgru;
       const BufferInfo &ob = nn.bufs[op.out_buf];
       const RowMaps::Entry *rm = row_maps.Find(ob.lext, ob.rext, ob.stride);
       const int outs[3] = {k.hc_buf, k.s_buf, k.y_buf};      // (y_buf: -1 without a projection)
-      // (as for an LSTM block: the rows of a stream advance the walk does not reach hold zeros, not what the arena held)
-      if (!rm)
-        for (int b : outs)
-          if (b >= 0) RS_HIP(hipMemsetAsync(bufp[b], 0, sizeof(float) * (size_t)rows * buf_ld[b], s));
+      zero_unreached(rm, outs, 3);
       PgruDev d;
       std::memset(&d, 0, sizeof(d));
       d.pre = bufp[k.pre_buf]; d.ld_pre = buf_ld[k.pre_buf];
@@ -1537,20 +1531,13 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       d.st = bufp[k.s_buf]; d.ld_st = buf_ld[k.s_buf];
       d.wr_t = pgru_dev_[i].wr_t; d.wzh_t = pgru_dev_[i].wzh_t; d.wy_t = pgru_dev_[i].wy_t; d.b_y = pgru_dev_[i].b_y;
       d.cell = k.cell; d.rec = k.RecDim(); d.out_dim = k.rec + k.nonrec; d.proj = k.proj() ? 1 : 0;
-      d.delay = k.delay; d.stride = ob.stride; d.scale = k.scale;
+      d.scale = k.scale;
       d.norm = k.norm ? 1 : 0; d.norm_alpha = 1.0f / ((float)k.RecDim() * k.target_rms * k.target_rms);
-      d.n_utts = lstm->n_utts; d.L = L_; d.lext = ob.lext; d.rext = ob.rext;
-      d.num_frames = lstm->num_frames; d.row_base = lstm->row_base;
-      d.t0 = lstm->t0; d.slot = lstm->slot; d.lext_cont = k.need_lext;
-      d.ring = lstm->rings ? (*lstm->rings)[i] : nullptr;
-      if (d.slot && !d.ring) Fail("internal error: a stream advance without the recurrent block's parked state");
+      d.walk = rec_walk(i, ob, k.delay, k.need_lext, k.StateDim());
       d.plan = pgru_plans_[i];
       if (k.composed) LaunchPgruc(d, s);      // (gru-layer / pgru-layer / norm-pgru-layer: likewise)
       else LaunchPgru(d, s);
-      if (images_on)
-        for (int b : outs)
-          if (b >= 0 && (*imgs)[b].base)
-            LaunchToImage(bufp[b], buf_ld[b], nn.bufs[b].dim, rm ? rm->count : rows, (*imgs)[b], tls_gemm_ovf_dev, s, rm ? rm->rows : nullptr);
+      image_rows_written(rm, outs, 3);
       continue;
     } else if (op.kind == LayerOp::kAttention) {
       const AttentionGeom &g = op.attention;

@@ -23,12 +23,12 @@ GruLaunchPlan PlanGru(const GruBlock &b, const std::string &name) {
   p.n_out = 16 * p.out_tiles;
   p.ld_s = p.k_s + 4;
   p.ld_c = p.k_c + 4;
-  p.rows_per_block = kGruChains;
+  p.rows_per_block = kRecChains;
   // two tiles of s rows (the one a step reads, the one it writes for the next step) and the tile of c . o rows
-  const long lds = (long)kGruChains * (2 * p.ld_s + p.ld_c) * (long)sizeof(float);
-  if (lds > kGruMaxLdsBytes)
-    Fail(what + "the state and product rows of " + std::to_string(kGruChains) + " chains (cell dim " + std::to_string(b.cell) + " + recurrent dim " +
-         std::to_string(b.rec) + ", " + std::to_string(lds) + " bytes) do not fit the " + std::to_string(kGruMaxLdsBytes) +
+  const long lds = (long)kRecChains * (2 * p.ld_s + p.ld_c) * (long)sizeof(float);
+  if (lds > kRecMaxLdsBytes)
+    Fail(what + "the state and product rows of " + std::to_string(kRecChains) + " chains (cell dim " + std::to_string(b.cell) + " + recurrent dim " +
+         std::to_string(b.rec) + ", " + std::to_string(lds) + " bytes) do not fit the " + std::to_string(kRecMaxLdsBytes) +
          " bytes of LDS the HIP kernel keeps them in");
   p.lds_bytes = (int)lds;
   return p;
@@ -48,7 +48,7 @@ void GruWeightImages(const GruBlock &b, const GruLaunchPlan &p, std::vector<floa
 std::string DescribeGru(const std::string &name, const GruBlock &b, const GruLaunchPlan &p) {
   std::ostringstream os;
   os << name << " input=" << b.in_dim << " cell=" << b.cell << " rec=" << b.rec << " nonrec=" << b.nonrec << " delay=" << b.delay << " scale=" << b.scale
-     << " norm=" << (b.norm ? 1 : 0) << " dropout=" << (b.dropout ? 1 : 0) << " kernel=" << (b.composed ? "gruc" : "gru") << "16x16x4<w" << kGruWaves << "> rows_per_block=" << p.rows_per_block
+     << " norm=" << (b.norm ? 1 : 0) << " dropout=" << (b.dropout ? 1 : 0) << " kernel=" << (b.composed ? "gruc" : "gru") << "16x16x4<w" << kRecWaves << "> rows_per_block=" << p.rows_per_block
      << " lds=" << p.lds_bytes << " w_zo=" << p.x_cols << "+" << p.s_cols << " cell_tiles=" << p.cell_tiles << " out_tiles=" << p.out_tiles << " grid=chains/"
      << p.rows_per_block;
   if (b.composed) os << " form=composed";      // (opgru-layer / norm-opgru-layer: walked by nnet_gruc.hip on the same plan)

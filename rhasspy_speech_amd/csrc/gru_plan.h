@@ -7,8 +7,8 @@
 //   c = h - z . h + z . c[t - d];  y = W_y (c . o) + b_y;  s[t] = scale y[0:rec]  (norm: scale Normalize(y[0:rec]))
 // pre = [W_z,x; W_o,x; W_hpart] x + b has no dependence on time and is one layer GEMM over all rows.  What is serial is walked by
 // this kernel the way nnet_lstm.hip walks an LSTM block (lstm_plan.h): row t needs row t - d only, so the rows of an utterance fall
-// into d independent chains (d / stride of them under --frame-subsampling-factor); a workgroup owns kGruChains chains for the whole
-// launch and walks their steps with workgroup barriers only, the grid is the number of chains over kGruChains.
+// into d independent chains (d / stride of them under --frame-subsampling-factor); a workgroup owns kRecChains chains for the whole
+// launch and walks their steps with workgroup barriers only, the grid is the number of chains over kRecChains.
 //
 // A step: the 16 chains' s[t - d] rows are in LDS (zero where a chain has no earlier row), W_zo,s s for 16 cells x 2 gates per wave
 // item on v_mfma_f32_16x16x4_f32 (the accumulators start from pre[t]), the sigmoids, h and c in the accumulators' registers against
@@ -31,9 +31,6 @@
 
 namespace rs {
 
-constexpr int kGruChains = kLstmChains;            // chains of a workgroup: the rows of one MFMA tile
-constexpr int kGruWaves = 8;                       // waves of a workgroup
-constexpr int kGruMaxLdsBytes = kLstmMaxLdsBytes;  // two tiles of s rows and the tile of c . o rows of one workgroup
 constexpr int kGruMaxCell = 2048;                  // cell dim
 constexpr int kGruMaxProj = 4096;                  // recurrent + non-recurrent dim
 
@@ -45,14 +42,11 @@ struct GruLaunchPlan {
   int n_gates = 0, n_out = 0;      // column pitch of the transposed weights: 2 * 16 * cell_tiles, 16 * out_tiles
   int ld_s = 0, ld_c = 0;          // LDS row pitch of the staged s rows / the c . o rows, in floats (k extent + 4: rows on different banks)
   int lds_bytes = 0;
-  int rows_per_block = 0;          // kGruChains
+  int rows_per_block = 0;          // kRecChains
 };
 
 // Fails (rs::Error) with a message naming the block when a dim is beyond the kernel's limits or the LDS tiles do not fit.
 GruLaunchPlan PlanGru(const GruBlock &b, const std::string &name);
-// chains and grid of a launch: those of an LSTM block (lstm_plan.h)
-constexpr int GruChainsPerUtt(int delay, int stride) { return LstmChainsPerUtt(delay, stride); }
-constexpr int GruGridX(int n_utts, int delay, int stride) { return LstmGridX(n_utts, delay, stride); }
 // the weights in the kernel's order, zero padded: W_s as [k_s][n_gates] with gate g (0: z, 1: o) of cell c in column 2 c + g (a
 // lane's two gate weights of a k-step are one 8-byte load), W_y as [k_c][n_out]
 void GruWeightImages(const GruBlock &b, const GruLaunchPlan &p, std::vector<float> *ws_t, std::vector<float> *wy_t);
@@ -68,16 +62,10 @@ struct GruDev {
   int ld_pre, ld_hc, ld_y, ld_st;
   const float *ws_t, *wy_t, *b_y, *w_h;      // GruWeightImages; b_y: rec + nonrec; w_h: cell
   int cell, rec, out_dim;
-  int delay, stride;
   float scale;
   int norm;              // 1: Normalize in front of the scale
   float norm_alpha;      // 1 / (rec * target_rms^2)
-  // geometry and streams: as LstmDev (lstm_plan.h); a parked state row is [c | s]
-  int n_utts, L, lext, rext;
-  const int *num_frames, *row_base;
-  const int *t0, *slot;
-  int lext_cont;
-  float *ring;           // [slot][delay][cell + rec]
+  RecWalk walk;          // the call's rows and streams (recurrent_walk.h); a parked state row is [c | s], cell + rec
   GruLaunchPlan plan;
 };
 

@@ -23,12 +23,12 @@ LstmLaunchPlan PlanLstm(const LstmBlock &b, const std::string &name) {
   p.n_out = 16 * p.out_tiles;
   p.ld_r = p.k_r + 4;
   p.ld_m = p.k_m + 4;
-  p.rows_per_block = kLstmChains;
+  p.rows_per_block = kRecChains;
   // two tiles of s_r rows (the one a step reads, the one it writes for the next step) and, with a projection, the tile of m rows
-  const long lds = (long)kLstmChains * (2 * p.ld_r + (b.proj() ? p.ld_m : 0)) * (long)sizeof(float);
-  if (lds > kLstmMaxLdsBytes)
-    Fail(what + "the state and output rows of " + std::to_string(kLstmChains) + " chains (cell dim " + std::to_string(b.cell) + " + recurrent dim " +
-         std::to_string(p.r_cols) + ", " + std::to_string(lds) + " bytes) do not fit the " + std::to_string(kLstmMaxLdsBytes) +
+  const long lds = (long)kRecChains * (2 * p.ld_r + (b.proj() ? p.ld_m : 0)) * (long)sizeof(float);
+  if (lds > kRecMaxLdsBytes)
+    Fail(what + "the state and output rows of " + std::to_string(kRecChains) + " chains (cell dim " + std::to_string(b.cell) + " + recurrent dim " +
+         std::to_string(p.r_cols) + ", " + std::to_string(lds) + " bytes) do not fit the " + std::to_string(kRecMaxLdsBytes) +
          " bytes of LDS the HIP kernel keeps them in");
   p.lds_bytes = (int)lds;
   return p;
@@ -49,7 +49,7 @@ void LstmWeightImages(const LstmBlock &b, const LstmLaunchPlan &p, std::vector<f
 std::string DescribeLstm(const std::string &name, const LstmBlock &b, const LstmLaunchPlan &p) {
   std::ostringstream os;
   os << name << " input=" << b.in_dim << " cell=" << b.cell << " rec=" << b.rec << " nonrec=" << b.nonrec << " delay=" << b.delay << " scale=" << b.scale
-     << " dropout_mask=" << (b.dropout_mask ? 1 : 0) << " kernel=lstm16x16x4<w" << kLstmWaves << "> rows_per_block=" << p.rows_per_block << " lds=" << p.lds_bytes
+     << " dropout_mask=" << (b.dropout_mask ? 1 : 0) << " kernel=lstm16x16x4<w" << kRecWaves << "> rows_per_block=" << p.rows_per_block << " lds=" << p.lds_bytes
      << " w_all=" << p.x_cols << "+" << p.r_cols << " cell_tiles=" << p.cell_tiles << " out_tiles=" << p.out_tiles << " grid=chains/" << p.rows_per_block;
   return os.str();
 }
@@ -57,7 +57,7 @@ std::string DescribeLstm(const std::string &name, const LstmBlock &b, const Lstm
 std::string DescribeLstmp(const std::string &name, const LstmBlock &b, const LstmLaunchPlan &p) {
   std::ostringstream os;
   os << name << " input=" << b.in_dim << " cell=" << b.cell << " rec=" << b.rec << " nonrec=" << b.nonrec << " delay=" << b.delay << " scale_c=" << b.scale
-     << " scale_r=" << b.scale_r << " dropout=" << (b.dropout ? 1 : 0) << " kernel=lstmp16x16x4<w" << kLstmWaves << "> rows_per_block=" << p.rows_per_block
+     << " scale_r=" << b.scale_r << " dropout=" << (b.dropout ? 1 : 0) << " kernel=lstmp16x16x4<w" << kRecWaves << "> rows_per_block=" << p.rows_per_block
      << " lds=" << p.lds_bytes << " w_x=" << p.x_cols << " w_r=" << p.r_cols << " cell_tiles=" << p.cell_tiles << " out_tiles=" << p.out_tiles
      << " grid=chains/" << p.rows_per_block;
   return os.str();

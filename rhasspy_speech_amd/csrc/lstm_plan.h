@@ -9,9 +9,9 @@
 // pre = W_x x + b has no dependence on time and is a layer GEMM over all rows (W_all's first x_cols columns; the remaining r_cols
 // are W_r).  What is serial is walked by this kernel.  Row t needs row t - d only, so the rows of an utterance fall into d
 // independent CHAINS, t = first, first + d, first + 2 d, ... (d / stride of them where only every stride-th row is read,
-// --frame-subsampling-factor), and the chains of different utterances never meet.  A workgroup owns kLstmChains chains for the
+// --frame-subsampling-factor), and the chains of different utterances never meet.  A workgroup owns kRecChains chains for the
 // whole launch and walks their steps with workgroup barriers only: no kernel waits for another workgroup, the grid is the number of
-// chains over kLstmChains whatever the device holds.
+// chains over kRecChains whatever the device holds.
 //
 // A step: the 16 chains' s_r[t - d] rows are in LDS (zero where a chain has no earlier row; the previous step left them there --
 // a chain's step n + 1 reads what its step n wrote, so nothing one wave stores to global memory is read by another inside a
@@ -28,10 +28,8 @@
 
 namespace rs {
 
-constexpr int kLstmChains = 16;                 // chains of a workgroup: the rows of one MFMA tile
-constexpr int kLstmWaves = 8;                   // waves of a workgroup
-constexpr int kLstmMaxLdsBytes = 144 * 1024;    // two tiles of s_r rows and the tile of m rows of one workgroup (of the CU's 160 KiB)
-constexpr int kLstmMaxCell = 2048;              // cell dim (the LDS bound below is the tighter one with a wide recurrent input)
+// (chains and waves of a workgroup and its LDS bound -- here two tiles of s_r rows and the tile of m rows --: recurrent_walk.h)
+constexpr int kLstmMaxCell = 2048;             // cell dim (the LDS bound below is the tighter one with a wide recurrent input)
 constexpr int kLstmMaxProj = 4096;              // recurrent + non-recurrent projection dim
 
 struct LstmLaunchPlan {
@@ -42,14 +40,12 @@ struct LstmLaunchPlan {
   int n_gates = 0, n_out = 0;      // column pitch of the transposed weights: 4 * 16 * cell_tiles, 16 * out_tiles
   int ld_r = 0, ld_m = 0;          // LDS row pitch of the staged s_r rows / the m rows, in floats (k extent + 4: rows on different banks)
   int lds_bytes = 0;
-  int rows_per_block = 0;          // kLstmChains
+  int rows_per_block = 0;          // kRecChains
 };
 
 // Fails (rs::Error) with a message naming the block when a dim is beyond the kernel's limits or the two LDS tiles do not fit.
 LstmLaunchPlan PlanLstm(const LstmBlock &b, const std::string &name);
-// chains of a launch: per utterance with rows delay / stride (stride divides the delay wherever it is above 1: Nnet::SetSubsampling)
-constexpr int LstmChainsPerUtt(int delay, int stride) { return stride > 1 ? delay / stride : delay; }
-constexpr int LstmGridX(int n_utts, int delay, int stride) { return (n_utts * LstmChainsPerUtt(delay, stride) + kLstmChains - 1) / kLstmChains; }
+// chains and grid of a launch: RecChainsPerUtt, RecGridX (recurrent_walk.h)
 // the weights in the kernel's order, zero padded: W_r as [k_r][n_gates] with gate g of cell c in column 4 c + g (a lane's four gate
 // weights of a k-step are one 16-byte load), W_rp as [k_m][n_out]
 void LstmWeightImages(const LstmBlock &b, const LstmLaunchPlan &p, std::vector<float> *wr_t, std::vector<float> *wrp_t);
@@ -68,18 +64,9 @@ struct LstmDev {
   int ld_pre, ld_cm, ld_rp, ld_st;
   const float *wr_t, *wrp_t, *b_rp, *params;      // LstmWeightImages; params: 3 x cell
   int cell, rec_dim, out_dim, rec;                // rec_dim: width of s_r; out_dim / rec: rp's width and its recurrent part (0 without a projection)
-  int delay, stride;
   float scale;
   float scale_r;         // the composed form only (nnet_lstmp.hip): `scale` is the cell's truncation component's, this the recurrent state's
-  // geometry: utterance u has frames [0, T_u) at rows row_base[u] + L + t; the walk covers t in [-lext, T_u + rext) (nothing where T_u = 0)
-  int n_utts, L, lext, rext;
-  const int *num_frames, *row_base;
-  // streams: utterance u is the advance of a stream that has computed t0[u] frames before (t0 > 0: the walk re-enters at
-  // -lext_cont, and a chain's first step reads the state row parked for it: ring row (t0 + t) mod delay of slot[u]); every chain parks
-  // the state row the next advance re-enters behind, the t in [T_u - lext_cont - delay, T_u - lext_cont).  null: a batch call.
-  const int *t0, *slot;
-  int lext_cont;
-  float *ring;           // [slot][delay][cell + rec_dim]
+  RecWalk walk;          // the call's rows and streams (recurrent_walk.h); a parked state row is [s_c | s_r], cell + rec_dim
   LstmLaunchPlan plan;
 };
 

@@ -23,12 +23,12 @@ LstmbLaunchPlan PlanLstmb(const LstmBlock &b, const std::string &name) {
   p.n_gates = 4 * 16 * p.cell_tiles;
   p.ld_m = p.k_m + 4;
   p.ld_b = p.k_b + 4;
-  p.rows_per_block = kLstmbChains;
+  p.rows_per_block = kRecChains;
   // the tile of sm rows and the tile of b rows
-  const long lds = (long)kLstmbChains * (p.ld_m + p.ld_b) * (long)sizeof(float);
-  if (lds > kLstmbMaxLdsBytes)
-    Fail(what + "the state and bottleneck rows of " + std::to_string(kLstmbChains) + " chains (cell dim " + std::to_string(b.cell) + " + bottleneck dim " +
-         std::to_string(b.bottleneck) + ", " + std::to_string(lds) + " bytes) do not fit the " + std::to_string(kLstmbMaxLdsBytes) +
+  const long lds = (long)kRecChains * (p.ld_m + p.ld_b) * (long)sizeof(float);
+  if (lds > kRecMaxLdsBytes)
+    Fail(what + "the state and bottleneck rows of " + std::to_string(kRecChains) + " chains (cell dim " + std::to_string(b.cell) + " + bottleneck dim " +
+         std::to_string(b.bottleneck) + ", " + std::to_string(lds) + " bytes) do not fit the " + std::to_string(kRecMaxLdsBytes) +
          " bytes of LDS the HIP kernel keeps them in");
   p.lds_bytes = (int)lds;
   return p;
@@ -48,7 +48,7 @@ void LstmbWeightImages(const LstmBlock &b, const LstmbLaunchPlan &p, std::vector
 std::string DescribeLstmb(const std::string &name, const LstmBlock &b, const LstmbLaunchPlan &p) {
   std::ostringstream os;
   os << name << " input=" << b.in_dim << " cell=" << b.cell << " bottleneck=" << b.bottleneck << " delay=" << b.delay << " scale=" << b.scale
-     << " self_scale=" << b.self_scale << " kernel=lstmb16x16x4<w" << kLstmbWaves << "> rows_per_block=" << p.rows_per_block << " lds=" << p.lds_bytes
+     << " self_scale=" << b.self_scale << " kernel=lstmb16x16x4<w" << kRecWaves << "> rows_per_block=" << p.rows_per_block << " lds=" << p.lds_bytes
      << " w_a=" << p.x_cols << "+" << p.m_cols << " cell_tiles=" << p.cell_tiles << " b_tiles=" << p.b_tiles << " grid=chains/" << p.rows_per_block;
   return os.str();
 }

@@ -6,8 +6,8 @@
 //   b = pre_b[t] + W_a,m sm[t - d];  g = W_b b;  g' = g * so_scale;  g' = g' + so_offset
 //   (c, m) = LstmNonlinearity(g', sc[t - d]; params);  sc[t] = scale c;  sm[t] = self_scale (scale m)
 // pre_b = W_a,x x has no dependence on time and is a layer GEMM over all rows, B wide, without a bias.  What is serial is walked by
-// this kernel the way nnet_lstm.hip walks a fast block (lstm_plan.h): a workgroup of kLstmbWaves waves owns kLstmbChains chains for
-// the whole launch and walks their steps with workgroup barriers only; the grid is the number of chains over kLstmbChains.
+// this kernel the way nnet_lstm.hip walks a fast block (lstm_plan.h): a workgroup of kRecWaves waves owns kRecChains chains for
+// the whole launch and walks their steps with workgroup barriers only; the grid is the number of chains over kRecChains.
 //
 // A step has two phases:
 //   A. b: a wave item is 16 columns of b for the 16 chains, the accumulator starts from pre_b[t] and takes W_a,m sm on
@@ -30,9 +30,6 @@
 
 namespace rs {
 
-constexpr int kLstmbChains = kLstmChains;            // chains of a workgroup: the rows of one MFMA tile
-constexpr int kLstmbWaves = 8;                       // waves of a workgroup
-constexpr int kLstmbMaxLdsBytes = kLstmMaxLdsBytes;  // the two tiles of one workgroup
 constexpr int kLstmbMaxCell = 2048;                  // cell dim
 constexpr int kLstmbMaxBottleneck = 2048;            // bottleneck dim (the LDS bound is the tighter one where both are wide)
 
@@ -44,12 +41,11 @@ struct LstmbLaunchPlan {
   int n_b = 0, n_gates = 0;        // column pitch of the transposed weights: 16 * b_tiles, 4 * 16 * cell_tiles
   int ld_m = 0, ld_b = 0;          // LDS row pitch of the sm rows / the b rows, in floats (k extent + 4: rows on different banks)
   int lds_bytes = 0;
-  int rows_per_block = 0;          // kLstmbChains
+  int rows_per_block = 0;          // kRecChains
 };
 
 // Fails (rs::Error) with a message naming the block when a dim is beyond the kernel's limits or the two LDS tiles do not fit.
 LstmbLaunchPlan PlanLstmb(const LstmBlock &b, const std::string &name);
-// chains and grid of a launch: those of a fast block (lstm_plan.h: LstmChainsPerUtt, LstmGridX)
 // the weights in the kernel's order, zero padded: W_a,m as [k_m][n_b]; W_b as [k_b][n_gates] with gate g of cell c in column 4 c + g
 // (a lane's four gate weights of a k-step are one 16-byte load, as LstmWeightImages' wr_t)
 void LstmbWeightImages(const LstmBlock &b, const LstmbLaunchPlan &p, std::vector<float> *wam_t, std::vector<float> *wb_t);
@@ -65,14 +61,8 @@ struct LstmbDev {
   const float *wam_t, *wb_t;                        // LstmbWeightImages
   const float *so_scale, *so_offset, *params;       // 4 cell each (gate order i, f, c, o); params: 3 x cell
   int cell, bottleneck;
-  int delay, stride;
   float scale, self_scale;
-  // geometry and streams: as LstmDev (lstm_plan.h); a parked state row is [sc | sm]
-  int n_utts, L, lext, rext;
-  const int *num_frames, *row_base;
-  const int *t0, *slot;
-  int lext_cont;
-  float *ring;           // [slot][delay][2 cell]
+  RecWalk walk;          // the call's rows and streams (recurrent_walk.h); a parked state row is [sc | sm], 2 cell
   LstmbLaunchPlan plan;
 };
 

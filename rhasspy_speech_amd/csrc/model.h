@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "kaldi_io.h"
+#include "recurrent_walk.h"
 
 namespace rs {
 
@@ -235,8 +236,8 @@ struct LstmBlock {
   bool proj() const { return rec > 0; }
   int RecDim() const { return rec > 0 ? rec : cell; }
   int OutDim() const { return rec > 0 ? rec + nonrec : cell; }
+  int StateDim() const { return bottleneck > 0 ? 2 * cell : cell + RecDim(); }      // a parked state row: [s_c | s_r], behind a bottleneck [sc | sm]
 };
-constexpr int kLstmMaxDelay = 8;
 // The same cell spelled out as separate components: what nnet3's lstmp-layer / lstmp-batchnorm-layer / lstm-layer emit
 // (xconfig/lstm.py: XconfigLstmpLayer, XconfigLstmLayer), recognised as a unit and held in an LstmBlock with composed = true.  Four
 // affines over Append(x, IfDefined(Offset(r_t, -d))) stacked in gate order i, f, c(g), o (pre = W_x x + b a kGemm op, W_r their

@@ -1,183 +1,111 @@
 // The serial part of a recurrent block around a GruNonlinearityComponent (nnet3's fast-pgru-layer / fast-norm-pgru-layer /
 // fast-gru-layer) on the exact-FP32 matrix cores.  What a workgroup owns, the phases of a step, what it keeps in LDS and why a
-// row's result does not depend on its place: pgru_plan.h.  The chain set-up is that of nnet_gru.hip, restated here: that kernel is
-// left as it is.
+// row's result does not depend on its place: pgru_plan.h.  The chains, the k-loops and the projection and normalisation phases are
+// the ones every recurrent kernel shares (recurrent_dev.h); here are the two gate phases with the cell's roundings.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
 #include "pgru_plan.h"
+#include "recurrent_dev.h"
 
 namespace rs {
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// SigmoidComponent / TanhComponent on the CPU: VectorBase::Sigmoid / Tanh (matrix/kaldi-vector.cc:899-951), on the full-precision expf
-__device__ __forceinline__ float PgruSigmoid(float x) {
-  if (x > 0.f) return 1.f / (1.f + expf(-x));
-  const float ex = expf(x);
-  return ex / (ex + 1.f);
-}
-__device__ __forceinline__ float PgruTanh(float x) {
-  if (x > 0.f) {
-    const float inv_expx = expf(-x);
-    return -1.f + 2.f / (1.f + inv_expx * inv_expx);
-  }
-  const float expx = expf(x);
-  return 1.f - 2.f / (1.f + expx * expx);
-}
-
-// per chain of the workgroup
-struct PgruChain {
-  int row0;        // physical row of the chain's first step; step n is row0 + n * delay
-  int count;       // steps
-  int ring_off;    // streams: offset of the chain's parked state row ([c | s], or [s]) in PgruDev::ring
-  int cont;        // its first step continues from the parked row (else from zeros)
-  int save_step;   // the step whose state row is parked for the next advance, -1: none
-};
-
-__global__ __launch_bounds__(64 * kPgruWaves) void PgruKernel(PgruDev d) {
+__global__ __launch_bounds__(64 * kRecWaves) void PgruKernel(PgruDev d) {
   extern __shared__ float lds[];
-  __shared__ PgruChain chains[kPgruChains];
-  __shared__ int n_steps_s;
+  __shared__ RecChain chains[kRecChains];
   const PgruLaunchPlan &p = d.plan;
+  const RecWalk &w = d.walk;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lm = lane & 15, lk = lane >> 4;
   const int C = d.cell, R = d.rec;
   const bool proj = d.proj != 0;
-  const int state_w = proj ? C + R : C, s_off = proj ? C : 0;      // a parked row, and where its s starts
-  float *const s_tile[2] = {lds, lds + kPgruChains * p.ld_s};
-  float *const sr_tile = lds + 2 * kPgruChains * p.ld_s;
-  float *const c_tile = lds + 3 * kPgruChains * p.ld_s;           // (with a projection only)
+  float *const s_tile[2] = {lds, lds + kRecChains * p.ld_s};
+  float *const sr_tile = lds + 2 * kRecChains * p.ld_s;
+  float *const c_tile = lds + 3 * kRecChains * p.ld_s;           // (with a projection only)
 
-  if (tid < kPgruChains) {
-    const int per_utt = PgruChainsPerUtt(d.delay, d.stride), step = d.stride > 1 ? d.stride : 1;
-    const int chain = blockIdx.x * kPgruChains + tid, u = chain / per_utt, c = chain - u * per_utt;
-    PgruChain ch = {0, 0, 0, 0, -1};
-    const int T = u < d.n_utts ? d.num_frames[u] : 0;
-    if (T > 0) {
-      const int t0 = d.t0 ? d.t0[u] : 0;
-      ch.cont = d.slot != nullptr && t0 > 0;
-      const int t_start = ch.cont ? -d.lext_cont : -d.lext, t_end = T + d.rext;
-      int m = (c * step - t_start) % d.delay;      // the first t >= t_start of the chain's class, t = c * step mod delay
-      if (m < 0) m += d.delay;
-      const int t_first = t_start + m;
-      if (t_first < t_end) ch.count = (t_end - 1 - t_first) / d.delay + 1;
-      ch.row0 = d.row_base[u] + d.L + t_first;
-      if (d.slot) {
-        int rr = (t0 + t_first) % d.delay;
-        if (rr < 0) rr += d.delay;
-        ch.ring_off = (d.slot[u] * d.delay + rr) * state_w;
-        const int re = T - d.lext_cont;            // where the next advance re-enters: it reads the rows [re - delay, re)
-        if (re - 1 >= t_first) ch.save_step = (re - 1 - t_first) / d.delay;
-      }
-    }
-    chains[tid] = ch;
-  }
-  for (int e = tid; e < kPgruChains * (3 * p.ld_s + p.ld_c); e += 64 * kPgruWaves) lds[e] = 0.f;
-  __syncthreads();
-  if (tid == 0) {
-    int n = 0;
-    for (int i = 0; i < kPgruChains; i++) n = max(n, chains[i].count);
-    n_steps_s = n;
-  }
-  // s of the rows before the chains' first: what an earlier advance parked, else the zeros above
-  for (int e = tid; e < kPgruChains * R; e += 64 * kPgruWaves) {
-    const int i = e / R, k = e - i * R;
-    if (chains[i].count > 0 && chains[i].cont) s_tile[0][i * p.ld_s + k] = d.ring[chains[i].ring_off + s_off + k];
-  }
-  __syncthreads();
-  const int n_steps = n_steps_s;
+  // (s starts behind c in a parked row, or is all of it)
+  const int n_steps = RecPrologue(w, chains, lds, kRecChains * (3 * p.ld_s + p.ld_c), s_tile[0], p.ld_s, R, proj ? C : 0);
 
   for (int n = 0; n < n_steps; n++) {
     const float *s_cur = s_tile[n & 1];
     float *s_next = s_tile[(n + 1) & 1];
     // ---- phase 1: r = Sigmoid(pre_r[t] + W_r,s s[t - d]) and sdotr = r . s[t - d]: a wave item is 16 columns of r for the 16 chains
-    for (int item = wave; item < p.rec_tiles; item += kPgruWaves) {
+    for (int item = wave; item < p.rec_tiles; item += kRecWaves) {
       const int col = 16 * item + lm;
-      f32x4 acc;
+      f32x4 acc[1];
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        const PgruChain &ch = chains[4 * lk + r];
+        const RecChain &ch = chains[4 * lk + r];
         const bool live = n < ch.count && col < R;
-        acc[r] = live ? d.pre[(long)(ch.row0 + n * d.delay) * d.ld_pre + C + col] : 0.f;
+        acc[0][r] = live ? d.pre[(long)(ch.row0 + n * w.delay) * d.ld_pre + C + col] : 0.f;
       }
-      const float *wp = d.wr_t + (size_t)lk * p.n_r + col;
-      for (int k0 = 0; k0 < p.k_s; k0 += 16) {      // (k_s is a multiple of 16: four k-steps' operands first, then their MFMAs in k order)
-        float a[4], w[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          a[u] = s_cur[lm * p.ld_s + k0 + 4 * u + lk];
-          w[u] = wp[(size_t)(k0 + 4 * u) * p.n_r];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u], acc, 0, 0, 0);
-      }
-      // (accumulator register r of lane l: chain 4 (l >> 4) + r, column 16 item + (l & 15))
+      RecMfma<1>(acc, s_cur, lm * p.ld_s + lk, d.wr_t + (size_t)lk * p.n_r + col, p.n_r, p.k_s);
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int i = 4 * lk + r;
         const bool live = n < chains[i].count && col < R;
         // AddMatMatElements(1.0, r_t, s_t1, 0.0): one rounding
-        sr_tile[i * p.ld_s + col] = live ? __fmul_rn(PgruSigmoid(acc[r]), s_cur[i * p.ld_s + col]) : 0.f;
+        sr_tile[i * p.ld_s + col] = live ? __fmul_rn(RefSigmoid(acc[0][r]), s_cur[i * p.ld_s + col]) : 0.f;
       }
     }
     __syncthreads();
     // ---- phase 2: z = Sigmoid(pre_z[t] + W_z,s s[t - d]), h = Tanh(pre_h[t] + W_h sdotr), then c: a wave item is 16 cells
-    for (int item = wave; item < p.cell_tiles; item += kPgruWaves) {
+    for (int item = wave; item < p.cell_tiles; item += kRecWaves) {
       const int cell = 16 * item + lm;
       f32x4 acc[2];
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        const PgruChain &ch = chains[4 * lk + r];
+        const RecChain &ch = chains[4 * lk + r];
         const bool live = n < ch.count && cell < C;
-        const float *prow = d.pre + (long)(ch.row0 + n * d.delay) * d.ld_pre + cell;
+        const float *prow = d.pre + (long)(ch.row0 + n * w.delay) * d.ld_pre + cell;
         acc[0][r] = live ? prow[0] : 0.f;
         acc[1][r] = live ? prow[C + R] : 0.f;
       }
       // (a lane's z and h weights of a k are one 8-byte load; z runs over the s rows, h over the sdotr rows)
+      // (the k-loop of recurrent_dev.h over two tiles: four k-steps' operands first, then their MFMAs in k order)
       const float *wp = d.wzh_t + (size_t)lk * p.n_zh + 2 * cell;
       for (int k0 = 0; k0 < p.k_s; k0 += 16) {
         float a[4], ar[4];
-        float2 w[4];
+        float2 wzh[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
           a[u] = s_cur[lm * p.ld_s + k0 + 4 * u + lk];
           ar[u] = sr_tile[lm * p.ld_s + k0 + 4 * u + lk];
-          w[u] = *reinterpret_cast<const float2 *>(wp + (size_t)(k0 + 4 * u) * p.n_zh);
+          wzh[u] = *reinterpret_cast<const float2 *>(wp + (size_t)(k0 + 4 * u) * p.n_zh);
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-          acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u].x, acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[u], w[u].y, acc[1], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], wzh[u].x, acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ar[u], wzh[u].y, acc[1], 0, 0, 0);
         }
       }
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int i = 4 * lk + r;
-        const PgruChain &ch = chains[i];
+        const RecChain &ch = chains[i];
         const bool live = n < ch.count && cell < C;
         float c_t = 0.f, s_t = 0.f;
         if (live) {
-          const long row = ch.row0 + n * d.delay;
+          const long row = ch.row0 + n * w.delay;
           float c_prev;
           if (!proj) c_prev = s_cur[i * p.ld_s + cell];      // (c[t - d] and s[t - d] are one variable)
-          else if (n > 0) c_prev = d.hc[(row - d.delay) * d.ld_hc + C + cell];      // (this lane's own store of the step before)
-          else c_prev = ch.cont ? d.ring[ch.ring_off + cell] : 0.f;
-          const float z_t = PgruSigmoid(acc[0][r]);
+          else if (n > 0) c_prev = d.hc[(row - w.delay) * d.ld_hc + C + cell];      // (this lane's own store of the step before)
+          else c_prev = ch.cont ? w.ring[ch.ring_off + cell] : 0.f;
+          const float z_t = RefSigmoid(acc[0][r]);
           // GruNonlinearityComponent::Propagate (nnet-combined-component.cc:1473-1480): Tanh, CopyFromMat and two AddMatMatElements,
           // one rounding per operation
-          const float h_t = PgruTanh(acc[1][r]);
+          const float h_t = RefTanh(acc[1][r]);
           c_t = __fadd_rn(h_t, __fmul_rn(-z_t, h_t));
           c_t = __fadd_rn(c_t, __fmul_rn(z_t, c_prev));
           d.hc[row * d.ld_hc + cell] = h_t;
           d.hc[row * d.ld_hc + C + cell] = c_t;
           if (proj) {
-            if (n == ch.save_step) d.ring[ch.ring_off + cell] = c_t;
+            if (n == ch.save_step) w.ring[ch.ring_off + cell] = c_t;
           } else {
             s_t = __fmul_rn(c_t, d.scale);
             d.st[row * d.ld_st + cell] = s_t;
-            if (n == ch.save_step) d.ring[ch.ring_off + cell] = s_t;
+            if (n == ch.save_step) w.ring[ch.ring_off + cell] = s_t;
           }
         }
         if (proj) c_tile[i * p.ld_c + cell] = c_t;      // (cell < k_c = 16 cell_tiles)
@@ -187,77 +115,18 @@ __global__ __launch_bounds__(64 * kPgruWaves) void PgruKernel(PgruDev d) {
     __syncthreads();
     if (!proj) continue;
     // ---- phase 3: y = W_y c + b, and its first columns as the recurrent state: scaled here, or left for the normalisation below
-    for (int item = wave; item < p.out_tiles; item += kPgruWaves) {
-      const int col = 16 * item + lm;
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      const float *wp = d.wy_t + (size_t)lk * p.n_out + col;
-      for (int k0 = 0; k0 < p.k_c; k0 += 16) {
-        float a[4], w[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          a[u] = c_tile[lm * p.ld_c + k0 + 4 * u + lk];
-          w[u] = wp[(size_t)(k0 + 4 * u) * p.n_out];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u], acc, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int i = 4 * lk + r;
-        const PgruChain &ch = chains[i];
-        const bool live = n < ch.count && col < d.out_dim;
-        float s_t = 0.f;
-        if (live) {
-          const long row = ch.row0 + n * d.delay;
-          const float v = __fadd_rn(acc[r], d.b_y[col]);
-          d.y[row * d.ld_y + col] = v;
-          if (col < R) {
-            if (d.norm) {
-              s_t = v;
-            } else {
-              s_t = __fmul_rn(v, d.scale);
-              d.st[row * d.ld_st + col] = s_t;
-              if (n == ch.save_step) d.ring[ch.ring_off + C + col] = s_t;
-            }
-          }
-        }
-        if (col < R) s_next[i * p.ld_s + col] = s_t;
-      }
-    }
+    RecProject(chains, n, w.delay, c_tile, p.ld_c, p.k_c, d.wy_t, p.n_out, p.out_tiles, d.b_y, d.y, d.ld_y, d.out_dim, R, d.scale, d.norm != 0,
+               d.st, d.ld_st, 0, w.ring, C, s_next, p.ld_s);
     __syncthreads();
-    // ---- phase 4, norm variant: NormalizePerRow (cu-math.cc:302-310) over each chain's rec columns, then the scale.  A wave takes
-    // two chains; a lane sums its k = lane, lane + 64, ... in that order, the 64 partial sums meet in a fixed tree.
+    // ---- phase 4, norm variant
     if (d.norm) {
-      for (int i = wave; i < kPgruChains; i += kPgruWaves) {
-        const PgruChain &ch = chains[i];
-        if (n >= ch.count) continue;      // (the whole wave: its row of the tile holds zeros)
-        float *srow = s_next + i * p.ld_s;
-        float ss = 0.f;
-        for (int k = lane; k < R; k += 64) ss = __fadd_rn(ss, __fmul_rn(srow[k], srow[k]));
-        for (int o = 32; o > 0; o >>= 1) ss = __fadd_rn(ss, __shfl_xor(ss, o, 64));
-        float nrm = __fmul_rn(ss, d.norm_alpha);
-        nrm = fmaxf(nrm, 1.3552527156068805425e-20f);      // kSquaredNormFloor, 2^-66
-        nrm = powf(nrm, -0.5f);
-        const long row = ch.row0 + n * d.delay;
-        for (int k = lane; k < R; k += 64) {
-          const float s_t = __fmul_rn(__fmul_rn(srow[k], nrm), d.scale);
-          srow[k] = s_t;
-          d.st[row * d.ld_st + k] = s_t;
-          if (n == ch.save_step) d.ring[ch.ring_off + C + k] = s_t;
-        }
-      }
+      RecNormalize(chains, n, w.delay, s_next, p.ld_s, R, d.norm_alpha, d.scale, d.st, d.ld_st, w.ring, C);
       __syncthreads();
     }
   }
 }
 }  // namespace
 
-void LaunchPgru(const PgruDev &d, hipStream_t s) {
-  const int grid = PgruGridX(d.n_utts, d.delay, d.stride);
-  if (grid <= 0) return;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&PgruKernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPgruMaxLdsBytes);
-  if (attr != hipSuccess) Fail(std::string("recurrent block kernel: cannot reserve its LDS: ") + hipGetErrorString(attr));
-  hipLaunchKernelGGL(PgruKernel, dim3((unsigned)grid), dim3(64 * kPgruWaves), (size_t)d.plan.lds_bytes, s, d);
-}
+void LaunchPgru(const PgruDev &d, hipStream_t s) { RecLaunch<PgruDev, PgruKernel>(d, s); }
 
 }  // namespace rs

@@ -26,13 +26,13 @@ PgruLaunchPlan PlanPgru(const PgruBlock &b, const std::string &name) {
   p.n_out = 16 * p.out_tiles;
   p.ld_s = p.k_s + 4;
   p.ld_c = b.proj() ? p.k_c + 4 : 0;
-  p.rows_per_block = kPgruChains;
+  p.rows_per_block = kRecChains;
   // two tiles of s rows (the one a step reads, the one it writes for the next step), the tile of r . s rows and, with a projection,
   // the tile of c rows
-  const long lds = (long)kPgruChains * (3 * p.ld_s + p.ld_c) * (long)sizeof(float);
-  if (lds > kPgruMaxLdsBytes)
-    Fail(what + "the state, product and cell rows of " + std::to_string(kPgruChains) + " chains (cell dim " + std::to_string(b.cell) + ", recurrent dim " +
-         std::to_string(R) + ", " + std::to_string(lds) + " bytes) do not fit the " + std::to_string(kPgruMaxLdsBytes) +
+  const long lds = (long)kRecChains * (3 * p.ld_s + p.ld_c) * (long)sizeof(float);
+  if (lds > kRecMaxLdsBytes)
+    Fail(what + "the state, product and cell rows of " + std::to_string(kRecChains) + " chains (cell dim " + std::to_string(b.cell) + ", recurrent dim " +
+         std::to_string(R) + ", " + std::to_string(lds) + " bytes) do not fit the " + std::to_string(kRecMaxLdsBytes) +
          " bytes of LDS the HIP kernel keeps them in");
   p.lds_bytes = (int)lds;
   return p;
@@ -57,7 +57,7 @@ void PgruWeightImages(const PgruBlock &b, const PgruLaunchPlan &p, std::vector<f
 std::string DescribePgru(const std::string &name, const PgruBlock &b, const PgruLaunchPlan &p) {
   std::ostringstream os;
   os << name << " input=" << b.in_dim << " cell=" << b.cell << " rec=" << b.rec << " nonrec=" << b.nonrec << " delay=" << b.delay << " scale=" << b.scale
-     << " norm=" << (b.norm ? 1 : 0) << " dropout=" << (b.dropout ? 1 : 0) << " kernel=" << (b.composed ? "pgruc" : "pgru") << "16x16x4<w" << kPgruWaves << "> rows_per_block=" << p.rows_per_block
+     << " norm=" << (b.norm ? 1 : 0) << " dropout=" << (b.dropout ? 1 : 0) << " kernel=" << (b.composed ? "pgruc" : "pgru") << "16x16x4<w" << kRecWaves << "> rows_per_block=" << p.rows_per_block
      << " lds=" << p.lds_bytes << " w_zr=" << p.x_cols << "+" << p.s_cols << " cell_tiles=" << p.cell_tiles << " rec_tiles=" << p.rec_tiles
      << " out_tiles=" << p.out_tiles << " grid=chains/" << p.rows_per_block;
   if (b.composed) os << " form=composed";      // (gru-layer / pgru-layer / norm-pgru-layer: walked by nnet_gruc.hip on the same plan)

@@ -8,8 +8,8 @@
 //   y = W_y c + b_y;  s[t] = scale y[0:R]  (norm: scale Normalize(y[0:R]));   without a projection R = cell, s[t] = scale c and
 //   c[t - d] is s[t - d]
 // pre = [W_z,x; W_r,x; W_hpart] x + b has no dependence on time and is one layer GEMM over all rows.  What is serial is walked by
-// this kernel the way nnet_gru.hip walks an OPGRU block (gru_plan.h): a workgroup of kPgruWaves waves owns kPgruChains chains for
-// the whole launch and walks their steps with workgroup barriers only; the grid is the number of chains over kPgruChains.
+// this kernel the way nnet_gru.hip walks an OPGRU block (gru_plan.h): a workgroup of kRecWaves waves owns kRecChains chains for
+// the whole launch and walks their steps with workgroup barriers only; the grid is the number of chains over kRecChains.
 //
 // A step has one phase and one barrier more than the OPGRU block's, because h waits for all of r:
 //   1. r: a wave item is 16 columns of r for the 16 chains, the accumulator starts from pre_r[t] and takes W_r,s s on
@@ -24,7 +24,7 @@
 // the tile, the workgroup or the batch -- a row's result is a function of its inputs alone.
 //
 // LDS: two tiles of s rows, the sdotr tile (pitch k_s + 4 floats each) and, with a projection, the tile of c rows (pitch k_c + 4).
-// Without a projection the three tiles are cell wide: 64 * 3 * (k_c + 4) bytes within kPgruMaxLdsBytes lets k_c be 752 at most.
+// Without a projection the three tiles are cell wide: 64 * 3 * (k_c + 4) bytes within kRecMaxLdsBytes lets k_c be 752 at most.
 //
 // The composed form of the same cell (gru-layer / pgru-layer / norm-pgru-layer, model.h: PgruBlock::composed; W_h is then the
 // recurrent columns of the affine W_h.UW) shares the descriptor, the planner, the weight images and the limits; it is walked by a
@@ -38,9 +38,6 @@
 
 namespace rs {
 
-constexpr int kPgruChains = kLstmChains;            // chains of a workgroup: the rows of one MFMA tile
-constexpr int kPgruWaves = 8;                       // waves of a workgroup
-constexpr int kPgruMaxLdsBytes = kLstmMaxLdsBytes;  // the tiles of one workgroup
 constexpr int kPgruMaxCell = 2048;                  // cell dim
 constexpr int kPgruMaxProj = 4096;                  // recurrent + non-recurrent dim
 
@@ -53,14 +50,11 @@ struct PgruLaunchPlan {
   int n_zh = 0, n_r = 0, n_out = 0;   // column pitch of the transposed weights: 2 * 16 * cell_tiles, 16 * rec_tiles, 16 * out_tiles
   int ld_s = 0, ld_c = 0;          // LDS row pitch of the s / sdotr rows and of the c rows, in floats (k extent + 4); ld_c = 0 without a projection
   int lds_bytes = 0;
-  int rows_per_block = 0;          // kPgruChains
+  int rows_per_block = 0;          // kRecChains
 };
 
 // Fails (rs::Error) with a message naming the block when a dim is beyond the kernel's limits or the LDS tiles do not fit.
 PgruLaunchPlan PlanPgru(const PgruBlock &b, const std::string &name);
-// chains and grid of a launch: those of an LSTM block (lstm_plan.h)
-constexpr int PgruChainsPerUtt(int delay, int stride) { return LstmChainsPerUtt(delay, stride); }
-constexpr int PgruGridX(int n_utts, int delay, int stride) { return LstmGridX(n_utts, delay, stride); }
 // the weights in the kernel's order, zero padded: W_r,s as [k_s][n_r]; W_z,s and W_h as [k_s][n_zh] with z's weight of cell c in
 // column 2 c and h's in column 2 c + 1 (a lane's two weights of a k-step are one 8-byte load); W_y as [k_c][n_out] (empty without a
 // projection)
@@ -78,16 +72,10 @@ struct PgruDev {
   const float *wr_t, *wzh_t, *wy_t, *b_y;      // PgruWeightImages; b_y: rec + nonrec
   int cell, rec, out_dim;                      // rec: R (the cell dim without a projection); out_dim: rec + nonrec, 0 without a projection
   int proj;              // 1: W_y and a state row [c | s]; 0: s = scale c, a state row [s]
-  int delay, stride;
   float scale;
   int norm;              // 1: Normalize in front of the scale
   float norm_alpha;      // 1 / (rec * target_rms^2)
-  // geometry and streams: as LstmDev (lstm_plan.h)
-  int n_utts, L, lext, rext;
-  const int *num_frames, *row_base;
-  const int *t0, *slot;
-  int lext_cont;
-  float *ring;           // [slot][delay][cell + rec], without a projection [slot][delay][cell]
+  RecWalk walk;          // the call's rows and streams (recurrent_walk.h); a parked state row is [c | s], without a projection [s]
   PgruLaunchPlan plan;
 };
 

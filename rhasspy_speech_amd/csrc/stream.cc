@@ -161,7 +161,7 @@ struct StreamPool {
   long long *dec_ctr = nullptr;
   // Recurrent blocks: per kLstm / kGru op (indexed like the network's ops, null elsewhere) and slot, the `delay` state rows [s_c | s_r] the
   // stream's next advance re-enters the block behind -- row (t mod delay) holds the state of the one t in
-  // [ll_done - need_lext - delay, ll_done - need_lext) of that class (lstm_plan.h: LstmDev::ring).  Written by the advance that
+  // [ll_done - need_lext - delay, ll_done - need_lext) of that class (recurrent_walk.h: RecWalk::ring).  Written by the advance that
   // computes those rows, read by the next one; a stream's first advance reads nothing (it starts from zeros), so opening, growing,
   // reclaiming and ending a stream have nothing to do here: the state goes with the slot.
   std::vector<float *> lstm_ring;
@@ -285,19 +285,15 @@ StreamPool *Model::Pool() {
   }
   p->dec_ctr = static_cast<long long *>(dalloc((size_t)p->max_slots * 64));
   p->lstm_ring.assign(nn.ops.size(), nullptr);
-  for (size_t i = 0; i < nn.ops.size(); i++)
-    if (nn.ops[i].kind == LayerOp::kLstm || nn.ops[i].kind == LayerOp::kLstmp) {      // (the composed form parks [sc | sr] the same way)
-      const LstmBlock &k = nn.ops[i].lstm;
-      p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * (k.cell + k.RecDim()) * 4));
-    } else if (nn.ops[i].kind == LayerOp::kLstmb) {    // (the bottleneck form parks [sc | sm]: lstmb_plan.h)
-      p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * nn.ops[i].lstm.delay * 2 * nn.ops[i].lstm.cell * 4));
-    } else if (nn.ops[i].kind == LayerOp::kGru) {      // (a GRU block's rows are [c | s]: gru_plan.h)
-      const GruBlock &k = nn.ops[i].gru;
-      p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * k.StateDim() * 4));
-    } else if (nn.ops[i].kind == LayerOp::kPgru) {     // ([c | s], without a projection [s]: pgru_plan.h)
-      const PgruBlock &k = nn.ops[i].pgru;
-      p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * k.delay * k.StateDim() * 4));
-    }
+  // a recurrent block's ring: [slot][delay][StateDim()], the row width its kernel is given as RecWalk::state_w (Model::RunNnet)
+  for (size_t i = 0; i < nn.ops.size(); i++) {
+    const LayerOp &op = nn.ops[i];
+    size_t row_floats = 0;
+    if (op.kind == LayerOp::kLstm || op.kind == LayerOp::kLstmp || op.kind == LayerOp::kLstmb) row_floats = (size_t)op.lstm.delay * op.lstm.StateDim();
+    else if (op.kind == LayerOp::kGru) row_floats = (size_t)op.gru.delay * op.gru.StateDim();
+    else if (op.kind == LayerOp::kPgru) row_floats = (size_t)op.pgru.delay * op.pgru.StateDim();
+    if (row_floats > 0) p->lstm_ring[i] = static_cast<float *>(dalloc((size_t)p->max_slots * row_floats * 4));
+  }
   if (fc_.ie.present) {
     const int Di = fc_.ie.ivector_dim(), usz = Di * (Di + 1) / 2;
     p->ld_i = RoundUp(Di, 4);

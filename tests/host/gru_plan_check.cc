@@ -52,13 +52,13 @@ int main(int argc, char **argv) {
         Require(p.cell_tiles * 16 >= C && (p.cell_tiles - 1) * 16 < C && p.out_tiles * 16 >= out && (p.out_tiles - 1) * 16 < out, "tiles");
         Require(p.k_s % 16 == 0 && p.k_s >= R && p.k_s < R + 16 && p.k_c % 16 == 0 && p.k_c >= C && p.k_c < C + 16, "k padding");
         Require(p.n_gates == 2 * 16 * p.cell_tiles && p.n_out == 16 * p.out_tiles && p.ld_s > p.k_s && p.ld_c > p.k_c, "pitches");
-        const long lds_floats = (long)rs::kGruChains * (2 * p.ld_s + p.ld_c);
-        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kGruMaxLdsBytes && p.rows_per_block == rs::kGruChains, "LDS size");
+        const long lds_floats = (long)rs::kRecChains * (2 * p.ld_s + p.ld_c);
+        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kRecMaxLdsBytes && p.rows_per_block == rs::kRecChains, "LDS size");
         // the kernel's LDS addresses: tile base + chain * pitch + k
         for (int tile = 0; tile < 3; tile++) {
-          const long base = tile < 2 ? (long)tile * rs::kGruChains * p.ld_s : 2L * rs::kGruChains * p.ld_s;
+          const long base = tile < 2 ? (long)tile * rs::kRecChains * p.ld_s : 2L * rs::kRecChains * p.ld_s;
           const int ld = tile < 2 ? p.ld_s : p.ld_c, kmax = tile < 2 ? p.k_s : p.k_c;
-          for (int c = 0; c < rs::kGruChains; c++) Require(base + (long)c * ld + kmax - 1 < lds_floats, "LDS address outside the planned bytes");
+          for (int c = 0; c < rs::kRecChains; c++) Require(base + (long)c * ld + kmax - 1 < lds_floats, "LDS address outside the planned bytes");
         }
         // the c . o tile's padding columns are written by the cell tiles; the s tiles' padding columns stay at the kernel's zeros
         Require(16 * p.cell_tiles >= p.k_c && 16 * p.out_tiles >= R, "a tile's columns are written");
@@ -84,8 +84,8 @@ int main(int argc, char **argv) {
         // grid: every chain of a call in exactly one workgroup
         for (int utts : {1, 5, 256})
           for (int stride : {1, k.delay})
-            Require(rs::GruGridX(utts, k.delay, stride) * rs::kGruChains >= utts * rs::GruChainsPerUtt(k.delay, stride) &&
-                        (rs::GruGridX(utts, k.delay, stride) - 1) * rs::kGruChains < utts * rs::GruChainsPerUtt(k.delay, stride), "grid");
+            Require(rs::RecGridX(utts, k.delay, stride) * rs::kRecChains >= utts * rs::RecChainsPerUtt(k.delay, stride) &&
+                        (rs::RecGridX(utts, k.delay, stride) - 1) * rs::kRecChains < utts * rs::RecChainsPerUtt(k.delay, stride), "grid");
         std::printf("%s gru: %s\n", name.c_str(), rs::DescribeGru(op.name, k, p).c_str());
       }
       if (blocks == 0) std::printf("%s no recurrent block\n", name.c_str());

@@ -50,13 +50,13 @@ int main(int argc, char **argv) {
         Require(k.proj() ? (p.out_tiles * 16 >= k.rec + k.nonrec && (p.out_tiles - 1) * 16 < k.rec + k.nonrec) : p.out_tiles == 0, "projection tiles");
         Require(p.k_r % 16 == 0 && p.k_r >= p.r_cols && p.k_r < p.r_cols + 16 && p.k_m % 16 == 0 && p.k_m >= k.cell && p.k_m < k.cell + 16, "k padding");
         Require(p.n_gates == 4 * 16 * p.cell_tiles && p.n_out == 16 * p.out_tiles && p.ld_r > p.k_r && p.ld_m > p.k_m, "pitches");
-        const long lds_floats = (long)rs::kLstmChains * (2 * p.ld_r + (k.proj() ? p.ld_m : 0));
-        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kLstmMaxLdsBytes && p.rows_per_block == rs::kLstmChains, "LDS size");
+        const long lds_floats = (long)rs::kRecChains * (2 * p.ld_r + (k.proj() ? p.ld_m : 0));
+        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kRecMaxLdsBytes && p.rows_per_block == rs::kRecChains, "LDS size");
         // the kernel's LDS addresses: tile base + chain * pitch + k
         for (int tile = 0; tile < (k.proj() ? 3 : 2); tile++) {
-          const long base = tile < 2 ? (long)tile * rs::kLstmChains * p.ld_r : 2L * rs::kLstmChains * p.ld_r;
+          const long base = tile < 2 ? (long)tile * rs::kRecChains * p.ld_r : 2L * rs::kRecChains * p.ld_r;
           const int ld = tile < 2 ? p.ld_r : p.ld_m, kmax = tile < 2 ? p.k_r : p.k_m;
-          for (int c = 0; c < rs::kLstmChains; c++) Require(base + (long)c * ld + kmax - 1 < lds_floats, "LDS address outside the planned bytes");
+          for (int c = 0; c < rs::kRecChains; c++) Require(base + (long)c * ld + kmax - 1 < lds_floats, "LDS address outside the planned bytes");
         }
         // the tiles the waves write cover the k extents the next product reads (16 cell_tiles >= k_m, and k_r without a projection)
         Require(16 * p.cell_tiles >= p.k_m && (k.proj() || 16 * p.cell_tiles >= p.k_r), "a tile's padding columns are written");
@@ -83,8 +83,8 @@ int main(int argc, char **argv) {
         // grid: every chain of a call in exactly one workgroup
         for (int utts : {1, 5, 256})
           for (int stride : {1, k.delay})
-            Require(rs::LstmGridX(utts, k.delay, stride) * rs::kLstmChains >= utts * rs::LstmChainsPerUtt(k.delay, stride) &&
-                        (rs::LstmGridX(utts, k.delay, stride) - 1) * rs::kLstmChains < utts * rs::LstmChainsPerUtt(k.delay, stride), "grid");
+            Require(rs::RecGridX(utts, k.delay, stride) * rs::kRecChains >= utts * rs::RecChainsPerUtt(k.delay, stride) &&
+                        (rs::RecGridX(utts, k.delay, stride) - 1) * rs::kRecChains < utts * rs::RecChainsPerUtt(k.delay, stride), "grid");
         std::printf("%s lstm: %s\n", name.c_str(), rs::DescribeLstm(op.name, k, p).c_str());
       }
       if (blocks == 0) std::printf("%s no recurrent block\n", name.c_str());

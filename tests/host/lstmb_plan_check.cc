@@ -65,9 +65,9 @@ int main(int argc, char **argv) {
         }
         Require(p.cell_tiles == (C + 15) / 16 && p.b_tiles == (B + 15) / 16 && p.k_m == 16 * p.cell_tiles && p.k_b == 16 * p.b_tiles &&
                     p.n_b == p.k_b && p.n_gates == 4 * p.k_m && p.ld_m == p.k_m + 4 && p.ld_b == p.k_b + 4, "tiles and k extents");
-        const long lds_floats = (long)rs::kLstmbChains * (p.ld_m + p.ld_b);
-        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kLstmbMaxLdsBytes && p.rows_per_block == rs::kLstmbChains, "LDS size");
-        Require(rs::LstmGridX(256, k.delay, 1) == (256 * k.delay + 15) / 16, "the grid");
+        const long lds_floats = (long)rs::kRecChains * (p.ld_m + p.ld_b);
+        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kRecMaxLdsBytes && p.rows_per_block == rs::kRecChains, "LDS size");
+        Require(rs::RecGridX(256, k.delay, 1) == (256 * k.delay + 15) / 16, "the grid");
         std::vector<float> wam_t, wb_t;
         rs::LstmbWeightImages(k, p, &wam_t, &wb_t);
         Require((long)wam_t.size() == (long)p.k_m * p.n_b && (long)wb_t.size() == (long)p.k_b * p.n_gates, "image sizes");

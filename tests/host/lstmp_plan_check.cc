@@ -50,8 +50,8 @@ int main(int argc, char **argv) {
           const rs::BufferInfo &bi = nn.bufs[bufs[b]], &b0 = nn.bufs[k.pre_buf];
           Require(bi.dim == dims[b] && bi.lext == b0.lext && bi.rext == b0.rext && bi.stride == b0.stride, "the block's buffers hold the same rows");
         }
-        const long lds_floats = (long)rs::kLstmChains * (2 * p.ld_r + (k.proj() ? p.ld_m : 0));
-        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kLstmMaxLdsBytes && p.rows_per_block == rs::kLstmChains, "LDS size");
+        const long lds_floats = (long)rs::kRecChains * (2 * p.ld_r + (k.proj() ? p.ld_m : 0));
+        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kRecMaxLdsBytes && p.rows_per_block == rs::kRecChains, "LDS size");
         Require(16 * p.cell_tiles >= p.k_m && (k.proj() || 16 * p.cell_tiles >= p.k_r), "a tile's padding columns are written");
         std::vector<float> wr_t, wrp_t;
         rs::LstmWeightImages(k, p, &wr_t, &wrp_t);

@@ -64,13 +64,13 @@ int main(int argc, char **argv) {
         Require(p.k_s == 16 * p.rec_tiles && p.k_c == 16 * p.cell_tiles && (proj || p.k_s == p.k_c), "k padding");
         Require(p.n_zh == 2 * 16 * p.cell_tiles && p.n_r == 16 * p.rec_tiles && p.n_out == 16 * p.out_tiles && p.ld_s > p.k_s && (proj ? p.ld_c > p.k_c : p.ld_c == 0),
                 "pitches");
-        const long lds_floats = (long)rs::kPgruChains * (3 * p.ld_s + p.ld_c);
-        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kPgruMaxLdsBytes && p.rows_per_block == rs::kPgruChains, "LDS size");
+        const long lds_floats = (long)rs::kRecChains * (3 * p.ld_s + p.ld_c);
+        Require(p.lds_bytes == lds_floats * 4 && p.lds_bytes <= rs::kRecMaxLdsBytes && p.rows_per_block == rs::kRecChains, "LDS size");
         // the kernel's LDS addresses: tile base + chain * pitch + k; the widest column a phase writes is 16 * tiles - 1
         for (int tile = 0; tile < (proj ? 4 : 3); tile++) {
-          const long base = (long)tile * rs::kPgruChains * p.ld_s;
+          const long base = (long)tile * rs::kRecChains * p.ld_s;
           const int ld = tile < 3 ? p.ld_s : p.ld_c, kmax = tile < 3 ? p.k_s : p.k_c;
-          for (int c = 0; c < rs::kPgruChains; c++) Require(base + (long)c * ld + kmax - 1 < lds_floats, "LDS address outside the planned bytes");
+          for (int c = 0; c < rs::kRecChains; c++) Require(base + (long)c * ld + kmax - 1 < lds_floats, "LDS address outside the planned bytes");
         }
         Require(16 * p.rec_tiles <= p.k_s && 16 * p.cell_tiles <= p.k_c && (proj || 16 * p.cell_tiles <= p.k_s), "a phase writes outside its tile's k extent");
         std::vector<float> wr_t, wzh_t, wy_t;
@@ -94,8 +94,8 @@ int main(int argc, char **argv) {
         // grid: every chain of a call in exactly one workgroup
         for (int utts : {1, 5, 256})
           for (int stride : {1, k.delay})
-            Require(rs::PgruGridX(utts, k.delay, stride) * rs::kPgruChains >= utts * rs::PgruChainsPerUtt(k.delay, stride) &&
-                        (rs::PgruGridX(utts, k.delay, stride) - 1) * rs::kPgruChains < utts * rs::PgruChainsPerUtt(k.delay, stride), "grid");
+            Require(rs::RecGridX(utts, k.delay, stride) * rs::kRecChains >= utts * rs::RecChainsPerUtt(k.delay, stride) &&
+                        (rs::RecGridX(utts, k.delay, stride) - 1) * rs::kRecChains < utts * rs::RecChainsPerUtt(k.delay, stride), "grid");
         std::printf("%s pgru: %s\n", name.c_str(), rs::DescribePgru(op.name, k, p).c_str());
       }
       if (blocks == 0) std::printf("%s no recurrent block\n", name.c_str());
