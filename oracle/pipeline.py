@@ -666,6 +666,34 @@ class Nnet3:
                 nrm = (x * x).sum(1, dtype=F32) / F32(x.shape[1] * rms * rms)
                 nrm = np.power(np.maximum(nrm, F32(1.3552527156068805425e-20)), F32(-0.5))
                 out = (x * nrm[:, None]).astype(F32)
+            elif c.type == "FixedScaleComponent":
+                # nnet-simple-component.cc:3689-3695: CopyFromMat, MulColsVec(scales_)
+                out = (x * np.asarray(f["<Scales>"], F32)[None, :]).astype(F32)
+            elif c.type in ("PerElementScaleComponent", "NaturalGradientPerElementScaleComponent"):
+                # :2032-2039 (the natural-gradient class inherits it): CopyFromMat, MulColsVec(scales_)
+                out = (x * np.asarray(f["<Params>"], F32)[None, :]).astype(F32)
+            elif c.type == "FixedBiasComponent":
+                # :3764-3770: CopyFromMat, AddVecToRows(1.0, bias_)
+                out = (x + np.asarray(f["<Bias>"], F32)[None, :]).astype(F32)
+            elif c.type == "PerElementOffsetComponent":
+                # :2203-2220: AddVecToRows(1.0, offsets_); where dim_ is a multiple of the vector's length, on the rows re-read as
+                # dim_ / length times as many rows of that length: the vector repeats along the row
+                off = np.asarray(f["<Offsets>"], F32)
+                assert x.shape[1] % off.shape[0] == 0 and int(f.get("<Dim>", off.shape[0])) == x.shape[1]
+                out = (x + np.tile(off, x.shape[1] // off.shape[0])[None, :]).astype(F32)
+            elif c.type == "ScaleAndOffsetComponent":
+                # :2453-2485: the same re-reading for the block form; PropagateInternal: cu::EnsureNonzero(scales_, 1e-4) (cu-math.cc:
+                # 226-238: s where s <= -e or s >= e, else e where s >= 0, else -e), MulColsVec, AddVecToRows -- two roundings
+                s, off = np.asarray(f["<Scales>"], F32), np.asarray(f["<Offsets>"], F32)
+                e = F32(1.0e-4)
+                s = np.where((s <= -e) | (s >= e), s, np.where(s >= F32(0.0), e, -e)).astype(F32)
+                assert x.shape[1] % s.shape[0] == 0 and int(f["<Dim>"]) == x.shape[1]
+                rep = x.shape[1] // s.shape[0]
+                out = ((x * np.tile(s, rep)[None, :]).astype(F32) + np.tile(off, rep)[None, :]).astype(F32)
+            elif c.type == "BackpropTruncationComponent":
+                # nnet-general-component.cc:1094-1102: CopyFromMat, then Scale(scale_) unless it is 1
+                scale = F32(f.get("<Scale>", 1.0))
+                out = x if scale == F32(1.0) else (x * scale).astype(F32)
             else:
                 raise ValueError(f"oracle: unsupported component {c.type}")
         else:

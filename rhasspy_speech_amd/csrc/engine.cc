@@ -269,6 +269,11 @@ Model::Model(const std::string &final_mdl, const std::string &hclg, const std::s
     if ((int)op.stages.size() > kMaxStages) Fail("nnet3: layer " + op.name + " has too many fused stages");
     if (op.kind == LayerOp::kEltwise && op.terms.size() > 8) Fail("nnet3: layer " + op.name + " sums too many terms");
     if (op.kind == LayerOp::kGather && op.terms.size() > 8) Fail("nnet3: layer " + op.name + " gathers from too many Append() parts");
+    // a row-wise stage stands alone in an elementwise op over one unscaled source (Nnet::Compile keeps it so; RunNnet relies on it)
+    for (auto &st : op.stages)
+      if ((st.kind == EltStage::kLogSoftmax || st.kind == EltStage::kNormalize) &&
+          (op.kind != LayerOp::kEltwise || op.stages.size() != 1 || op.terms.size() != 1 || op.terms[0].scale != 1.0f))
+        Fail("nnet3: row-wise component in a fused position is not supported: " + op.name);
   }
   // which convolution kernel runs each convolution, on what tile and with how much LDS: decided here, so that a geometry the
   // kernels do not cover fails the load (conv_plan.h)
@@ -1585,9 +1590,7 @@ void Model::RunNnet(const std::vector<float *> &bufp, const std::vector<int> &bu
       d.dim = op.out_dim; d.out = bufp[op.out_buf]; d.ldo = buf_ld[op.out_buf];
       int ns = 0;
       for (auto &st : op.stages) {
-        if (st.kind == EltStage::kLogSoftmax || st.kind == EltStage::kNormalize) {
-          if (op.stages.size() != 1 || op.terms.size() != 1 || op.terms[0].scale != 1.0f)
-            Fail("nnet3: row-wise component in a fused position is not supported: " + op.name);
+        if (st.kind == EltStage::kLogSoftmax || st.kind == EltStage::kNormalize) {      // (alone over one unscaled source: checked at load)
           d.row_reduce = st.kind == EltStage::kLogSoftmax ? 2 : 3;
           d.alpha = st.alpha;
         } else {

@@ -1136,10 +1136,10 @@ bool EltStagesFor(const Component &c, const std::string &name, std::vector<EltSt
     return true;
   }
   if (c.type == "NormalizeComponent") {
-    if (c.f.count("<AddLogStddev>") && c.f.at("<AddLogStddev>")[0] != 0.0) Fail("nnet3: NormalizeComponent add-log-stddev=true is not supported");
+    if (c.f.count("<AddLogStddev>") && c.f.at("<AddLogStddev>")[0] != 0.0) Fail("nnet3: NormalizeComponent add-log-stddev=true is not supported (node " + name + ")");
     if (c.f.count("<BlockDim>")) {
       int d = c.i.count("<InputDim>") ? c.Int("<InputDim>") : c.Int("<Dim>");
-      if (c.Int("<BlockDim>") != d) Fail("nnet3: NormalizeComponent with block-dim is not supported");
+      if (c.Int("<BlockDim>") != d) Fail("nnet3: NormalizeComponent with block-dim is not supported (node " + name + ")");
     }
     EltStage s;
     s.kind = EltStage::kNormalize;
@@ -2062,6 +2062,16 @@ void FindBlocks(const Nnet &net, int out_node, std::vector<BlockNodes> *blocks, 
       Fail("nnet3: Const() in the input of node " + nodes[n].name + " is supported only as the Sum(Scale(-1.0, z_t), Const(1.0, cell-dim)) of a gru-layer / pgru-layer / "
            "norm-pgru-layer / opgru-layer / norm-opgru-layer block");
   }
+  // IfDefined() outside a cycle: the reference leaves the term out of the network's context and fills the rows it then cannot compute
+  // (the first frames of an utterance for Offset(x, -2)) with zeros; the feed-forward lowering has no optional inputs
+  for (int n = 0; n < N; n++) {
+    if (index[n] < 0 || (*block_of)[n] >= 0) continue;
+    for (auto &p : nodes[n].input.parts)
+      for (auto &t : p.terms)
+        if (t.optional)
+          Fail("nnet3: IfDefined() in the input of node " + nodes[n].name + " (over " + nodes[t.node].name + ") is supported only as the recurrent connection of a "
+               "recurrent block: outside a cycle the reference zero-fills the rows it cannot compute, which the feed-forward path does not do");
+  }
   // a block whose feed-forward input reads another block's state at a future time would need that block's rows before they exist
   for (const BlockNodes &b : *blocks)
     for (auto &p : b.x_parts)
@@ -2237,10 +2247,14 @@ void Nnet::Compile() {
   auto add_gemm_segs = [&](LayerOp *op, const std::vector<DescPart> &parts, int n, const std::vector<int> &toffs) {
     const NnetNode &nd = nodes[n];
     int wcol = 0;
+    std::vector<int> sum_buf(parts.size(), -1);      // a materialised part's buffer: made once, read at every time offset
     for (int o2 : toffs) {
       for (auto &p : parts) {
         int sbuf, scol, soff;
-        if (p.terms.size() == 1 && p.terms[0].scale == 1.0f) {
+        int &made = sum_buf[&p - &parts[0]];
+        if (made >= 0) {
+          sbuf = made; scol = 0; soff = 0;
+        } else if (p.terms.size() == 1 && p.terms[0].scale == 1.0f) {
           const DescTerm &t = p.terms[0];
           term_src(t, &sbuf, &scol);
           soff = t.const_t ? 0 : t.offset;
@@ -2262,7 +2276,7 @@ void Nnet::Compile() {
             sop.terms.push_back({b, c, t.offset, t.scale});
           }
           ops.push_back(sop);
-          sbuf = sop.out_buf; scol = 0; soff = 0;
+          sbuf = made = sop.out_buf; scol = 0; soff = 0;
         }
         GemmSegment sg;
         sg.src_buf = sbuf; sg.src_col = scol; sg.ncols = p.dim; sg.offset = soff + (sbuf == -1 ? 0 : o2); sg.w_col = wcol;
@@ -2626,6 +2640,10 @@ void Nnet::Compile() {
         // a row-wise reduction can only be fused when the op's tile covers the whole row; keep those standalone
         for (auto &s : stages) if (s.kind == EltStage::kLogSoftmax || s.kind == EltStage::kNormalize) ok = false;
         if (op.kind == LayerOp::kGather || op.kind == LayerOp::kAttention) ok = false;      // (a column gather and the attention kernel have no epilogue)
+        // ... and nothing follows a row-wise stage inside its op (the row kernel applies that stage alone): relu or batchnorm behind a
+        // NormalizeComponent, relu-renorm-layer's neighbour in the next layer, is an op of its own reading the normalised buffer
+        // (a node without a stage -- NoOp, dropout, the output-node -- still joins it: a name for the same rows)
+        for (auto &s : op.stages) if (!stages.empty() && (s.kind == EltStage::kLogSoftmax || s.kind == EltStage::kNormalize)) ok = false;
         if (ok) {
           op.stages.insert(op.stages.end(), stages.begin(), stages.end());
           op.name += "+" + nd.name;
@@ -2717,10 +2735,23 @@ void Nnet::Compile() {
       for (auto &t : nd.input.parts[0].terms) {
         int b, c;
         term_src(t, &b, &c);
-        if (b == -2 || t.const_t) Fail("nnet3: elementwise component over the iVector input is not supported");
+        if (b == -2 || t.const_t) Fail("nnet3: elementwise component over the iVector input is not supported (node " + nd.name + ")");
         op.terms.push_back({b, c, t.offset, t.scale});
       }
       op.stages = stages;
+      bool row_wise = false;
+      for (auto &s : stages) if (s.kind == EltStage::kLogSoftmax || s.kind == EltStage::kNormalize) row_wise = true;
+      if (row_wise && (op.terms.size() != 1 || op.terms[0].scale != 1.0f)) {
+        // the row kernel reads one unscaled source: a Sum() or Scale() in front of it is materialised first, as add_gemm_segs does
+        LayerOp sop;
+        sop.kind = LayerOp::kEltwise;
+        sop.name = nd.name + ".sum";
+        sop.out_dim = nd.dim;
+        sop.terms = op.terms;
+        sop.out_buf = new_buf(nd.dim, lext[n], rext[n]);
+        ops.push_back(sop);
+        op.terms.assign(1, SumTerm{sop.out_buf, 0, 0, 1.0f});
+      }
       if (nd.kind == NnetNode::kOutput && op.terms.size() == 1 && op.terms[0].offset == 0 && op.terms[0].scale == 1.0f &&
           op.terms[0].src_col == 0 && bufs[op.terms[0].src_buf].dim == nd.dim && op.stages.empty()) {
         // output-node that simply names a buffer: alias it

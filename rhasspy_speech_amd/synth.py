@@ -1410,11 +1410,14 @@ def build_nnet(spec: ModelSpec, rng: np.random.Generator):
     return cfg, comps
 
 
-def write_final_mdl(path: Path, spec: ModelSpec) -> None:
+def write_final_mdl(path: Path, spec: ModelSpec, nnet=None) -> None:
+    """nnet: None for the network of build_nnet(spec), or (config lines, [(component name, writer_fn)]) of a network written by
+    hand: its input-node dims are spec.feat_dim and spec.ivector_dim, its output dim spec.num_pdfs; transition model, priors,
+    extractor, tree and graph are the spec's either way."""
     rng = np.random.default_rng(spec.seed)
     w = KaldiWriter(spec.binary)
     _write_transition_model(w, spec)
-    cfg, comps = build_nnet(spec, rng)
+    cfg, comps = build_nnet(spec, rng) if nnet is None else nnet
     w.token("<Nnet3>").raw(b"\n")
     w.raw(("\n".join(cfg) + "\n\n").encode())
     w.token("<NumComponents>").i32(len(comps)).nl()
@@ -1491,10 +1494,10 @@ def write_ivector_extractor(ie_dir: Path, spec: ModelSpec) -> None:
     (ie_dir / "final.ie").write_bytes(w.getvalue())
 
 
-def write_model_dir(model_dir: Path, spec: ModelSpec) -> None:
-    """Writes <model_dir>/model/{model,online} in the layout of SURVEY.md §3.4."""
+def write_model_dir(model_dir: Path, spec: ModelSpec, nnet=None) -> None:
+    """Writes <model_dir>/model/{model,online} in the layout of SURVEY.md §3.4.  nnet: as write_final_mdl's."""
     model_dir = Path(model_dir).absolute()
-    write_final_mdl(model_dir / "model" / "model" / "final.mdl", spec)
+    write_final_mdl(model_dir / "model" / "model" / "final.mdl", spec, nnet)
     write_tree(model_dir / "model" / "model" / "tree", spec)
     conf = model_dir / "model" / "online" / "conf"
     conf.mkdir(parents=True, exist_ok=True)
