@@ -221,11 +221,16 @@ int rs_model_describe(const rs_model *model, char *buf, size_t len);
  * online2-wav-nnet3-latgen-faster shim do).  --allow-downsample / --allow-upsample in mfcc.conf / fbank.conf (the reference then resamples) are
  * refused with a message: the library does not resample. */
 int rs_model_check_sample_rate(const rs_model *model, float sample_rate);
+/* *out = the model's --sample-frequency (mfcc.conf / fbank.conf; 16000 without the line).  Every PCM entry point -- rs_decode_batch*,
+ * rs_stream_accept* -- takes samples AT THAT RATE and never sees a rate: 8 kHz telephone models (a 200-sample window, a 256-point
+ * transform) take 8 kHz audio, and so on.  Windows that pad to 256, 512, 1024 or 2048 points load; a caller whose audio carries a
+ * rate (a wav header, the stream binary's --samp-freq) compares it with rs_model_check_sample_rate before handing samples over. */
+int rs_model_sample_rate(const rs_model *model, float *out);
 
 /* Offline batch decode = N invocations of the reference's 3-process pipeline with --online=false
  * (online2-wav-nnet3-latgen-faster.cc:196-300 + lattice-to-nbest.cc:80-110 + nbest-to-linear.cc:67-87).
- * pcm[i] points to n_samples[i] mono 16 kHz int16 samples (WaveData::Read hands Kaldi the same values as
- * floats, unscaled).  nbest = lattice-to-nbest --n; lattice_acoustic_scale = its --acoustic-scale. */
+ * pcm[i] points to n_samples[i] mono int16 samples at the model's rate (rs_model_sample_rate; WaveData::Read hands Kaldi the same
+ * values as floats, unscaled).  nbest = lattice-to-nbest --n; lattice_acoustic_scale = its --acoustic-scale. */
 int rs_decode_batch(rs_model *model, const int16_t *const *pcm, const int32_t *n_samples, int32_t n_utts,
                     int32_t nbest, float lattice_acoustic_scale, rs_result **out);
 /* Same with the samples already resident in device memory (HBM): d_pcm is one device buffer holding all
@@ -235,7 +240,8 @@ int rs_decode_batch_device(rs_model *model, const int16_t *d_pcm, const int64_t 
                            int32_t n_utts, int32_t nbest, float lattice_acoustic_scale, void *stream,
                            rs_result **out);
 
-/* Streaming decode = online2-cli-nnet3-decode-faster (stdin s16le until EOF, :143-161) followed by
+/* Streaming decode = online2-cli-nnet3-decode-faster (stdin s16le at the model's rate until EOF, :143-161; its --samp-freq is
+ * the caller's to check, rs_model_check_sample_rate) followed by
  * lattice-to-nbest | nbest-to-linear (transcribe_stream.py:85-99).  Audio may arrive in arbitrary chunk
  * sizes; the library re-chunks to the binary's fixed 1024-sample ticks (:37) so results do not depend on
  * the caller's chunking, exactly like the reference. */

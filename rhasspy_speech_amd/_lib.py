@@ -61,7 +61,7 @@ FIXED_ONLINE, FIXED_DO_ENDPOINTING, FIXED_EXTRA_LEFT_CONTEXT_INITIAL, FIXED_PRUN
 
 EXPORTS = [
     "rs_default_opts", "rs_last_error", "rs_model_load_files", "rs_model_load", "rs_model_to_device", "rs_model_free",
-    "rs_model_describe", "rs_model_check_sample_rate", "rs_decode_batch", "rs_decode_batch_device", "rs_decode_batch_sharded", "rs_shard_gather", "rs_stream_open", "rs_stream_accept",
+    "rs_model_describe", "rs_model_check_sample_rate", "rs_model_sample_rate", "rs_decode_batch", "rs_decode_batch_device", "rs_decode_batch_sharded", "rs_shard_gather", "rs_stream_open", "rs_stream_accept",
     "rs_stream_finish", "rs_stream_free", "rs_streams_accept", "rs_streams_advance", "rs_streams_finish",
     "rs_streams_partial", "rs_stream_partial",
     "rs_default_endpoint_opts", "rs_model_endpoint_opts", "rs_endpoint_rule_fired", "rs_streams_endpoint", "rs_stream_endpoint",
@@ -93,6 +93,7 @@ def load_library() -> C.CDLL:
     lib.rs_model_free.restype = None
     lib.rs_model_describe.argtypes = [vp, C.c_char_p, C.c_size_t]
     lib.rs_model_check_sample_rate.argtypes = [vp, f32]
+    lib.rs_model_sample_rate.argtypes = [vp, C.POINTER(f32)]
     lib.rs_decode_batch.argtypes = [vp, C.POINTER(C.POINTER(C.c_int16)), C.POINTER(i32), i32, i32, f32, C.POINTER(vp)]
     lib.rs_decode_batch_device.argtypes = [vp, vp, C.POINTER(C.c_int64), i32, i32, f32, vp, C.POINTER(vp)]
     lib.rs_decode_batch_sharded.argtypes = [C.POINTER(vp), i32, C.POINTER(i32), C.POINTER(C.POINTER(C.c_int16)), C.POINTER(i32), i32, i32, i32, vp,
@@ -355,6 +356,13 @@ class Model:
     def check_sample_rate(self, sample_rate: float) -> None:
         """Raises RsError with Kaldi's "Sampling frequency mismatch ..." unless `sample_rate` is the model's --sample-frequency."""
         _check(lib().rs_model_check_sample_rate(self._h, float(sample_rate)))
+
+    @property
+    def sample_rate(self) -> float:
+        """rs_model_sample_rate: the model's --sample-frequency, the rate of the PCM every decode and stream call takes."""
+        out = C.c_float()
+        _check(lib().rs_model_sample_rate(self._h, C.byref(out)))
+        return float(out.value)
 
     def decode_batch(self, pcm: Sequence[np.ndarray], nbest: int = 1, lattice_acoustic_scale: float = 1.0) -> Result:
         n = len(pcm)

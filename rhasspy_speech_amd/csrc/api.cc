@@ -140,6 +140,11 @@ int rs_model_describe(const rs_model *model, char *buf, size_t len) {
   return (int)d.size();
 }
 
+int rs_model_sample_rate(const rs_model *model, float *out) {
+  if (!model || !out) return ArgError("rs_model_sample_rate: bad argument");
+  return Guard([&]() { *out = model->m->features().mfcc.opts.samp_freq; return RS_OK; });
+}
+
 // OnlineGenericBaseFeature<C>::MaybeCreateResampler (feat/online-feature.cc:86-101)
 int rs_model_check_sample_rate(const rs_model *model, float sample_rate) {
   if (!model) return ArgError("rs_model_check_sample_rate: null model");

@@ -668,11 +668,12 @@ void Model::ToDevice() {
     mfcc_dev_.fft_perm = Upload(pl_perm_swz);
     mfcc_dev_.fft_kn = Upload(pl.kn);
     mfcc_dev_.fft_post = nullptr;
-    if (t.padded == 512) {
-      std::vector<float> post(2 * 64 * 4, 0.f);
-      for (int q = 0; q < 2; q++)
+    if (t.padded == 512 || t.padded == 256) {      // (the kernel's fast path: k = 1 .. padded / 4 in rounds of 64 lanes)
+      const int NC = t.padded / 2, rounds = NC / 128;
+      std::vector<float> post((size_t)rounds * 64 * 4, 0.f);
+      for (int q = 0; q < rounds; q++)
         for (int lane = 0; lane < 64; lane++) {
-          const int k = lane + 1 + 64 * q, pk = pl_perm_swz[k], pd = pl_perm_swz[256 - k];
+          const int k = lane + 1 + 64 * q, pk = pl_perm_swz[k], pd = pl_perm_swz[NC - k];
           float *r = &post[(size_t)(q * 64 + lane) * 4];
           std::memcpy(r, &pk, 4); std::memcpy(r + 1, &pd, 4);
           r[2] = pl.kn[2 * k]; r[3] = pl.kn[2 * k + 1];
@@ -1101,7 +1102,9 @@ std::unique_ptr<Result> Model::DecodeBatchHost(const int16_t *const *pcm, const 
   std::unique_ptr<Result> res;
   try {
     RS_HIP(hipSetDevice(opts_.device_id));
-    size_t total = (size_t)off[n_utts] + 512;
+    // (the slack behind the last sample: the halo rows of an utterance too short for one frame read a whole window from its first
+    // sample -- 400 samples at 16 kHz, 1200 at 48 kHz)
+    size_t total = (size_t)off[n_utts] + std::max(512, fc_.mfcc.win);
     if (total > cx->h_pcm_cap) {
       if (cx->h_pcm_pinned) RS_HIP(hipHostFree(cx->h_pcm_pinned));
       if (cx->d_pcm) RS_HIP(hipFree(cx->d_pcm));

@@ -231,6 +231,12 @@ static void LaunchFeatureKernel(const MfccDev &m, const FbankDev *f, const Batch
     else if (shape == 8 && tab_ok) LaunchMfccT<FBANK, 512, 8, true>(m, f, g, pcm, feats, ld, false, out_rows, s);
     else if (shape == 17) LaunchMfccT<FBANK, 512, 16>(m, f, g, pcm, feats, ld, false, out_rows, s);
     else LaunchMfccT<FBANK, 512, 4>(m, f, g, pcm, feats, ld, false, out_rows, s);
+  } else if (m.padded == 256) {
+    // An 8 kHz model's window: 128 complex points, the record-driven levels with half the lanes at work, one round of the
+    // post-processing pass.  The 4-wave form only (DESIGN.md section 5 has its time per frame beside the 512-point window's).
+    LaunchMfccT<FBANK, 256, 4>(m, f, g, pcm, feats, ld, exclusive, out_rows, s);
+  } else if (m.padded == 1024) {
+    LaunchMfccT<FBANK, 1024, 4>(m, f, g, pcm, feats, ld, exclusive, out_rows, s);
   } else {
     LaunchMfccT<FBANK, 2048, 4>(m, f, g, pcm, feats, ld, exclusive, out_rows, s);
   }

@@ -51,7 +51,8 @@ __global__ __launch_bounds__(64 * WPB) void MfccKernel(MfccDev m, BatchGeom g, c
   // lifter in front of the FFT, whose seven LDS round trips cover them.
   // The kernel is a chain of ~20 dependent trips to L2 per frame, and eight waves per SIMD -- all it can hold -- do not hide them
   // (its LDS pipe is half busy since the swizzle, its vector ALU 63 %: profiles/micro/pmc_lds.sh, pmc_inst.sh; round 6).
-  constexpr bool kFast = NFFT == 512;
+  constexpr bool kFast = NFFT == 512 || NFFT == 256;      // one pre-addressed record per lane and level, fft_post rounds of 64 lanes
+  constexpr int kPostRounds = NFFT / 256;                 // k = 1 .. NFFT / 4 of the post-processing pass: two rounds at 512, one at 256
   float4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0;
   const bool recs_on = kFast && m.fft_recs != nullptr;
   if (recs_on && !TAB) {
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(64 * WPB) void MfccKernel(MfccDev m, BatchGeom g, c
   float pp_re[2] = {0.f, 0.f}, pp_im[2] = {0.f, 0.f};
   if (kFast) {
 #pragma unroll
-    for (int q = 0; q < 2; q++) {
+    for (int q = 0; q < kPostRounds; q++) {
       const int k = lane + 1 + RS_WAVE * q;          // (2 k <= NFFT / 2 for both)
       (void)k;
       const float4 pr = m.fft_post[q * RS_WAVE + lane];      // (one request instead of four: the kernel is bound by the NUMBER of its vector memory requests)
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(64 * WPB) void MfccKernel(MfccDev m, BatchGeom g, c
   const float lift = m.lifter[clane];
 #endif
   // 3. split-radix complex FFT, level by level (tasks of one level touch disjoint points)
-  if (NFFT == 512 && m.fft_recs) {
+  if (kFast && m.fft_recs) {
     // at most one task per lane and level: the record of the NEXT level (task + its twiddle factors, three 16-byte loads of one
     // 48-byte record) is requested before the current level runs, so no level waits for a global round trip -- the task-then-twiddles
     // pair of dependent loads per level was 14 of the frame's ~45 (profiles/r04/mfcc_notes.txt).  Round 6: 64 records per level (a
@@ -253,7 +254,7 @@ __global__ __launch_bounds__(64 * WPB) void MfccKernel(MfccDev m, BatchGeom g, c
     };
     if (kFast) {
 #pragma unroll
-      for (int q = 0; q < 2; q++) post(lane + 1 + RS_WAVE * q, pp_k[q], pp_d[q], pp_re[q], pp_im[q]);
+      for (int q = 0; q < kPostRounds; q++) post(lane + 1 + RS_WAVE * q, pp_k[q], pp_d[q], pp_re[q], pp_im[q]);
     } else {
       for (int k = lane + 1; 2 * k <= NC; k += RS_WAVE) post(k, m.fft_perm[k], m.fft_perm[NC - k], m.fft_kn[2 * k], m.fft_kn[2 * k + 1]);
     }

@@ -54,7 +54,7 @@ struct MfccDev {
   int fft_level_begin[16];   // task range of each level
   const float *fft_tw;       // 6 floats per twiddled butterfly
   // the same plan as 64 48-byte records per level, one per lane {byte offsets of the task's points in xr / xi; kind (3: no task) |
-  // twiddle class << 8, the task's six twiddle factors; -} when no level has more than 64 tasks (a 512-point window): a lane's
+  // twiddle class << 8, the task's six twiddle factors; -} when no level has more than 64 tasks (512- and 256-point windows): a lane's
   // record of the NEXT level is requested while the current one runs, at a fixed offset from the level's base, and the factors come
   // with it instead of by a second, dependent load (null: plans with wider levels).  With it the points live in a bank-conflict-
   // reducing layout: point i at index i ^ g(i >> 5), g(b) = fft_swz[0] (bit 0 of b) ^ fft_swz[1] (bit 1) ^ fft_swz[2] (bit 2);
@@ -63,9 +63,10 @@ struct MfccDev {
   const float4 *fft_recs;
   const int *fft_perm;       // padded/2: bit-reversal pass as a gather
   const float *fft_kn;       // (re, im) of the post-processing factor, k = 0 .. padded/4
-  // (512-point window) the same two tables as one 16-byte record per lane and round of the post-processing pass, k = lane + 1 + 64 q:
-  // {fft_perm[k], fft_perm[256 - k], kn re, kn im} -- one request instead of four; and the lane's mel filter {offset, length, start, -}
-  const float4 *fft_post;    // [2][64]
+  // (512- and 256-point windows) the same two tables as one 16-byte record per lane and round of the post-processing pass,
+  // k = lane + 1 + 64 q: {fft_perm[k], fft_perm[padded / 2 - k], kn re, kn im} -- one request instead of four; and the lane's mel filter
+  // {offset, length, start, -}
+  const float4 *fft_post;    // [padded / 256][64]: two rounds at 512 points, one at 256
   const int4 *mel_rec;       // nbins
   // Dither (feature-window.cc:90-98): sample i of frame t += dither[t * win + i] * dither_value, before DC removal.  The
   // table holds the reference's own RandGauss draws for frame t of a fresh decoder process (nnet3_setup.h); null = off.

@@ -75,8 +75,8 @@ static void BuildFrameAndMelTables(const MfccOptions &o, const std::string &what
   t->win = o.WindowSize();
   t->shift = o.WindowShift();
   t->padded = o.PaddedWindowSize();
-  if (t->padded != 512 && t->padded != 2048)
-    Fail(what + ": padded window size " + std::to_string(t->padded) + " unsupported by the HIP FFT (need 512 or 2048)");
+  if (t->padded != 256 && t->padded != 512 && t->padded != 1024 && t->padded != 2048)
+    Fail(what + ": padded window size " + std::to_string(t->padded) + " unsupported by the HIP FFT (need 256, 512, 1024 or 2048)");
   t->nbins = o.num_bins;
   // window (feature-window.cc:113-125): computed in double, stored as float
   t->window.resize(t->win);

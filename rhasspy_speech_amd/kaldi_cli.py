@@ -55,6 +55,13 @@ def parse_command_line(argv: List[str]) -> Tuple[Dict[str, object], str, List[st
                 # given on the command line: overrides online.conf's value (util/parse-options.cc:328-345), so the library must not
                 # refuse the model for what the file says (rs_decode_opts.command_line_fixed)
                 opts["command_line_fixed"] = int(opts.get("command_line_fixed", 0)) | _FIXED_BIT[name]
+            elif name == "samp-freq":
+                # online2-cli-nnet3-decode-faster.cc:67-70: the rate of the samples on stdin (cli_main checks it against the model's;
+                # the wav binary registers no such option and refuses it)
+                try:
+                    opts["samp_freq"] = float(value)
+                except ValueError:
+                    raise ValueError(f'Invalid floating-point option "{value}"') from None
             elif name in _IGNORED:
                 pass
             else:
@@ -118,6 +125,8 @@ def wav_main(argv: List[str]) -> int:
     if len(pos) != 5:
         raise ValueError("usage: online2-wav-nnet3-latgen-faster [options] <nnet3-in> <fst-in> <spk2utt-rspecifier> <wav-rspecifier> <lattice-wspecifier>")
     final_mdl, hclg, spk2utt, wav_rspec, lat_wspec = pos
+    if "samp_freq" in opts:
+        raise ValueError("invalid option --samp-freq")
     wavs = dict(read_table(wav_rspec))
     spk = read_table(spk2utt)
     # The binary carries the iVector estimator's adaptation state from one utterance of a speaker to the next
@@ -146,7 +155,10 @@ def cli_main(argv: List[str]) -> int:
     if len(pos) != 4:
         raise ValueError("usage: online2-cli-nnet3-decode-faster [options] <nnet3-in> <fst-in> <word-symbol-table> <lattice-wspecifier>")
     final_mdl, hclg, _words, lat_wspec = pos
+    samp_freq = opts.pop("samp_freq", 16000.0)
     _lib, model = _load(opts, config, final_mdl, hclg)
+    # the binary hands --samp-freq to AcceptWaveform with every block (:148): a rate other than the model's ends it at the first one
+    model.check_sample_rate(samp_freq)
     stream = _lib.Stream(model)
     carry = b""
     while True:

@@ -177,6 +177,14 @@ class ModelSpec:
     chain_topology: bool = True      # forward/self-loop pdf classes (nnet3 chain models)
     dither: Optional[float] = None   # None: no --dither line, i.e. the reference's default 1.0 like conf/mfcc_hires.conf (feature-window.h:57)
     frame_length: Optional[float] = None   # ms; None: no --frame-length line (25 ms: a 512-point FFT); 100 ms pads to 2048 points
+    # --sample-frequency of mfcc.conf / fbank.conf (8000: a 200-sample window, the 256-point FFT; 22050 / 32000: 1024 points) and the
+    # band of the mel banks, None: --low-freq=20 / --high-freq=-400 as for 16 kHz (Kaldi's mfcc_hires for 8 kHz has 40 and -200)
+    sample_frequency: int = 16000
+    low_freq: Optional[float] = None
+    high_freq: Optional[float] = None
+    # mfcc.conf holds --sample-frequency and --use-energy=false and nothing else: the reference's defaults for the rest (23 bins,
+    # 13 cepstra, which num_mel_bins / num_ceps then have to say; low-freq 20, high-freq 0, dither 1.0)
+    mfcc_defaults: bool = False
     nnet_cmvn: bool = False          # --cmvn-config on the nnet input branch
     binary: bool = True
     xent_branch: bool = True         # extra output-xent branch (ignored by decoding), as chain recipes have
@@ -1501,9 +1509,16 @@ def write_model_dir(model_dir: Path, spec: ModelSpec, nnet=None) -> None:
     write_tree(model_dir / "model" / "model" / "tree", spec)
     conf = model_dir / "model" / "online" / "conf"
     conf.mkdir(parents=True, exist_ok=True)
-    if spec.feature_type == "mfcc":
+    low_freq = 20 if spec.low_freq is None else spec.low_freq
+    high_freq = -400 if spec.high_freq is None else spec.high_freq
+    if spec.feature_type == "mfcc" and spec.mfcc_defaults:
+        if (spec.num_mel_bins, spec.num_ceps) != (23, 13):
+            raise ValueError("mfcc_defaults: the reference's defaults are 23 mel bins and 13 cepstra")
+        (conf / "mfcc.conf").write_text(f"--sample-frequency={spec.sample_frequency}\n--use-energy=false\n")
+        online = ["--feature-type=mfcc", f"--mfcc-config={conf / 'mfcc.conf'}"]
+    elif spec.feature_type == "mfcc":
         mfcc = ["--use-energy=false", f"--num-mel-bins={spec.num_mel_bins}", f"--num-ceps={spec.num_ceps}",
-                "--low-freq=20", "--high-freq=-400", "--sample-frequency=16000"]
+                f"--low-freq={low_freq}", f"--high-freq={high_freq}", f"--sample-frequency={spec.sample_frequency}"]
         if spec.dither is not None:
             mfcc.append(f"--dither={spec.dither}")
         if spec.frame_length is not None:
@@ -1514,7 +1529,8 @@ def write_model_dir(model_dir: Path, spec: ModelSpec, nnet=None) -> None:
         _ = spec.feat_dim      # (refuses a type other than fbank)
         online = ["--feature-type=fbank"]
         if spec.fbank_config:
-            fb: Dict[str, object] = {"num-mel-bins": spec.num_mel_bins, "low-freq": 20, "high-freq": -400, "sample-frequency": 16000}
+            fb: Dict[str, object] = {"num-mel-bins": spec.num_mel_bins, "low-freq": low_freq, "high-freq": high_freq,
+                                     "sample-frequency": spec.sample_frequency}
             if spec.dither is not None:
                 fb["dither"] = spec.dither
             if spec.frame_length is not None:

@@ -1,8 +1,9 @@
 """Transcribe an audio stream on an MI355X.
 
 Same public surface as rhasspy_speech/transcribe_stream.py:18-129: `KaldiNnet3StreamTranscriber.async_transcribe`
-consumes an async iterable of raw s16le 16 kHz mono chunks (the bytes the reference writes to the stdin of
-`online2-cli-nnet3-decode-faster`, :76-82) and returns the decoded texts.  The library re-chunks to the binary's
+consumes an async iterable of raw s16le mono chunks at the model's sampling rate (the bytes the reference writes to the stdin of
+`online2-cli-nnet3-decode-faster`, :76-82; `samp_freq`, the binary's --samp-freq, says which: 16 kHz unless given, 8000 for a
+telephone model) and returns the decoded texts.  The library re-chunks to the binary's
 fixed 1024-sample ticks, so -- like the reference -- the result does not depend on how the caller slices the audio.
 `async_transcribe_with_partials` also reports the best path so far as the audio arrives (the "temporary transcript" of
 online2-tcp-nnet3-decode-faster.cc:302-318), and returns what `async_transcribe` returns.
@@ -39,6 +40,7 @@ class KaldiNnet3StreamTranscriber:
         acoustic_scale: float = 1.0,
         beam: float = 24.0,
         device_id: int = 0,
+        samp_freq: float = 16000.0,
     ):
         self.model_dir = Path(model_dir)
         self.graph_dir = Path(graph_dir)
@@ -48,10 +50,12 @@ class KaldiNnet3StreamTranscriber:
         self.acoustic_scale = acoustic_scale
         self.beam = beam
         self.device_id = device_id
+        self.samp_freq = samp_freq      # online2-cli-nnet3-decode-faster.cc:67-70 (the reference's Python never passes it)
         self._model: Optional[_lib.Model] = None
         self._words = None
         self._lat_model: Optional[_lib.Model] = None      # the same files, results keep their lattices (rescoring path)
         self._rescorers = {}
+        self._rate_error: Optional[str] = None      # what rs_model_check_sample_rate said about samp_freq when the model was loaded
         self.last_endpoint_rule = 0      # async_transcribe_until_endpoint: the rule (1..5) that ended the last call, 0 = the audio ended first
         self.last_adaptation: Optional[_lib.Adaptation] = None      # async_transcribe_continuous: the speaker's state after the last utterance
 
@@ -59,9 +63,24 @@ class KaldiNnet3StreamTranscriber:
         if self._model is None:
             opts = _lib.default_opts(max_active=self.max_active, lattice_beam=self.lattice_beam, beam=self.beam,
                                      acoustic_scale=1.0, device_id=self.device_id)
-            self._model = _lib.Model(self.model_dir, self.graph_dir, opts)
+            self._model = self._load_model(opts)
             self._words = read_words_txt(self.graph_dir / "words.txt")
         return self._model
+
+    def _load_model(self, opts) -> _lib.Model:
+        model = _lib.Model(self.model_dir, self.graph_dir, opts)
+        try:
+            model.check_sample_rate(self.samp_freq)
+        except _lib.RsError as e:
+            self._rate_error = str(e)
+        return model
+
+    def _open_stream(self, model: _lib.Model, adaptation=None) -> _lib.Stream:
+        """A stream on `model`, refused before any audio when `samp_freq` is not the model's rate: the binary hands --samp-freq to
+        AcceptWaveform with the first block (:148) and ends with "Sampling frequency mismatch, expected ..., got ..."."""
+        if self._rate_error is not None:
+            raise RuntimeError(f"Unexpected error running command online2-cli-nnet3-decode-faster (HIP): {self._rate_error}")
+        return _lib.Stream(model) if adaptation is None else _lib.Stream(model, adaptation=adaptation)
 
     @staticmethod
     def _accept_and_advance(stream, chunk) -> None:
@@ -142,7 +161,7 @@ class KaldiNnet3StreamTranscriber:
     async def _transcribe(self, audio_stream, lang_dir, nbest, max_fuzzy_cost, require_fuzzy, on_partial, until_endpoint=False,
                           endpoint_opts=None) -> List[str]:
         lang_dir = Path(lang_dir)
-        stream = _lib.Stream(self._ensure_loaded())
+        stream = self._open_stream(self._ensure_loaded())
         loop = asyncio.get_running_loop()
         reported: List[int] = []
         fired = 0
@@ -237,7 +256,7 @@ class KaldiNnet3StreamTranscriber:
         loop = asyncio.get_running_loop()
         tick_bytes = 2 * 1024
         state = adaptation
-        stream = _lib.Stream(model, adaptation=state)
+        stream = self._open_stream(model, adaptation=state)
         pending = bytearray()
         fed = 0                # bytes the current utterance has got
 
@@ -250,7 +269,7 @@ class KaldiNnet3StreamTranscriber:
             finally:
                 stream.close()
             self.last_adaptation = state
-            stream, fed = _lib.Stream(model, adaptation=state), 0
+            stream, fed = self._open_stream(model, adaptation=state), 0
             return self._texts(nbest_stdout, lang_dir, max_fuzzy_cost, require_fuzzy)
 
         try:
@@ -288,7 +307,7 @@ class KaldiNnet3StreamTranscriber:
         if self._lat_model is None:
             opts = _lib.default_opts(max_active=self.max_active, lattice_beam=self.lattice_beam, beam=self.beam, acoustic_scale=1.0,
                                      device_id=self.device_id, emit_lattice=1)
-            self._lat_model = _lib.Model(self.model_dir, self.graph_dir, opts)
+            self._lat_model = self._load_model(opts)
         key = str(new_lang_dir)
         if key not in self._rescorers:
             try:
@@ -297,7 +316,7 @@ class KaldiNnet3StreamTranscriber:
                 if "No value for disambiguation state" in str(e):
                     raise ValueError("No value for disambiguation state (#0)") from e       # transcribe_stream.py:150-151
                 raise
-        stream = _lib.Stream(self._lat_model)
+        stream = self._open_stream(self._lat_model)
         loop = asyncio.get_running_loop()
         try:
             async for chunk in audio_stream:
